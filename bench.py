@@ -59,6 +59,49 @@ def gen_sorted_reads(api, n_reads, n_species, L, mu, seed, device, abundance=Non
     return sp, out
 
 
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: bytes of the arrays (the files, .npy headers included, stay under 64 MB)
+DUMP_READS = 1 << 20           # per-read arrays longer than this are written as a fixed, seeded sample of this many rows (the C3 set fits whole)
+
+
+def dump_outputs(folder, res):
+    """What a caller of the timed path received from its last step, as <folder>/<name>.npy: every numeric array of the result (rep_of, status, hpc_err,
+    counters, ...) as float64 (with `<name>_index`, the rows written, where a sample was taken), and the centres as center_n_reads / center_id, the
+    draft and polished sequences as float32 character codes concatenated (center_draft / center_polished) with float64 offsets (`<name>_off`), and
+    the merged cluster ids (center_groups, center_groups_off).  Where the centres do not fit the rest of the budget, a seeded sample of them is written
+    (center_index).  Returns {name: shape}."""
+    os.makedirs(folder, exist_ok=True)
+    out = {}
+    arrs = {k_: v_ for k_, v_ in res.items() if isinstance(v_, np.ndarray) and v_.dtype.kind in "biuf"}
+    long_ = [k_ for k_, v_ in arrs.items() if v_.ndim == 1 and len(v_) > DUMP_READS]
+    cap = min(DUMP_READS, (DUMP_BYTES // 2) // (8 * (2 * len(long_) or 1)))          # sampled arrays and their row indices take at most half the budget
+    for k_, v_ in sorted(arrs.items()):
+        if k_ in long_:
+            idx = np.sort(np.random.default_rng(len(v_)).choice(len(v_), cap, replace=False))
+            out[k_ + "_index"] = idx.astype(np.float64); v_ = v_[idx]
+        out[k_] = np.asarray(v_, dtype=np.float64)
+    cen = list(res.get("centers", []))
+    left = DUMP_BYTES - sum(a_.nbytes for a_ in out.values())
+    cost = [4 * (len(c[2]) + len(c[3])) + 8 * (len(c[4]) + 6) for c in cen]           # bytes a centre adds to the arrays below (center_index included)
+    ci = np.arange(len(cen))
+    if sum(cost) + 24 > left:
+        ci = np.random.default_rng(len(cen)).permutation(len(cen))
+        ci = np.sort(ci[np.cumsum(np.asarray(cost)[ci]) <= left - 24])
+        out["center_index"] = ci.astype(np.float64)
+    cen = [cen[i] for i in ci]
+    out["center_n_reads"] = np.asarray([c[0] for c in cen], dtype=np.float64)
+    out["center_id"] = np.asarray([c[1] for c in cen], dtype=np.float64)
+    for nm_, j_ in (("center_draft", 2), ("center_polished", 3)):
+        s_ = [c[j_].encode() if isinstance(c[j_], str) else bytes(c[j_]) for c in cen]
+        out[nm_] = np.frombuffer(b"".join(s_), dtype=np.uint8).astype(np.float32)
+        out[nm_ + "_off"] = np.concatenate(([0], np.cumsum([len(x) for x in s_]))).astype(np.float64)
+    out["center_groups"] = np.asarray([g for c in cen for g in c[4]], dtype=np.float64)
+    out["center_groups_off"] = np.concatenate(([0], np.cumsum([len(c[4]) for c in cen]))).astype(np.float64)
+    assert sum(a_.nbytes for a_ in out.values()) <= DUMP_BYTES
+    for k_, a_ in out.items():
+        np.save(os.path.join(folder, k_ + ".npy"), a_)
+    return {k_: list(a_.shape) for k_, a_ in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,10 +127,15 @@ def main():
                          "reference's `--t N` partition (parallelize.batch_list total_nt), so the N-GPU membership is the reference's --t N membership of that set")
     ap.add_argument("--check-membership", action="store_true", help="strong scaling: after the timed region rank 0 replays the `--t N` schedule on one GPU and compares the membership")
     ap.add_argument("--master-port", type=int, default=0, help="--gpus N > 1 started directly: the rendezvous port of the ranks this process launches (0 = a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all; a fixed, seeded sample of the per-read arrays beyond 1 M reads)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` IS the N-GPU run: this process becomes `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>`,
+        # `python bench.py --gpus N` IS the N-GPU run: a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>`,
         # one rank per GPU over RCCL (backend nccl; NGSID_DIST_BACKEND=gloo only as a dev aid for more ranks than GPUs).  stdout is inherited, so rank 0's JSON line is this command's.
+        # (a child process, not exec: torch.cuda.device_count() below has already opened the HIP runtime in this one)
         port = args.master_port
         if not port:
             import socket
@@ -95,8 +143,10 @@ def main():
         if os.environ.get("NGSID_DIST_BACKEND", "nccl") == "nccl" and torch.cuda.device_count() < args.gpus:
             sys.exit("bench.py --gpus %d: this node shows %d GPU(s); one RCCL rank per GPU is required (NGSID_DIST_BACKEND=gloo lets ranks share a GPU, as a dev aid)" % (args.gpus, torch.cuda.device_count()))
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port),
-                                  os.path.abspath(__file__)] + sys.argv[1:])
+        import subprocess
+        rc = subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port),
+                              os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(rc if rc >= 0 else 128 - rc)          # (a launcher killed by a signal exits like a shell reports it)
     cfg = CONFIGS[args.config]
     if args.scaling is None:      # the BASELINE shape of the configuration: C4 / C5 are ONE global set over the GPUs of a node (strong); C2 / C3 are per-GPU workloads (weak)
         args.scaling = "strong" if (args.config in ("c4", "c5") and args.gpus > 1) else "weak"
@@ -193,6 +243,7 @@ def main():
         res = step(T)
     barrier(); dt = time.perf_counter() - t0
     trace("timed region done: %.2f s, stages %s" % (dt, {k_: round(v, 2) for k_, v in T.items()}))
+    dumped = dump_outputs(args.dump_outputs, res) if (args.dump_outputs and rank == 0) else None          # (outside the timed region)
     if os.environ.get("NGSID_BENCH_TRACE"):
         for f_ in ("/sys/fs/cgroup/cpu.stat", "/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.stat"):
             try: trace("%s: %s" % (f_, open(f_).read().replace("\n", " ")))
@@ -531,6 +582,7 @@ def main():
         out["config"]["baseline_config_of_this_line"] = ("%s of BASELINE.json, %s" % (args.config.upper(), "ONE global set split into the reference's `--t %d` batches (strong scaling)" % world if args.scaling == "strong" else
                                                          "its per-GPU shape repeated on every GPU with an independent read set per rank (weak scaling%s)" % ("; C3 is BASELINE's 1-GPU configuration" if args.config == "c3" else "")))
         out["config"]["eight_gpu_configurations"] = "BASELINE.json quotes C4 (10 M x 750 bp, 50 species) and C5 (2 M x 2 kb CCS, 20 species) on 8 GPUs as ONE global set: python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --config c4 --scaling strong --check-membership   (likewise --config c5)"
+    if dumped is not None: out["config"]["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if cli_leg is not None: out["config"]["cli"] = cli_leg
     if host_leg is not None: out["config"]["host_buffers_in"] = host_leg
     if res_stop is not None: out["config"]["with_stable_stop"] = {"reads_per_s": round(n_total / dt_stop, 1), "ms_per_step": round(dt_stop * 1e3, 2), "same_result": stop_same,
