@@ -16,20 +16,23 @@
 // The traceback flags of this kernel are SIGN bits of packed 16-bit differences (d - h, E - mx, e_ext - E, f_ext - F): exact only while no difference wraps.  The
 // largest magnitude is a cell at the "minus infinity" NEG16 (less one extension) against the largest score a pair of this kernel can reach - the bounds of
 // ngsid_align16_applicable (match <= 4, ext <= 4, open <= 16) with queries of at most 896 bases (the single-strip classes): ADVICE r4.
+// The row state is g = h - open rather than h (one subtraction per cell instead of the two of e_opn / f_opn).  The bound holds unchanged in that frame: the four
+// differences are the same numbers as before (e_opn = g_left, f_opn = g_up, d = g_diag + (score + open)); the one new value g = h - open stays above NEG16 - ext
+// (an h is at least -open - ext * 4000, a gap along a whole target of the int16 range); the diagonal constant match + open is at most 20.
 static_assert(-(NEG16) + 4 /* ext */ + 16 /* open */ + 4 /* match */ * 896 /* query rows */ < 32768, "packed sign-bit flags of k_sg_align16p would wrap");
 #define PKOP2(name, mnem) __device__ __forceinline__ int name(int a, int b) { int d; asm(mnem " %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 PKOP2(pp_sub_i16, "v_pk_sub_i16")
 PKOP2(pp_add_i16, "v_pk_add_i16")
 PKOP2(pp_max_i16, "v_pk_max_i16")
 PKOP2(pp_sub_u16, "v_pk_sub_u16")
-__device__ __forceinline__ int pp_lshr16(int a, int k2_s) { int d; asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(d) : "s"(k2_s), "v"(a)); return d; }  // per-half logical shift right; k2_s = the amount in BOTH halves of an SGPR (an inline constant would shift the high half by 0)
-// (inline asm: from the C expression the compiler builds and / or3 chains of the same length as the min / shift / or form they replace; the masks live in SGPRs)
+// (inline asm: the masks and selectors live in SGPRs - gfx9 VOP3 takes no literal)
 __device__ __forceinline__ int pp_bfi(int mask_s, int a, int b) { int d; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "s"(mask_s), "v"(a), "v"(b)); return d; }        // (a & mask) | (b & ~mask)
-__device__ __forceinline__ int pp_and_or(int a, int mask_s, int b) { int d; asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(mask_s), "v"(b)); return d; }  // (a & mask) | b
 #define PKOP2S(name, mnem) __device__ __forceinline__ int name(int a, int b) { int d; asm(mnem " %0, %1, %2" : "=v"(d) : "v"(a), "s"(b)); return d; }
 PKOP2S(pp_sub_i16_s, "v_pk_sub_i16")
 PKOP2S(pp_min_u16_s, "v_pk_min_u16")
 __device__ __forceinline__ int pp_mad_i16_sv(int a, int b_s, int c) { int d; asm("v_pk_mad_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b_s), "v"(c)); return d; }
+// byte permute of {a : b} (b = bytes 0..3); selectors 8..11 give 0xFF or 0x00 by the sign of bits 15, 31, 47, 63 = of the halves b.lo, b.hi, a.lo, a.hi
+__device__ __forceinline__ int pp_perm(int a, int b, int sel_s) { int d; asm("v_perm_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(sel_s)); return d; }
 __device__ __forceinline__ int pp_sgpr(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint8_t pp_perm_letter(uint8_t c) {          // same byte permutation as k_align16.hip: A,C,G,T -> 0..3, a,c,g,t -> 0x80..0x83
     const int b = ngsid_bcode(c);
@@ -54,7 +57,7 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
     uint8_t* tgt0 = smem; uint8_t* tgt1 = tgt0 + seq_lds; uint8_t* qry0 = tgt1 + seq_lds; uint8_t* qry1 = qry0 + seq_lds;
     uint64_t* tbblk = (uint64_t*)(smem + 4 * (size_t)seq_lds);            // traceback block: 64 steps x 8 lanes
     uint64_t* mytb0 = tb + (uint64_t)blockIdx.x * tb_words_per_wave * 2; uint64_t* mytb1 = mytb0 + tb_words_per_wave;
-    constexpr int NA = (R + 3) / 4;                                       // flag accumulators: four nibbles (16 bits) per half each
+    constexpr int NA = 2 * ((R + 7) / 8);                                 // flag accumulators: two per group of 8 rows, one (flag, pair) plane per byte
     const uint32_t nitems = item_off[PBINS];
 
     for (;;) {
@@ -100,37 +103,38 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
 
-        const int OPEN2 = pp_sgpr(PP(J.open[p0], J.open[p1])), EXT2 = pp_sgpr(PP(J.ext, J.ext));
-        const int MATCH2 = PP(J.match, J.match), NDIFF2 = pp_sgpr(PP(J.mismatch - J.match, J.mismatch - J.match));
+        const int OPEN2 = pp_sgpr(PP(J.open[p0], J.open[p1])), NOPEN2 = pp_sgpr(PP(-J.open[p0], -J.open[p1])), EXT2 = pp_sgpr(PP(J.ext, J.ext));
+        const int MATCHO2 = PP(J.match + J.open[p0], J.match + J.open[p1]), NDIFF2 = pp_sgpr(PP(J.mismatch - J.match, J.mismatch - J.match));   // diagonal: g_diag + score + open
         const int ONE2 = pp_sgpr(0x00010001);
-        const int MK1 = pp_sgpr(0x20002000), MK2 = pp_sgpr(0x40004000), MK3 = pp_sgpr((int)0x80008000u), MKN = pp_sgpr((int)0xF000F000u);      // flag-nibble masks of the step
-        const int SH2 = pp_sgpr(0x00020002), SH3 = pp_sgpr(0x00030003), SH4 = pp_sgpr(0x00040004);                                              // packed shift amounts
+        // (the v_perm selectors and the row masks of the flag planes are constants for the "s" operands of the asm: s_mov, which the compiler can rematerialise)
+        constexpr int SGN = 0x0B0A0908;                                   // v_perm: the signs of b.lo, b.hi, a.lo, a.hi as 0x00 / 0xFF bytes
+        constexpr int SEL0 = 0x06040200, SEL1 = 0x07050301;               // v_perm: the pair 0 / pair 1 bytes of the two accumulators of a row group
         const int mmax = m0 > m1 ? m0 : m1;
         const int steps = mmax + 63;
         const int own_lane0 = n0 > 0 ? (n0 - 1) / R : -1, own_lane1 = n1 > 0 ? (n1 - 1) / R : -1;
         int bestRowV0 = -(1 << 29), bestRowJ0 = 0, bestRowV1 = -(1 << 29), bestRowJ1 = 0;
-        int hl2[R], e2[R], qc2[R], nwq2[R];
+        int hl2[R], e2[R], qc2[R], nwq2[R];                                // hl2 = g = H - open of the last column (column -1: H = 0)
         const int i0 = lane * R;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = i0 + r;
             const int ca = i < n0 ? qry0[i] : 0x7C, cb = i < n1 ? qry1[i] : 0x7C;
             qc2[r] = PP(ca & 3, cb & 3); nwq2[r] = PP((ca & 0x7C) ? 0 : 0xffff, (cb & 0x7C) ? 0 : 0xffff);
-            hl2[r] = 0; e2[r] = PP(NEG16, NEG16);
+            hl2[r] = NOPEN2; e2[r] = PP(NEG16, NEG16);
         }
 
         auto forward = [&](auto OPc, auto NWc) {
             constexpr int OWN_P = decltype(OPc)::value; constexpr bool NOWILD = decltype(NWc)::value;
-            int hdiag2 = 0;                                               // H[i0-1][j-1], both pairs
-            int send_h = 0, send_f = PP(NEG16, NEG16);                    // bottom row of this lane for the next one
-            int keyRow0 = (int)0x80000000u, keyRow1 = (int)0x80000000u; const int jinv0 = 0xFFFF + lane;      // steady steps: packed (last-row value, -column) maxima
+            int hdiag2 = NOPEN2;                                          // g[i0-1][j-1], both pairs
+            int send_h = NOPEN2, send_f = PP(NEG16, NEG16);               // bottom row (g, F) of this lane for the next one
+            int keyRow0 = (int)0x80000000u, keyRow1 = (int)0x80000000u; const int jinv0 = 0xFFFF + lane;      // steady steps: packed (last-row g, -column) maxima
             // The steps in which EVERY lane stands inside both targets (tau - lane in [0, min(m0, m1)) for all 64 lanes: 63 <= tau < min(m0, m1), 84 % of the steps of a 750-base
             // pair) need none of the range masks: their own instance of the step (STEADY) drops the mask selects of the state (one per row, three per step) and the range tests.
             auto step = [&](int tau, auto STc) {
                 constexpr bool STEADY = decltype(STc)::value;
                 const int j = tau - lane;
-                // lane 0 has no source lane: the shift leaves it the `old` operand - 0 for H (row -1 of the matrix), minus infinity for F (no select needed)
-                const int hup = __builtin_amdgcn_update_dpp(0, send_h, 0x138, 0xf, 0xf, false), fup = __builtin_amdgcn_update_dpp(PP(NEG16, NEG16), send_f, 0x138, 0xf, 0xf, false);
+                // lane 0 has no source lane: the shift leaves it the `old` operand - -open for g (H = 0 in row -1 of the matrix), minus infinity for F (no select needed)
+                const int hup = __builtin_amdgcn_update_dpp(NOPEN2, send_h, 0x138, 0xf, 0xf, false), fup = __builtin_amdgcn_update_dpp(PP(NEG16, NEG16), send_f, 0x138, 0xf, 0xf, false);
                 const bool a0 = STEADY || (j >= 0 && j < m0), a1 = STEADY || (j >= 0 && j < m1);      // STEADY: every lane stands inside both targets
                 const int l0 = tgt0[STEADY ? j : (a0 ? j : 0)], l1 = tgt1[STEADY ? j : (a1 ? j : 0)];
                 const int tc2 = PP(l0 & 3, l1 & 3);
@@ -139,35 +143,39 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                 int hu2 = hup, f2 = fup, hd2 = hdiag2;
                 int acc[NA], cap2 = 0;
 #pragma unroll
-                for (int a = 0; a < NA; ++a) acc[a] = 0;
-#pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    const int e_ext = pp_sub_i16_s(e2[r], EXT2), e_opn = pp_sub_i16_s(hl2[r], OPEN2); const int E = pp_max_i16(e_ext, e_opn);
-                    const int f_ext = pp_sub_i16_s(f2, EXT2), f_opn = pp_sub_i16_s(hu2, OPEN2); const int F = pp_max_i16(f_ext, f_opn);
+                    // the row state is g = H - open: the gap opens of E and F are the g of the left and of the upper cell, and the diagonal adds open back
+                    const int e_ext = pp_sub_i16_s(e2[r], EXT2); const int E = pp_max_i16(e_ext, hl2[r]);
+                    const int f_ext = pp_sub_i16_s(f2, EXT2); const int F = pp_max_i16(f_ext, hu2);
                     const int z = pp_min_u16_s(qc2[r] ^ tc2, ONE2);                                // 1 = letters differ
-                    int sc = pp_mad_i16_sv(z, NDIFF2, MATCH2);                                     // match / mismatch ...
-                    if constexpr (!NOWILD) sc = sc & nwq2[r] & nwt2;                                // ... / 0 for wildcards (and for columns outside the target, whose cells nothing reads)
+                    int sc = pp_mad_i16_sv(z, NDIFF2, MATCHO2);                                    // match / mismatch + open ...
+                    if constexpr (!NOWILD) { const int nw = nwq2[r] & nwt2; sc = pp_sel(nw, sc, OPEN2); }   // ... / 0 + open for wildcards (and for columns outside the target, whose cells nothing reads)
                     const int d = pp_add_i16(hd2, sc);
                     const int mx = pp_max_i16(E, F); const int h = pp_max_i16(d, mx);
-                    // COMPLEMENT flags (1 = "not equal"): bit0 h!=d, bit1 mx!=E (F>E), bit2 E!=e_ext (opened), bit3 F!=f_ext (opened)
-                    // each flag is the SIGN of a packed difference (smaller - larger: negative iff they differ); the four signs are moved to bits 12..15 of their half by
-                    // per-half shifts and merged with bit-field inserts (6 operations instead of 4 min + 3 shift + ors), and the nibble enters its accumulator at the TOP:
-                    // the k-th of the cnt rows of an accumulator ends in nibble (4 - cnt + k) of its half (round 4)
+                    const int g = pp_sub_i16_s(h, OPEN2);
+                    // COMPLEMENT flags (1 = "not equal"): 0 h!=d, 1 mx!=E (F>E), 2 E!=e_ext (opened), 3 F!=f_ext (opened)
+                    // each flag is the SIGN of a packed difference (smaller - larger: negative iff they differ).  One v_perm turns the four signs of two differences into
+                    // 0x00 / 0xFF bytes (flag 0 pair 0, flag 0 pair 1, flag 1 pair 0, flag 1 pair 1; flags 2 / 3 alike) and one bit-field insert keeps bit r & 7 of each:
+                    // accumulator 2 (r >> 3) holds flags 0 / 1 of the rows of group r >> 3 as four bit planes of 8 rows, accumulator 2 (r >> 3) + 1 flags 2 / 3
                     const int s0 = pp_sub_i16(d, h), s1 = pp_sub_i16(E, mx), s2 = pp_sub_i16(e_ext, E), s3 = pp_sub_i16(f_ext, F);
-                    int c = pp_bfi(MK1, pp_lshr16(s1, SH2), pp_lshr16(s0, SH3));
-                    c = pp_bfi(MK2, pp_lshr16(s2, ONE2), c);
-                    c = pp_bfi(MK3, s3, c);
-                    acc[r >> 2] = pp_and_or(c, MKN, pp_lshr16(acc[r >> 2], SH4));                   // four nibbles per half and accumulator
+                    const int pa = pp_perm(s1, s0, SGN), pb = pp_perm(s3, s2, SGN);
+                    int& a01 = acc[2 * (r >> 3)]; int& a23 = acc[2 * (r >> 3) + 1];
+                    if ((r & 7) == 0) { a01 = pa & 0x01010101; a23 = pb & 0x01010101; }                     // first row of a group: no zeroing
+                    else { a01 = pp_bfi(0x01010101 << (r & 7), pa, a01); a23 = pp_bfi(0x01010101 << (r & 7), pb, a23); }
                     hd2 = hl2[r];
-                    hl2[r] = STEADY ? h : pp_sel(am2, h, hl2[r]);
+                    hl2[r] = STEADY ? g : pp_sel(am2, g, hl2[r]);
                     e2[r] = E;                 // not masked (see k_align16.hip: before a lane's first column E only relaxes to -open, after its last it is not used)
-                    hu2 = h; f2 = F;
-                    if (r == OWN_P) cap2 = h;
+                    hu2 = g; f2 = F;
+                    if (r == OWN_P) cap2 = g;
                 }
-                // traceback words: pair 0 = the low halves of the accumulators, pair 1 = the high halves (complement nibbles); accumulator a sits at bits [16 a, 16 a + 16)
+                // traceback words: bits [32 k, 32 k + 32) = row group k, byte f of the group = flag f (complement), bit b of the byte = row 8 k + b; pair 0 takes the
+                // even bytes of the group's two accumulators, pair 1 the odd ones
                 unsigned long long w0 = 0, w1 = 0;
 #pragma unroll
-                for (int a = 0; a < NA; ++a) { w0 |= (unsigned long long)((unsigned)acc[a] & 0xffffu) << (16 * a); w1 |= (unsigned long long)((unsigned)acc[a] >> 16) << (16 * a); }
+                for (int k = 0; k < NA / 2; ++k) {
+                    w0 |= (unsigned long long)(unsigned)pp_perm(acc[2 * k + 1], acc[2 * k], SEL0) << (32 * k);
+                    w1 |= (unsigned long long)(unsigned)pp_perm(acc[2 * k + 1], acc[2 * k], SEL1) << (32 * k);
+                }
                 mytb0[(uint64_t)tau * 64 + lane] = w0;
                 mytb1[(uint64_t)tau * 64 + lane] = w1;
                 if (STEADY) { hdiag2 = hup; send_h = hu2; send_f = f2; }
@@ -178,7 +186,7 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                     const int jinv = jinv0 - tau;
                     keyRow0 = max(keyRow0, (int)(((unsigned)cap2 << 16) | (unsigned)jinv));
                     keyRow1 = max(keyRow1, (int)(((unsigned)cap2 & 0xFFFF0000u) | (unsigned)jinv));
-                } else {   // last query row: first maximum over the columns
+                } else {   // last query row: first maximum over the columns (of g: the same order as H within a pair)
                     const int v0 = PLO(cap2), v1 = PHI(cap2);
                     const bool b0_ = a0 && lane == own_lane0 && v0 > bestRowV0; bestRowV0 = b0_ ? v0 : bestRowV0; bestRowJ0 = b0_ ? j : bestRowJ0;
                     const bool b1_ = a1 && lane == own_lane1 && v1 > bestRowV1; bestRowV1 = b1_ ? v1 : bestRowV1; bestRowJ1 = b1_ ? j : bestRowJ1;
@@ -188,7 +196,7 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
             const int st_lo = 63 < steps ? 63 : steps, st_hi = mmin > st_lo ? (mmin < steps ? mmin : steps) : st_lo;
             int tau = 0;
             for (; tau < st_lo; ++tau) step(tau, std::false_type{});
-            // two steps per iteration: the state a step leaves (one register per row: the new H of the row, while the old one is still the diagonal input of the row below)
+            // two steps per iteration: the state a step leaves (one register per row: the new g of the row, while the old one is still the diagonal input of the row below)
             // is consumed by the second step in place, instead of being copied back into the loop's registers after every step (~38 v_mov per step of ~340 instructions)
             for (; tau + 1 < st_hi; tau += 2) { step(tau, std::true_type{}); step(tau + 1, std::true_type{}); }
             for (; tau < st_hi; ++tau) step(tau, std::true_type{});
@@ -205,11 +213,12 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
 #undef PCASE
             default: if (nowild) forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::true_type{}); else forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::false_type{}); break;
         }
-        // last target column of each pair: the state holds H[i][m-1] for every row
+        bestRowV0 += PLO(OPEN2); bestRowV1 += PHI(OPEN2);                  // g -> H
+        // last target column of each pair: the state holds g[i][m-1] = H[i][m-1] - open for every row
         int bestColV0 = -(1 << 29), bestColI0 = 0x7fffffff, bestColV1 = -(1 << 29), bestColI1 = 0x7fffffff;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int i = i0 + r; const int v0 = PLO(hl2[r]), v1 = PHI(hl2[r]);
+            const int i = i0 + r; const int v0 = PLO(hl2[r]) + PLO(OPEN2), v1 = PHI(hl2[r]) + PHI(OPEN2);
             if (i < n0 && v0 > bestColV0) { bestColV0 = v0; bestColI0 = i; }
             if (i < n1 && v1 > bestColV1) { bestColV1 = v1; bestColI1 = i; }
         }
@@ -235,7 +244,8 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
             if (colV > best) { best = colV; ei = colI; ej = m - 1; }
             ei = pp_sgpr(ei); ej = pp_sgpr(ej); best = pp_sgpr(best);
 
-            // ---- traceback (uniform over the wave): the bookkeeping of k_sg_align16, the word of cell (i, j) is at step j + i / R, lane i / R, nibble i % R
+            // ---- traceback (uniform over the wave): the bookkeeping of k_sg_align16, the word of cell (i, j) is at step j + i / R, lane i / R, row r = i % R:
+            // bit (r % 8) of the four bytes of its 32-bit half r / 8
             if (Jt->bp) for (int x = lane; x < Jt->bp_windows * 4; x += 64) Jt->bp[p * (uint64_t)Jt->bp_windows * 4 + x] = -1;
             const int K = Jt->k; const int mid = Jt->match_id ? Jt->match_id[p] : K;
             const uint64_t kmask = (K >= 64) ? ~0ull : ((1ull << K) - 1);
@@ -279,9 +289,8 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                     const int tau = jk + l;
                     if ((l >> 3) == blk_g && tau <= blk_hi && tau >= blk_hi - 63) {
                         const uint64_t word = tbblk[(blk_hi - tau) * 8 + (l & 7)];
-                        const int a = r >> 2; const int cnt_a = (R - 4 * a) < 4 ? (R - 4 * a) : 4;
-                        const int sh = 16 * a + 4 * (4 - cnt_a + (r & 3));
-                        vk = (int)((~(word >> sh)) & 15);        // stored complemented -> bit0 diag, bit1 E>=F, bit2 E extends, bit3 F extends
+                        const unsigned x = (unsigned)(word >> (32 * (r >> 3) + (r & 7)));
+                        vk = (int)(~(x & 1u) & 1u) | (int)(~(x >> 7) & 2u) | (int)(~(x >> 14) & 4u) | (int)(~(x >> 21) & 8u);   // stored complemented -> bit0 diag, bit1 E>=F, bit2 E extends, bit3 F extends
                         inb = true;
                     }
                 }
