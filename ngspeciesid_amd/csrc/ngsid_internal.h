@@ -199,15 +199,12 @@ struct AlignJob {            // device pointers
     const uint32_t* pair_list2; const uint32_t* npairs_dev2;
     int clip;        // k_ed_align only (round 5, aln_mode 3): != 0 = overlap-span clipping of the recorded span / break points
 };
+// the clustering / polishing aligner (k_align.hip: routes every pair to one of the kernels of k_align.hip, k_align16.hip, k_align16p.hip)
 int32_t ngsid_launch_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open = 1 << 20, uint32_t min_qlen = 0);   // min_qlen: lower bound of the query lengths (lets empty length classes be skipped)
 bool ngsid_align16_applicable(const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open);
 #define NGSID_ALIGN16_MAXLEN 4000u      // sequences up to this length run the packed int16 aligners (score range)
-#define NGSID_ALIGN_LONG_CLASS 5        // list / counter index of the pairs above it in a partitioned batch (aln_cls list 5, aln_ctr[13])
-int32_t ngsid_launch_align16(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t min_qlen = 0, uint32_t long_len = 0);
-int32_t ngsid_side_streams(ngsid_ctx* ctx);          // creates ctx->side / events on first use
-int32_t ngsid_paired_tb_words(ngsid_ctx* ctx, int cls, uint64_t npairs, uint32_t max_tlen, uint64_t* words);      // k_align16p.hip: two pairs per wave for every single-strip length class (queries of up to 896 bases)
-int32_t ngsid_launch_paired_class(ngsid_ctx* ctx, const AlignJob& job, int cls, uint32_t max_tlen, hipStream_t st, uint64_t* tb);
 int32_t ngsid_partition_pairs(ngsid_ctx* ctx, const AlignJob& job, uint32_t long_len = 0);      // query-length classes {<=256, <=512, <=768, <=896, rest}: lists in ctx->aln_cls, counts in ctx->aln_ctr[8..12]
+int32_t ngsid_side_streams(ngsid_ctx* ctx);          // creates ctx->side / events on first use
 int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out);   // k_ed_align.hip (uses qseq..npairs, bp, bp_windows, window, span)
 
 typedef unsigned int ngsid_v4u __attribute__((ext_vector_type(4)));
