@@ -213,13 +213,19 @@ typedef struct {
                                  columns count - read ends that do not align stay out of the layers, as minimap2's q_begin / q_end keep them out of racon's edlib call
                                  (consensus.py:121: PAF without CIGAR = first anchor to last anchor of the chain, k = 15 for -x map-ont; racon src/overlap.cpp
                                  find_breaking_points aligns only that span).  A read without such a run contributes nothing.  The CLI uses it where read ends are KNOWN
-                                 to overhang the backbone: polishing primer-trimmed drafts (--primer_file / --remove_universal_tails) */
+                                 to overhang the backbone: polishing primer-trimmed drafts (--primer_file / --remove_universal_tails);
+                                 | NGSID_ALN_SUBGRAPH (flag bit, combines with 0 - 3): racon's sub-graph layers, see below */
     int32_t stop_when_stable; /* 1 = a group whose backbone comes back unchanged from an iteration is not polished again: the polisher is a
                                  deterministic function of (backbone, reads), so every further iteration would return the same string and
                                  the same n_used - the result is identical, only the time differs.  0 = always run `iters` iterations */
     int32_t single_below;     /* round 6: a polishing window with FEWER layers than this is built as ONE graph (racon's own order: backbone, then the layers by first
                                  position), see ngsid_poa_params_t.single_below; 0 = off */
 } ngsid_polish_params_t;
+/* ngsid_polish_params_t.aln_mode flag: SUB-GRAPH LAYERS (racon src/window.cpp).  A window layer that does not span its window (racon's 1 % slack) is aligned globally to
+ * the sub-graph between its first and last backbone positions [a0, a1] - every node reached backwards (in-edges, aligned siblings) from backbone position a1 without
+ * entering a backbone node below a0; nodes without a predecessor / successor inside it are sources / ends - instead of end-free to the whole window graph.  Level-0
+ * layers only: tile consensuses of the upper levels and the draft consensus are unchanged.  Off by default; without the flag every call is what it was. */
+#define NGSID_ALN_SUBGRAPH 16
 
 /* (a16,a17) replaces run_racon's (minimap2 -> racon) x racon_iter chain (consensus.py:107-126).
  * backbones: one sequence per group (qual ignored); reads grouped like ngsid_poa_consensus; a read may be listed under ONE group only

@@ -61,11 +61,17 @@ def poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=0, band=
     return PoaParams(int(mode), int(match), int(mismatch), int(gap), int(tile_depth), int(band), int(node_cap), int(trim), int(single_below))
 
 
+ALN_SUBGRAPH = 16      # include/ngsid.h NGSID_ALN_SUBGRAPH: flag bit of aln_mode (racon's sub-graph alignment of the layers that do not span their window)
+
+
 def polish_params(iters=2, window=500, quality_threshold=10.0, error_threshold=0.3, match=3, mismatch=-5, gap=-4,
-                  k=13, w=20, tile_depth=0, band=0, node_cap=0, aln_match=2, aln_mismatch=-2, aln_open=3, aln_ext=1, trim=1, aln_mode=2, stop_when_stable=1, single_below=0):
-    """Defaults = racon 1.4.x (-w 500 -q 10 -e 0.3 -m 3 -x -5 -g -4), iters = --racon_iter (NGSpeciesID:212)."""
+                  k=13, w=20, tile_depth=0, band=0, node_cap=0, aln_match=2, aln_mismatch=-2, aln_open=3, aln_ext=1, trim=1, aln_mode=2, stop_when_stable=1, single_below=0,
+                  subgraph_layers=False):
+    """Defaults = racon 1.4.x (-w 500 -q 10 -e 0.3 -m 3 -x -5 -g -4), iters = --racon_iter (NGSpeciesID:212).
+    subgraph_layers: ORs ALN_SUBGRAPH into aln_mode."""
+    mode = int(aln_mode) | (ALN_SUBGRAPH if subgraph_layers else 0)
     return PolishParams(int(iters), int(window), float(quality_threshold), float(error_threshold), int(match), int(mismatch), int(gap),
-                        int(k), int(w), int(tile_depth), int(band), int(node_cap), int(aln_match), int(aln_mismatch), int(aln_open), int(aln_ext), int(trim), int(aln_mode), int(stop_when_stable), int(single_below))
+                        int(k), int(w), int(tile_depth), int(band), int(node_cap), int(aln_match), int(aln_mismatch), int(aln_open), int(aln_ext), int(trim), mode, int(stop_when_stable), int(single_below))
 
 
 class ReadSet:

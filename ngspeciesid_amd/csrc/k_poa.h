@@ -4,6 +4,11 @@
 
 struct PSeq { const uint8_t* s; const uint8_t* q; int32_t len, uw; uint32_t cw; int32_t mode, a0, a1; };   // 40 bytes
 
+// PSeq.mode of a polishing layer that does not span its window when ngsid_polish_params_t.aln_mode carries NGSID_ALN_SUBGRAPH: aligned globally to the sub-graph
+// between its backbone positions [a0, a1] (racon src/window.cpp; oracle/ngsid_oracle_poa.c POA_SUBGRAPH, same value).  Internal: not one of the NGSID_POA_* modes,
+// and only the sub-graph instances of the tile kernel (k_poa_tile*_sub) handle it.
+#define POA_MODE_SUBGRAPH 3
+
 struct PoaJobSet {
     const PSeq* seqs; const PSeq* bbs; const uint32_t* seq_idx; const uint32_t* job_off; const int32_t* job_bb; uint32_t njobs; const uint32_t* job_list; uint32_t nrun;   /* job_list != null: this launch runs tiles job_list[0..nrun) (band-edge redo); else all njobs */
     const uint8_t* job_final;                 /* != null (round 5, polish trim 3): job_final[j] != 0 = tile j ends its unit: its consensus is NOT trimmed (trim_tiles counts as 0) */
@@ -19,8 +24,8 @@ struct PoaJobSet {
 __host__ __device__ inline uint32_t poa_ntiles(uint32_t n, uint32_t D) { if (n == 0) return 0; if (D == 0 || n <= D) return 1; const uint32_t r = n % D; return (r != 0 && r < (D + 1) / 2) ? n / D : (n + D - 1) / D; }
 
 size_t poa_lds_bytes(int Vc, int Ec, int Lm, int BW);
-int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band);
+int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band, bool sub = false);      // sub: launch the sub-graph instance (the job set may hold POA_MODE_SUBGRAPH sequences)
 // device-driven hierarchy: scratch for all three band instances sized once (poa_prepare), then launches that neither allocate nor touch the host
-struct PoaPlan { int Vcap, Ecap, Lmax; uint32_t nwg_main, nwg_redo; int band0; };
+struct PoaPlan { int Vcap, Ecap, Lmax; uint32_t nwg_main, nwg_redo; int band0; bool sub = false; };      // sub: scratch also sized for the sub-graph instances
 int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs);
-int32_t poa_launch(ngsid_ctx* ctx, const PoaPlan& P, PoaJobSet J, int band, bool redo, uint32_t* work_ctr);
+int32_t poa_launch(ngsid_ctx* ctx, const PoaPlan& P, PoaJobSet J, int band, bool redo, uint32_t* work_ctr, bool sub = false);      // sub: needs P.sub

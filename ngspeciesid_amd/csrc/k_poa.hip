@@ -75,6 +75,10 @@ struct GG {   // the graph in the workgroup's HBM scratch, every array indexed b
     // per sequence position (the alignment being merged) when the LDS cannot hold them: aligned rank, existing / final rank
     __device__ __forceinline__ uint16_t& alnode(uint32_t i) const { return *(uint16_t*)(base + 3u * s32 + 3u * s64 + 2u * s16 + 3u * s8 + 2u * se16 + se32 + 2u * i); }
     __device__ __forceinline__ uint16_t& nodeof(uint32_t i) const { return *(uint16_t*)(base + 3u * s32 + 3u * s64 + 2u * s16 + 3u * s8 + 2u * se16 + se32 + sl + 2u * i); }
+    // sub-graph instances only (k_poa_tile*_sub, scratch sized by poa_graph_bytes(.., sub)): rank of backbone position p (kept through every merge), and the per-rank
+    // sub-graph state of the alignment in progress (SM_* bits)
+    __device__ __forceinline__ uint16_t& bbr(uint32_t p) const { return *(uint16_t*)(base + 3u * s32 + 3u * s64 + 2u * s16 + 3u * s8 + 2u * se16 + se32 + 2u * sl + 2u * p); }
+    __device__ __forceinline__ uint8_t& sm(uint32_t i) const { return *(base + 3u * s32 + 3u * s64 + 3u * s16 + 3u * s8 + 2u * se16 + se32 + 2u * sl + i); }
 };
 // LDS working set.  ~10 KB per tile for 750-base reads, so sixteen tiles (four waves per SIMD) are resident per CU.  The hot arrays sit at
 // COMPILE-TIME offsets so the row loop spends no SGPRs on them.  Layout (BW = band width), alignment phases | consensus phase:
@@ -209,9 +213,11 @@ __device__ __forceinline__ int band_lo(int anchor, const BandMap& m, int BW) {
     return (int)lo;
 }
 
+template <bool SUB = false>
 __device__ __forceinline__ void tile_add_first(const GG& g, const PSeq& S, TS& st, int lane)
 {
     for (int i = lane; i < S.len; i += 64) {
+        if constexpr (SUB) g.bbr(i) = (uint16_t)i;             // the first sequence of a window graph is its backbone: position i is rank i
         g.cm(i) = S.s[i]; g.ar(i) = (uint32_t)i | ((uint32_t)i << 16); g.cov(i) = S.cw; g.of(i) = (i + 1 < S.len) ? 1 : 0; g.far(i) = 0;
         g.pp(i) = ((i > 0) ? (uint32_t)(i - 1) : (uint32_t)NONE16) | ((uint32_t)NONE16 << 16);
         g.ww(i) = (i > 0) ? (unsigned long long)(unsigned)(wtof(S, i - 1) + wtof(S, i)) : 0ull;
@@ -231,6 +237,87 @@ __device__ __forceinline__ int ov_next(const GG& g, int nov, int r, int from, in
         if (m) return x0 + __builtin_ctzll(m);
     }
     return -1;
+}
+
+// ---- sub-graph layers (POA_MODE_SUBGRAPH; the k_poa_tile*_sub instances only).  oracle subgraph_mask: the sub-graph of a layer spanning backbone positions [a0, a1]
+// holds every node reached backwards - through in-edges and aligned rings - from backbone node a1 without entering a backbone node below a0.  sm[] per rank:
+enum { SM_IN = 1, SM_BLK = 2 /* backbone below a0: never entered */, SM_DONE = 4 /* in-edges and ring walked */, SM_SUCC = 8 /* a successor is in the sub-graph */,
+       SM_PRED = 16 /* a predecessor is */ };
+__device__ __forceinline__ bool sm_inside(unsigned v) { return (v & (SM_IN | SM_BLK)) == SM_IN; }
+__device__ __forceinline__ unsigned sm_or(const GG& g, int t, unsigned bits)      // returns the old byte
+{
+    const unsigned sh = 8u * (unsigned)(t & 3);
+    return (atomicOr((unsigned int*)&g.sm((uint32_t)(t & ~3)), bits << sh) >> sh) & 0xffu;
+}
+// Ranks are swept from the top down in 64-rank chunks.  Inside a chunk the marks spread along runs of "predecessor = previous rank" in one step of bit arithmetic, the
+// other in-edges and the rings of newly marked ranks are walked lane-parallel until the chunk's set stops growing; marks below the chunk go to sm[] (atomic OR) and are
+// picked up when the sweep gets there.  A ring sibling can sit ABOVE the rank that reaches it (new nodes are inserted in front of the next aligned node): such a mark
+// starts another sweep from there.  Every rank is walked once (SM_DONE); the sweeps end when no mark lands above the chunk that made it.
+__device__ void sub_mask(const GG& g, int V, int nov, int L0, int a0, int a1, int lane)
+{
+    if (a1 < 0 || a1 >= L0) a1 = L0 - 1; if (a0 < 0) a0 = 0;
+    for (int r = lane; r < V; r += 64) g.sm(r) = 0;
+    mem_sync();
+    for (int p = lane; p < a0 && p < L0; p += 64) g.sm(g.bbr(p)) = SM_BLK;
+    mem_sync();
+    const int top = __builtin_amdgcn_readfirstlane((int)g.bbr(a1));
+    if (lane == 0) g.sm(top) |= SM_IN;                     // (a1 < a0 would leave the start blocked: an empty sub-graph, the layer is dropped as by the oracle)
+    mem_sync();
+    int hi = top, lo = top;                                  // the ranks that may hold a node of the sub-graph whose edges are not walked yet lie in [lo, hi]
+    for (int sweep = 0; hi >= 0 && sweep <= V; ++sweep) {
+        int up_hi = -1, up_lo = 0x7fffffff;
+        for (int c0 = hi & ~63; c0 >= 0 && c0 + 63 >= lo; c0 -= 64) {
+            const int r = c0 + lane; const bool ok = r < V;
+            const unsigned mv = ok ? (unsigned)g.sm(r) : (unsigned)SM_BLK;
+            const unsigned long long B = __ballot(mv & SM_BLK);
+            unsigned long long M = __ballot(sm_inside(mv)), Dn = __ballot(mv & SM_DONE);
+            if (!(M & ~Dn)) continue;
+            const uint32_t ppv = ok ? g.pp(r) : 0xFFFFFFFFu; const int rg = ok ? (int)g.ring(r) : r; const bool many = ok && (g.cm(r) & 0x80);
+            const int p0 = ppv & 0xffff, p1 = ppv >> 16;
+            // chain step: lane x marks lane x - 1 (an in-edge from the previous rank, which is not blocked)
+            const unsigned long long C = __ballot(lane > 0 && (p0 == r - 1 || p1 == r - 1) && !((B >> (lane - 1)) & 1ull));
+            unsigned long long S = 0; bool haspred = false; int lo_l = 0x7fffffff;
+            for (;;) {
+                unsigned long long Gs = C;                   // Gs bit x: rank x reaches x - s through chain steps
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) { M |= (M & Gs) >> s; Gs &= Gs << s; }
+                const unsigned long long N = M & ~Dn;
+                if (!N) break;
+                Dn |= N;
+                unsigned long long T = 0, TS = 0;            // this lane's marks inside the chunk (TS: as a predecessor)
+                if ((N >> lane) & 1ull) {
+                    auto tail = [&](int t) {                 // in-edge tail: t < r
+                        if (t >= c0) { if (!((B >> (t - c0)) & 1ull)) { T |= 1ull << (t - c0); TS |= 1ull << (t - c0); haspred = true; } }
+                        else { const unsigned o = sm_or(g, t, SM_IN | SM_SUCC); if (!(o & SM_BLK)) { haspred = true; if (!(o & SM_IN)) lo_l = min(lo_l, t); } }
+                    };
+                    if (p0 != NONE16) tail(p0);
+                    if (p1 != NONE16) tail(p1);
+                    if (many) for (int e = 0; e < nov; ++e) if ((int)g.ov_head(e) == r) tail((int)g.ov_tail(e));
+                    for (int u = rg, k = 0; u != r && k < V; u = (int)g.ring(u), ++k) {
+                        if (u >= c0 && u < c0 + 64) { if (!((B >> (u - c0)) & 1ull)) T |= 1ull << (u - c0); }
+                        else {
+                            const unsigned o = sm_or(g, u, SM_IN);
+                            if (!(o & (SM_IN | SM_BLK))) { if (u < c0) lo_l = min(lo_l, u); else { up_hi = max(up_hi, u); up_lo = min(up_lo, u); } }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) { T |= __shfl_xor(T, d); TS |= __shfl_xor(TS, d); }
+                M |= T; S |= TS;
+            }
+            if (ok) {
+                unsigned nv = mv | (((M >> lane) & 1ull) ? SM_IN : 0u) | (((Dn >> lane) & 1ull) ? SM_DONE : 0u) | (((S >> lane) & 1ull) ? SM_SUCC : 0u) | (haspred ? SM_PRED : 0u);
+                if (nv != mv) g.sm(r) = (uint8_t)nv;
+            }
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) lo_l = min(lo_l, __shfl_xor(lo_l, d));
+            lo = min(lo, lo_l);
+            mem_sync();
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { up_hi = max(up_hi, __shfl_xor(up_hi, d)); up_lo = min(up_lo, __shfl_xor(up_lo, d)); }
+        hi = __builtin_amdgcn_readfirstlane(up_hi); lo = __builtin_amdgcn_readfirstlane(up_lo);
+    }
 }
 
 // one pass of the heaviest-bundle recurrence over ranks [rb, V) in RANK space.  Per 64-rank chunk every lane fetches the first two
@@ -549,7 +636,8 @@ __device__ __forceinline__ unsigned poa_row_finish(const int (&X)[CPL], const in
     return dpack;
 }
 
-template <int CPL, int MODE>
+// SUB (the sub-graph instances): rows outside the sub-graph of a POA_MODE_SUBGRAPH layer carry flags 1 | 2 (see the prepass) and become rows of minus infinity.
+template <int CPL, int MODE, bool SUB = false>
 __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w, int32_t* Hg, uint8_t* Dg, uint8_t* Dfull, const PSeq& S, int V, int nov, int gp_, int sm_, int sn_, int lane, int& bestv_out, int& bestpk_out, int& nslow_out)
 {
     constexpr int BW = 64 * CPL;
@@ -704,6 +792,13 @@ __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w,
                 for (int c = 0; c < CPL; ++c) if (l0 + lane * CPL + c == L && hprev[c] > bestv) { bestv = hprev[c]; bestpk = (r << 8) | (lane * CPL + c); }
             }
             ++r;
+        } else if (SUB && (rfl & 3) == 3) {
+            // ---- outside the sub-graph: minus infinity in every column (a successor inside may still read the row: LDS ring, or its HBM copy under flag 8 below);
+            //      the direction bytes are never read
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) hprev[c] = 0;
+            poa_row_tail_store<CPL>(ring0 + (r & (HR - 1)) * RS, stage0 + (r & (TBR - 1)) * BW, hprev, 0x03030303u);
+            ++r;
         } else {
             // ---- generic row (no predecessor, semi-global mode, far or many predecessors): walk the in-edge list in HBM
             ++nslow;
@@ -784,7 +879,7 @@ __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w,
                 *(ngsid_v4u*)(dstb + q * 16) = dir_pack32(a, b);
             }
             // rows with more than two in-edges keep their byte rows (row info of the block's ranks is still in this chunk's registers)
-            unsigned long long irr = __ballot(((chi >> 24) & 2u) != 0) & (0xFFFFFFFFull << ((r - TBR) & 63));
+            unsigned long long irr = __ballot(SUB ? ((chi >> 24) & 3u) == 2u : ((chi >> 24) & 2u) != 0) & (0xFFFFFFFFull << ((r - TBR) & 63));      // (SUB: not the rows outside)
             while (irr) {
                 const int bq = __builtin_ctzll(irr); irr &= irr - 1;
                 const int row = ((r - 1) & ~63) + bq;
@@ -811,7 +906,7 @@ __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w,
             pk[xq] = dir_pack32(a, b);
         }
         if (V & (TBR - 1)) {         // a partial block was never flushed: its rows with more than two in-edges go to the byte rows now
-            unsigned long long irr = __ballot(((chi >> 24) & 2u) != 0) & (0xFFFFFFFFull << (blk & 63));
+            unsigned long long irr = __ballot(SUB ? ((chi >> 24) & 3u) == 2u : ((chi >> 24) & 2u) != 0) & (0xFFFFFFFFull << (blk & 63));
             while (irr) {
                 const int bq = __builtin_ctzll(irr); irr &= irr - 1;
                 const int row = cb + bq;
@@ -860,7 +955,7 @@ __device__ __attribute__((noinline)) FwdOut poa_forward_call(unsigned long long 
 #endif
 
 // align S to the graph and merge it.  returns 0 = dropped (no valid end cell), 1 = added, 2 = does not fit
-template <int CPL>
+template <int CPL, bool SUB = false>
 __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& w, int32_t* Hg, uint8_t* Dg, uint8_t* Dfull, const PoaJobSet& J, const PSeq& S, TS& st, int lane, int& edge_out)
 {
     constexpr int BW = 64 * CPL;
@@ -876,6 +971,8 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     //          64 near row (one or two predecessors, all within the LDS ring, band shifts 0..DLO_MAX),
     //          128 first row of a tight run of chain rows (its length replaces dlo0; see the last pass)
     const BandMap bm = band_map(S, st.L0, BW);
+    const bool sub = SUB && mode == POA_MODE_SUBGRAPH;     // racon's sub-graph layer: the global DP on the sub-graph of the span (mask built here, rows re-flagged below)
+    if constexpr (SUB) if (sub) sub_mask(g, V, st.nov, st.L0, S.a0, S.a1, lane);
     // One STREAMING pass, two 64-rank chunks per iteration: the graph is stored in rank order, so a rank's record (tails of its first two in-edges, anchor,
     // letter, flags) is one coalesced load per array; the only dependent loads are the anchors of the two predecessors (their band starts are recomputed
     // from them).  far[] (a successor more than HR ranks behind: the row needs an HBM copy) is a graph property kept by the merge, so the rows of a tight
@@ -894,9 +991,9 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     if (lt_lds) { for (int a = lane; a < st.L0; a += 64) lt[a] = (uint16_t)band_lo(a, bm, BW); lds_sync(); }
     auto BL = [&](int anchor) __attribute__((always_inline)) -> int { return lt_lds ? (int)lt[anchor] : band_lo(anchor, bm, BW); };
     for (int rb = 0; rb < V; rb += 128) {
-        uint32_t ppv[2], arv[2]; int cmv[2], ofv[2], frv[2], lp0[2], lp1[2];
+        uint32_t ppv[2], arv[2]; int cmv[2], ofv[2], frv[2], lp0[2], lp1[2], smv[2];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { const int r = rb + u * 64 + lane; const bool ok = r < V; ppv[u] = ok ? g.pp(r) : 0xFFFFFFFFu; arv[u] = ok ? g.ar(r) : 0u; cmv[u] = ok ? (int)g.cm(r) : 0; ofv[u] = ok ? (int)g.of(r) : 1; frv[u] = ok ? (int)g.far(r) : 0; }
+        for (int u = 0; u < 2; ++u) { const int r = rb + u * 64 + lane; const bool ok = r < V; ppv[u] = ok ? g.pp(r) : 0xFFFFFFFFu; arv[u] = ok ? g.ar(r) : 0u; cmv[u] = ok ? (int)g.cm(r) : 0; ofv[u] = ok ? (int)g.of(r) : 1; frv[u] = ok ? (int)g.far(r) : 0; smv[u] = (sub && ok) ? (int)g.sm(r) : 0; }
 #pragma unroll
         for (int u = 0; u < 2; ++u) { const int a = ppv[u] & 0xffff, b = ppv[u] >> 16; lp0[u] = a != NONE16 ? (int)g.anchor(a) : 0; lp1[u] = b != NONE16 ? (int)g.anchor(b) : 0; }
 #pragma unroll
@@ -916,6 +1013,13 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
                 if (!(fl & 3)) {
                     if (d0 == 1 && d1 == 0 && dl0 <= 1) fl |= 16 | (dl0 << 5);
                     else if (d0 <= HR && d1 <= HR && dl0 <= DLO_MAX && dl1 <= DLO_MAX) fl |= 64;
+                }
+            }
+            if constexpr (SUB) if (sub && ok) {        // oracle poa_align, POA_SUBGRAPH: source / sink relative to the sub-graph
+                if (!sm_inside((unsigned)smv[u])) { fl = 3 | (fl & 8); d0 = d1 = dl0 = dl1 = 0; }      // outside: flags 1 | 2 (a pair no other row has), the HBM copy flag stays
+                else {
+                    if (!(smv[u] & SM_PRED)) { fl = 1 | (fl & (4 | 8)); d0 = d1 = dl0 = dl1 = 0; }    // every predecessor outside: a source row
+                    fl = (fl & ~4) | ((smv[u] & SM_SUCC) ? 0 : 4);                                    // no successor inside: an end row
                 }
             }
             // TIGHT runs of the forward pass: consecutive chain rows whose band moves by one column per row, that hold no end cell, need no HBM copy and lie
@@ -967,9 +1071,9 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
       else fo = poa_forward_call<CPL, NGSID_POA_GLOBAL>((unsigned long long)g.base, g.s32, g.s64, g.s16, g.s8, g.se16, g.se32, g.sl, (unsigned long long)Hg, (unsigned long long)Dg, (unsigned long long)Dfull, L, V, st.nov, gp, J.m, J.n, lane);
       bestv = fo.bestv; bestpk = fo.bestpk; nslow = fo.nslow; }
 #else
-    if (local) poa_forward<CPL, NGSID_POA_LOCAL>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
-    else if (mode == NGSID_POA_SEMI) poa_forward<CPL, NGSID_POA_SEMI>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
-    else poa_forward<CPL, NGSID_POA_GLOBAL>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
+    if (local) poa_forward<CPL, NGSID_POA_LOCAL, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
+    else if (mode == NGSID_POA_SEMI) poa_forward<CPL, NGSID_POA_SEMI, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
+    else poa_forward<CPL, NGSID_POA_GLOBAL, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);      // (POA_MODE_SUBGRAPH: global on the sub-graph)
 #endif
     if (POA_PHC(J) && lane == 0) { atomicAdd(&PHS(J)[5], (unsigned long long)V); atomicAdd(&PHS(J)[6], (unsigned long long)nslow); }
     mem_sync();                                       // direction rows must have landed before the traceback pulls them back
@@ -1255,6 +1359,7 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
         } else new_nodes(1);
         // existing nodes the sequence goes through: their final ranks
         for (int i = lane; i < L; i += 64) if (!((ch_new[i >> 6] >> (i & 63)) & 1ull)) nodeof.set(i, RM(nodeof.get(i)));
+        if constexpr (SUB) for (int p = lane; p < st.L0; p += 64) g.bbr(p) = (uint16_t)RM(g.bbr(p));      // backbone nodes move with their ranks
         mem_sync();
         PH(J, 23, tpu);
     }
@@ -1318,15 +1423,15 @@ size_t poa_lds_bytes(int Vc, int Ec, int Lm, int BW)
     const size_t cons = poa_al16((size_t)2 * Vc) + poa_al16(((size_t)Vc + 31) / 32 * 4);
     return aln > cons ? aln : cons;
 }
-// HBM scratch bytes of one workgroup for the graph arrays
-static size_t poa_graph_bytes(int Vc, int Ec, int Lm)
+// HBM scratch bytes of one workgroup for the graph arrays (sub: + GG::bbr / GG::sm of the sub-graph instances)
+static size_t poa_graph_bytes(int Vc, int Ec, int Lm, bool sub)
 {
     auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t n = (size_t)Vc + 1;
-    return 3 * al(4 * n) + 3 * al(8 * n) + 2 * al(2 * n) + 3 * al(n) + 2 * al(2 * (size_t)Ec) + al(4 * (size_t)Ec) + 2 * al(2 * (size_t)Lm);
+    return 3 * al(4 * n) + 3 * al(8 * n) + 2 * al(2 * n) + 3 * al(n) + 2 * al(2 * (size_t)Ec) + al(4 * (size_t)Ec) + 2 * al(2 * (size_t)Lm) + (sub ? al(2 * n) + al(n) : 0);
 }
 
-template <int CPL>
+template <int CPL, bool SUB = false>
 __device__ __forceinline__ void poa_tile_body(const PoaJobSet& J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr)
 {
     constexpr int BW = 64 * CPL;
@@ -1380,11 +1485,11 @@ __device__ __forceinline__ void poa_tile_body(const PoaJobSet& J, uint8_t* gscra
             // at most two attempts: when the graph is full (code 2) the tile is emitted and the sequence starts / joins a fresh one
             for (int attempt = 0; attempt < 2; ++attempt) {
                 if (st.V == 0) {
-                    if (bbi >= 0) { const PSeq B = JC.bbs[bbi]; tile_add_first(g, B, st, lane); }
+                    if (bbi >= 0) { const PSeq B = JC.bbs[bbi]; tile_add_first<SUB>(g, B, st, lane); }
                     else { if (S.len > st.capV) ++ndrop; else { tile_add_first(g, S, st, lane); st.members = 1; } break; }
                 }
                 nrows += (unsigned)st.V;
-                const int rcode = tile_align_add<CPL>(g, w, Hg, Dg, Dfull, J, S, st, lane, edge);
+                const int rcode = tile_align_add<CPL, SUB>(g, w, Hg, Dg, Dfull, J, S, st, lane, edge);
                 if (rcode == 1) { st.members += 1; break; }
                 if (rcode == 0 || attempt == 1) { ++ndrop; break; }
                 tile_emit(g, w, JC, job, st, lane);
@@ -1411,9 +1516,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_poa_tile2(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<2>(J, gscratch, gbytes, work_ctr); }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_poa_tile4(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<4>(J, gscratch, gbytes, work_ctr); }
+// The same with sub-graph layers (POA_MODE_SUBGRAPH, ngsid_polish_params_t.aln_mode & NGSID_ALN_SUBGRAPH): launched only for the level-0 tiles of such polishing calls, so the
+// instances above keep their code, registers and occupancy.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(POA_W1, POA_W1)))
+void k_poa_tile1_sub(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<1, true>(J, gscratch, gbytes, work_ctr); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_poa_tile2_sub(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<2, true>(J, gscratch, gbytes, work_ctr); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_poa_tile4_sub(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<4, true>(J, gscratch, gbytes, work_ctr); }
 
 // ------------------------------------------------------------------------------------------------ host side
-int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band)
+// one launch of the instance for the band width (sub: the sub-graph instance)
+static int32_t poa_launch_tile(ngsid_ctx* ctx, const PoaJobSet& J, int BW, bool sub, uint32_t nwg, size_t lds, size_t gbytes, uint32_t* work_ctr)
+{
+    typedef void (*TileFn)(PoaJobSet, uint8_t*, size_t, uint32_t*);
+    const TileFn fn = BW == 64 ? (sub ? k_poa_tile1_sub : k_poa_tile1) : BW == 128 ? (sub ? k_poa_tile2_sub : k_poa_tile2) : (sub ? k_poa_tile4_sub : k_poa_tile4);
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(fn, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr);
+    HIPCHK(ctx, hipGetLastError());
+    return NGSID_OK;
+}
+int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band, bool sub)
 {
     if (J.njobs == 0) return NGSID_OK;
     if (!J.job_list) J.nrun = J.njobs;
@@ -1429,19 +1552,15 @@ int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band)
     if (ngsid_opt(ctx, "poa_tiles_per_cu", 0) > 0) per_cu = std::max(1, std::min(per_cu, (int)ngsid_opt(ctx, "poa_tiles_per_cu", 0)));
     uint32_t nwg = (uint32_t)std::min<uint64_t>(J.nrun, (uint64_t)ctx->n_cu * per_cu);
     const size_t cells = (size_t)J.Vcap * BW;
-    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax);
+    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax, sub);
     if (ctx->poa_h.n < nwg * cells) HIPCHK(ctx, ctx->poa_h.alloc(nwg * cells));
     if (ctx->poa_d.n < nwg * cells * 3 / 2) HIPCHK(ctx, ctx->poa_d.alloc(nwg * cells * 3 / 2));
     if (ctx->poa_g.n < nwg * gbytes) HIPCHK(ctx, ctx->poa_g.alloc(nwg * gbytes));
     J.Hglob = ctx->poa_h.p; J.dirglob = ctx->poa_d.p; J.covglob = nullptr; J.stat_rows = ctx->prof ? ctx->stat.p : nullptr;
     if (ctx->poa_ctr.n < 1) HIPCHK(ctx, ctx->poa_ctr.alloc(16));
     HIPCHK(ctx, hipMemsetAsync(ctx->poa_ctr.p, 0, sizeof(uint32_t), ctx->stream));
-    ProfScope ps_(ctx, "k_poa_tile");
-    if (BW == 64) { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile1, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, ctx->poa_ctr.p); }
-    else if (BW == 128) { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile2, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, ctx->poa_ctr.p); }
-    else { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile4, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, ctx->poa_ctr.p); }
-    HIPCHK(ctx, hipGetLastError());
-    return NGSID_OK;
+    ProfScope ps_(ctx, sub ? "k_poa_tile_sub" : "k_poa_tile");
+    return poa_launch_tile(ctx, J, BW, sub, nwg, lds, gbytes, ctx->poa_ctr.p);
 }
 
 // ---- device-driven hierarchy (poa_host.hip): one scratch allocation for the main band and the two wider redo instances, launches without host work
@@ -1458,7 +1577,7 @@ int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs)
     const int B0 = P.band0 <= 64 ? 64 : (P.band0 <= 128 ? 128 : 256);
     P.band0 = B0;
     if (P.Vcap > 0xFFF0 || P.Ecap > 0xFFF0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA graph capacity exceeds 16-bit indices (sequence too long for the tile engine)");
-    const size_t gbytes = poa_graph_bytes(P.Vcap, P.Ecap, P.Lmax);
+    const size_t gbytes = poa_graph_bytes(P.Vcap, P.Ecap, P.Lmax, P.sub);
     // resident workgroups per CU; halved when the scratch does not fit (several contexts sharing one GPU, very long reads): the persistent
     // workgroups pull tiles from a queue, so fewer of them only lowers the parallelism
     for (int shrink = 1;; shrink *= 2) {
@@ -1483,20 +1602,17 @@ int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs)
     }
     return NGSID_OK;
 }
-int32_t poa_launch(ngsid_ctx* ctx, const PoaPlan& P, PoaJobSet J, int BW, bool redo, uint32_t* work_ctr)
+int32_t poa_launch(ngsid_ctx* ctx, const PoaPlan& P, PoaJobSet J, int BW, bool redo, uint32_t* work_ctr, bool sub)
 {
+    if (sub && !P.sub) NGSID_FAIL(ctx, NGSID_ERR_ARG, "internal: sub-graph POA launch on a plan without its scratch");
     if (J.g >= 0) NGSID_FAIL(ctx, NGSID_ERR_ARG, "POA gap score must be negative");
     if ((long long)J.m * J.Lmax >= 65536 || J.m < 0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA local score range exceeds 16 bits (match %d x length %d)", J.m, J.Lmax);
     const size_t lds = poa_lds_bytes(J.Vcap, J.Ecap, J.Lmax, BW);
     if (lds > 160 * 1024) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);      // (the caller checks all three instances before it starts)
     const uint32_t nwg = redo ? P.nwg_redo : P.nwg_main;
     if (nwg == 0) return NGSID_OK;
-    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax);
+    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax, P.sub);      // (the stride the scratch was allocated with)
     J.Hglob = ctx->poa_h.p; J.dirglob = ctx->poa_d.p; J.covglob = nullptr; J.stat_rows = ctx->prof ? ctx->stat.p : nullptr;
-    ProfScope ps_(ctx, redo ? "k_poa_tile_redo" : "k_poa_tile");
-    if (BW == 64) { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile1, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr); }
-    else if (BW == 128) { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile2, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr); }
-    else { HIPCHK(ctx, hipFuncSetAttribute((const void*)k_poa_tile4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hipLaunchKernelGGL(k_poa_tile4, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr); }
-    HIPCHK(ctx, hipGetLastError());
-    return NGSID_OK;
+    ProfScope ps_(ctx, sub ? (redo ? "k_poa_tile_sub_redo" : "k_poa_tile_sub") : (redo ? "k_poa_tile_redo" : "k_poa_tile"));
+    return poa_launch_tile(ctx, J, BW, sub, nwg, lds, gbytes, work_ctr);
 }

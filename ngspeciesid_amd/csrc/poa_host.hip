@@ -36,7 +36,7 @@ __global__ void k_make_pseq_reads(const uint8_t* seq, const uint8_t* qual, const
     out[i] = S;
 }
 
-struct HierParams { int m, n, g, band, node_cap, D, upper_mode; bool want_cov; int trim_tiles; int single_below = 0; };      // single_below: ngsid_poa_params_t.single_below (units the caller marked with single_maxlen)
+struct HierParams { int m, n, g, band, node_cap, D, upper_mode; bool want_cov; int trim_tiles; int single_below = 0; bool sub = false; };      // single_below: ngsid_poa_params_t.single_below (units the caller marked with single_maxlen); sub: level 0 may hold POA_MODE_SUBGRAPH layers (the sub-graph tile instances run it)
 
 // Runs all units to completion.  level0: device PSeq array (nseq0 entries) whose max length is maxlen0;
 // bbs: device backbone PSeqs (may be null), maxbb = longest backbone.
@@ -97,7 +97,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
             DevBuf<unsigned long long> d_ph; static const bool want_ph = getenv("NGSID_POA_PHASES") != nullptr;
             if (want_ph) { HIPCHK(ctx, d_ph.alloc(24 * 256)); HIPCHK(ctx, hipMemsetAsync(d_ph.p, 0, 192 * 256, ctx->stream)); J.phase_cycles = d_ph.p; J.phase_detail = atoi(getenv("NGSID_POA_PHASES")) >= 2; }
             if (level == 0) ht.mark("L0 alloc + upload");
-            int32_t rc = poa_run_jobs(ctx, J, hp.band); if (rc) return rc;
+            int32_t rc = poa_run_jobs(ctx, J, hp.band, hp.sub && level == 0); if (rc) return rc;
             if (level == 0) ht.mark("L0 kernel");
             uint32_t h_flags[4];
             h_out_n.resize(njobs); h_out_len.resize((size_t)njobs * slots); h_out_cw.resize((size_t)njobs * slots); h_out_span.resize((size_t)njobs * slots * 2);
@@ -120,7 +120,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
                 HIPCHK(ctx, Lv->job_list.reserve(redo.size()));
                 HIPCHK(ctx, hipMemcpyAsync(Lv->job_list.p, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, ctx->stream));
                 J.job_list = Lv->job_list.p; J.nrun = (uint32_t)redo.size();
-                rc = poa_run_jobs(ctx, J, bw); if (rc) return rc;
+                rc = poa_run_jobs(ctx, J, bw, hp.sub && level == 0); if (rc) return rc;
                 rc = download(); if (rc) return rc;
                 ctx->poa_redo_tiles += redo.size();
             }
@@ -421,7 +421,7 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
     levels_est = std::min(std::max(levels_est, 1), C_MAXLV - 2);
     uint32_t cap[2]; cap[0] = njobs0;
     { const uint64_t e1 = hp.D > 0 ? (njobs0 + (uint64_t)hp.D - 1) / (uint64_t)hp.D * (uint64_t)slots + U : U; cap[1] = (uint32_t)std::min<uint64_t>(njobs0, e1 + e1 / 4 + 1024); }
-    PoaPlan plan{(int)capV, (int)(3 * capV / 2), Lmax, 0, 0, band0};
+    PoaPlan plan{(int)capV, (int)(3 * capV / 2), Lmax, 0, 0, band0, hp.sub};
     { int32_t rc = poa_prepare(ctx, plan, njobs0); if (rc) return rc; }
     // ---- buffers
     const bool need_cov = hp.want_cov || hp.trim_tiles;
@@ -469,13 +469,13 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
             J.out = Lv.out; J.out_len = Lv.out_len; J.out_cw = Lv.out_cw; J.out_n = Lv.out_n; J.out_cov = Lv.out_cov; J.out_span = Lv.out_span;
             J.dropped = d_ctrl.p + C_FLAGS; J.slot_overflow = d_ctrl.p + C_FLAGS + 1;
             J.job_list = nullptr; J.nrun = 0; J.nrun_dev = d_ctrl.p + C_NJOBS + par;
-            int32_t rc = poa_launch(ctx, plan, J, band0, false, d_ctrl.p + C_WORK + 3 * level); if (rc) return rc;
+            int32_t rc = poa_launch(ctx, plan, J, band0, false, d_ctrl.p + C_WORK + 3 * level, hp.sub && level == 0); if (rc) return rc;
             int stage = 0;
             for (int bw = band0 * 2; bw <= 256; bw *= 2, ++stage) {          // band-edge check (oracle run_tile): flagged tiles run again, whole, with twice the band
                 uint32_t* cnt = d_ctrl.p + C_REDO + 2 * level + stage;
                 hipLaunchKernelGGL(k_poa_redo_list, dim3(std::min<uint32_t>((cap[par] + 255) / 256, 1024u)), dim3(256), 0, ctx->stream, Lv.out_n, d_ctrl.p + C_NJOBS + par, Lv.job_list, cnt, d_ctrl.p + C_REDO_TOTAL);
                 PoaJobSet R = J; R.job_list = Lv.job_list; R.nrun_dev = cnt;
-                rc = poa_launch(ctx, plan, R, bw, true, d_ctrl.p + C_WORK + 3 * level + 1 + stage); if (rc) return rc;
+                rc = poa_launch(ctx, plan, R, bw, true, d_ctrl.p + C_WORK + 3 * level + 1 + stage, hp.sub && level == 0); if (rc) return rc;
             }
             hipLaunchKernelGGL(k_poa_unit_scan, dim3(U), dim3(256), 0, ctx->stream, H, Lv, par);
             hipLaunchKernelGGL(k_poa_unit_offsets, dim3(1), dim3(1024), 0, ctx->stream, H, par);
@@ -712,7 +712,8 @@ __global__ void k_orient(const uint8_t* __restrict__ seq, const uint8_t* __restr
 __global__ __launch_bounds__(256) void k_layers(const uint8_t* __restrict__ oseq, const uint8_t* __restrict__ oqual, const uint64_t* __restrict__ off,
                          const uint32_t* __restrict__ pair_read, const uint32_t* __restrict__ pair_group, uint64_t npairs, int nwinmax,
                          const int32_t* __restrict__ bp, const int32_t* __restrict__ span, const int32_t* __restrict__ blen /* per group */,
-                         int W, double qthr, double ethr, PSeq* __restrict__ lay, uint16_t* __restrict__ valid /* 0 = no layer, else 1 + its first window position */, int* __restrict__ maxlen_out)
+                         int W, double qthr, double ethr, int sub /* NGSID_ALN_SUBGRAPH: a layer that does not span its window gets POA_MODE_SUBGRAPH */,
+                         PSeq* __restrict__ lay, uint16_t* __restrict__ valid /* 0 = no layer, else 1 + its first window position */, int* __restrict__ maxlen_out)
 {
     const int lane = threadIdx.x & 63;
     const uint64_t t = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -744,7 +745,7 @@ __global__ __launch_bounds__(256) void k_layers(const uint8_t* __restrict__ oseq
     const int ws = wdx * W; const int wlen = polish_wlen(Bl, W, wdx);
     const int begin = tf - ws, end = tl - ws; const int offset = (int)(0.01 * (double)wlen);
     PSeq S; S.s = oseq + rb + qf; S.q = oqual ? oqual + rb + qf : nullptr; S.len = len; S.uw = 1; S.cw = 1; S.a0 = begin; S.a1 = end;
-    S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : NGSID_POA_SEMI;
+    S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : (sub ? POA_MODE_SUBGRAPH : NGSID_POA_SEMI);
     if (lane == 0) { lay[t] = S; valid[t] = (uint16_t)((begin < 0 ? 0 : (begin > 65533 ? 65533 : begin)) + 1); if (len > __atomic_load_n(maxlen_out, __ATOMIC_RELAXED)) atomicMax(maxlen_out, len); }      // (millions of atomics on one word would serialise)
 }
 
@@ -949,14 +950,14 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
             J.qseq = oseq.p; J.qoff = RD.off; J.tseq = BB.seq; J.toff = BB.off; J.qidx = d_pair_read.p; J.tidx = d_pair_group.p; J.npairs = NP;
             J.match = prm->aln_match; J.mismatch = prm->aln_mismatch; J.ext = prm->aln_ext; J.k = 1; J.open = d_open.p; J.match_id = nullptr;
             J.score = nullptr; J.ncols = nullptr; J.nmatch = nullptr; J.region = nullptr; J.bp = d_bp.p; J.bp_windows = nwinmax; J.window = W; J.span = d_span.p;
-            int aln_mode = prm->aln_mode == 2 ? 1 : prm->aln_mode;
+            int aln_mode = prm->aln_mode & ~NGSID_ALN_SUBGRAPH; if (aln_mode == 2) aln_mode = 1;      // (the sub-graph flag is a rule of the window layers, not of this aligner)
             if (aln_mode == 3) { aln_mode = 1; J.clip = 1; }          // edit distance + overlap-span clipping (include/ngsid.h)
             if (aln_mode == 1) rc = ngsid_launch_ed_align(ctx, J, RD.maxlen, maxb, want_aln ? d_dist.p : nullptr);          // unit-cost, bit-parallel (k_ed_align.hip)
             else rc = ngsid_launch_align(ctx, J, RD.maxlen, maxb, prm->aln_open);
             if (rc) return rc;
             const uint64_t T = NP * (uint64_t)nwinmax;
             { ProfScope ps_(ctx, "k_layers"); hipLaunchKernelGGL(k_layers, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, ctx->stream, oseq.p, RD.qual ? oqual.p : nullptr, RD.off, d_pair_read.p, d_pair_group.p, NP, nwinmax,
-                               d_bp.p, d_span.p, d_blen.p, W, prm->quality_threshold, prm->error_threshold, (PSeq*)d_lay_raw.p, d_valid.p, flag.p); }
+                               d_bp.p, d_span.p, d_blen.p, W, prm->quality_threshold, prm->error_threshold, (prm->aln_mode & NGSID_ALN_SUBGRAPH) ? 1 : 0, (PSeq*)d_lay_raw.p, d_valid.p, flag.p); }
             HIPCHK(ctx, hipGetLastError());
             h_valid.resize(T);
             HIPCHK(ctx, hipMemcpyAsync(&max_layer, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1056,6 +1057,7 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
         bool any_tgs = prm->trim == 2; for (uint32_t g = 0; g < G; ++g) any_tgs = any_tgs || (tgs[g] && prm->trim);
         HierParams hp{prm->match, prm->mismatch, prm->gap, prm->band > 0 ? prm->band : (RD.maxlen <= NGSID_POA_BAND64_MAXLEN ? 64 : 128), prm->node_cap, prm->tile_depth, NGSID_POA_GLOBAL, any_tgs, (prm->trim >= 2 ? 1 : 0) | (prm->trim == 3 ? 4 : 0)};      // trim_tiles: 1 = trim tile consensuses, 4 = except the tile that ends a unit (trim 3)
         hp.single_below = prm->single_below > 0 ? prm->single_below : 0;
+        hp.sub = (prm->aln_mode & NGSID_ALN_SUBGRAPH) != 0;
         if (hp.single_below > 0) for (size_t u = 0; u < units.size(); ++u) {       // windows with few layers: ONE graph; the longest sequence that can enter it = the longest READ behind its layers, or the window
             Unit& U = units[u]; if (U.done || U.seqs.size() >= (size_t)hp.single_below) continue;
             uint32_t mx = (uint32_t)std::max(1, bb_len[U.bb]);

@@ -107,6 +107,13 @@ def _single_below(args):
     return pipeline.SINGLE_BELOW if v is None else int(v)
 
 
+def _polish_prm(args, node_cap, clip):
+    """the polisher's parameters of a CLI run; clip: the backbones are primer-trimmed (include/ngsid.h: aln_mode 3, trim 3).  --racon_subgraph_layers sets
+    NGSID_ALN_SUBGRAPH in both flows."""
+    return polish_params(iters=args.racon_iter, k=args.k, w=args.w, tile_depth=(getattr(args, "poa_tile_depth", 0) if getattr(args, "poa_tile_depth", 0) > 0 else pipeline.TILE_DEPTH), band=getattr(args, "poa_band", 0), node_cap=node_cap, trim=3 if clip else 2, aln_mode=3 if clip else 2,
+                         stop_when_stable=0 if getattr(args, "polish_all_iterations", False) else 1, single_below=_single_below(args), subgraph_layers=getattr(args, "racon_subgraph_layers", False))
+
+
 def _write(args, fn, *a, **kw):
     bg = getattr(args, "_writers", None)
     if bg is None:
@@ -549,8 +556,7 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
     if getattr(args, "racon", False) and args.racon_iter >= 0:
         p_off = np.concatenate(([0], np.cumsum([len(x) for x in polish_lists]))).astype(np.uint64)
         bb = ReadSet.from_strings([(polish_backbones or {}).get(m[1], m[2]) for m in merged])
-        prm = polish_params(iters=args.racon_iter, k=args.k, w=args.w, tile_depth=(getattr(args, "poa_tile_depth", 0) if getattr(args, "poa_tile_depth", 0) > 0 else pipeline.TILE_DEPTH), band=getattr(args, "poa_band", 0), node_cap=node_cap, trim=3 if clip else 2, aln_mode=3 if clip else 2,
-                            stop_when_stable=0 if getattr(args, "polish_all_iterations", False) else 1, single_below=_single_below(args))      # clip: backbones are primer-trimmed (include/ngsid.h: aln_mode 3, trim 3)
+        prm = _polish_prm(args, node_cap, clip)
         ro = np.concatenate(polish_lists).astype(np.uint32)
         want_paf = not getattr(args, "skip_paf", False)
         its_aln = None

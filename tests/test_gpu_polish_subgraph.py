@@ -1,0 +1,150 @@
+"""NGSID_ALN_SUBGRAPH: racon's sub-graph alignment of the window layers that do not span their window (csrc/k_poa.hip k_poa_tile*_sub).  The oracle is the
+definition: ongsid_polish* with ongsid_debug_polish_rules bit 1 on the node-indexed tile engine (engine 0), aln_mode without the flag bit."""
+import ctypes, os, time
+import numpy as np
+import pytest
+
+from ngspeciesid_amd import synth
+from ngspeciesid_amd._capi import ReadSet, polish_params, ALN_SUBGRAPH
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+pytestmark = pytest.mark.gpu
+
+
+def _oracle_call(oracle, name, bb, rs, off, prm, **kw):
+    """the oracle's restatement of a call with NGSID_ALN_SUBGRAPH: the bit comes off aln_mode, the rule is switched on (bit 1; with aln_mode 3 also bit 0, the same
+    overlap-span clipping).  The switches are process-global state of the oracle library: restored in any case."""
+    mode = int(prm.aln_mode); rules = 0
+    if mode & ALN_SUBGRAPH:
+        mode &= ~ALN_SUBGRAPH; rules = 3 if mode == 3 else 2
+    p2 = type(prm).from_buffer_copy(prm); p2.aln_mode = mode
+    old_engine = oracle.lib.ongsid_debug_poa_engine(ctypes.c_int32(0))
+    oracle.lib.ongsid_debug_polish_rules(ctypes.c_int32(rules))
+    try:
+        return getattr(oracle, name)(bb, rs, off, p2, **kw)
+    finally:
+        oracle.lib.ongsid_debug_polish_rules(ctypes.c_int32(0))
+        oracle.lib.ongsid_debug_poa_engine(ctypes.c_int32(old_engine))
+
+
+class SubgraphOracle:
+    """the oracle backend as the CLI sees it, with the adapter in front of its polishing calls"""
+    def __init__(self, o): self._o = o
+    def __getattr__(self, k): return getattr(self._o, k)
+    def polish(self, bb, rs, off, prm, **kw): return _oracle_call(self._o, "polish", bb, rs, off, prm, **kw)
+    def polish_trace(self, bb, rs, off, prm, **kw): return _oracle_call(self._o, "polish_trace", bb, rs, off, prm, **kw)
+
+
+def _amplicons(L, nsp, seed, insert=0):
+    """amplicons, and drafts of them (a few substitutions / indels) as backbones; insert > 0: the reads' amplicon carries an insertion of that many bases the draft lacks"""
+    rng = np.random.default_rng(seed)
+    amps = [a.tobytes().decode() for a in synth.make_species(nsp, L, 0.15, seed=seed)]
+    drafts = []
+    for a in amps:
+        d = list(a)
+        for _ in range(max(2, L // 150)):
+            p = int(rng.integers(5, len(d) - 5)); k = int(rng.integers(0, 3))
+            if k == 0: d[p] = "ACGT"[(("ACGT".index(d[p])) + 1) % 4]
+            elif k == 1: del d[p]
+            else: d.insert(p, "ACGT"[int(rng.integers(0, 4))])
+        drafts.append("".join(d))
+    if insert:
+        extra = "".join("ACGT"[x] for x in rng.integers(0, 4, insert))
+        amps = [a[:len(a) // 2] + extra + a[len(a) // 2:] for a in amps]
+    return amps, drafts
+
+
+def _reads(amps, counts, seed, mu=14.0, cut=250):
+    """reads of each amplicon in turn (both strands), about half of them cut by 0 - cut bases at one or both ends: their layers stop inside their windows"""
+    rng = np.random.default_rng(seed)
+    S, Q, off = [], [], [0]
+    for a, n in zip(amps, counts):
+        rd = synth.make_reads([np.frombuffer(a.encode(), dtype=np.uint8)], n, mu=mu, seed=seed, rc_fraction=0.5)
+        seq, qual, o = rd["seq"].numpy(), rd["qual"].numpy(), rd["off"].numpy()
+        for i in range(n):
+            s, q = seq[o[i]:o[i + 1]].tobytes().decode(), qual[o[i]:o[i + 1]].tobytes().decode()
+            if rng.random() < 0.5:
+                h = int(rng.integers(0, cut + 1)) if rng.random() < 0.7 else 0
+                t = int(rng.integers(0, cut + 1)) if rng.random() < 0.7 else 0
+                if len(s) - h - t > 100: s, q = s[h:len(s) - t], q[h:len(q) - t]
+            S.append(s); Q.append(q)
+        off.append(len(S))
+        seed += 1
+    return ReadSet.from_strings(S, Q), off
+
+
+def _check(gpu_api, oracle, bbs, rs, off, prm, fns=("polish", "polish_trace")):
+    bb = ReadSet.from_strings(bbs)
+    out = {}
+    for fn in fns:
+        kw = {"aln": True} if fn == "polish_trace_aln" else {}
+        name = "polish_trace" if fn == "polish_trace_aln" else fn
+        got = getattr(gpu_api, name)(bb, rs, off, prm, **kw)
+        want = _oracle_call(oracle, name, bb, rs, off, prm, **kw)
+        assert len(got) == len(want)
+        for x, (a, b) in enumerate(zip(got, want)):
+            if isinstance(a, np.ndarray) or (isinstance(a, list) and a and isinstance(a[0], np.ndarray)):
+                assert all(np.array_equal(u, v) for u, v in zip(a, b)) if isinstance(a, list) else np.array_equal(a, b), (fn, x)
+            else:
+                assert a == b, (fn, x)
+        out[fn] = got
+    return out
+
+
+def test_subgraph_layers_equal_the_oracle_750(gpu_api, oracle):
+    """two groups in one call - 30 reads (below single_below: one graph per window) and 150 reads (depth-4 tiles) of 750-base amplicons, both strands, half the reads
+    cut at their ends - aln_mode 2: polish, polish_trace and polish_trace_aln equal the oracle; the flag changes the result; without the flag the call is the shipped
+    polisher (oracle rules 0)."""
+    amps, drafts = _amplicons(750, 2, seed=31)
+    rs, off = _reads(amps, [30, 150], seed=40)
+    base = dict(iters=2, k=13, w=20, tile_depth=4, band=0, trim=2, aln_mode=2, stop_when_stable=0, single_below=64)
+    on = _check(gpu_api, oracle, drafts, rs, off, polish_params(**base, subgraph_layers=True), fns=("polish", "polish_trace_aln"))
+    offr = _check(gpu_api, oracle, drafts, rs, off, polish_params(**base), fns=("polish",))
+    assert on["polish"][0] != offr["polish"][0], "the sub-graph rule changed no polished sequence"
+
+
+def test_subgraph_layers_equal_the_oracle_three_windows(gpu_api, oracle):
+    """a 1 525-base amplicon: three windows, the last one with the merged 25-base tail; 120 reads (depth-4 tiles); aln_mode 2 with stop_when_stable, and aln_mode 3
+    (overlap-span clipping) with trim 3"""
+    amps, drafts = _amplicons(1525, 1, seed=52)
+    rs, off = _reads(amps, [120], seed=60)
+    for aln_mode, trim in ((2, 2), (3, 3)):
+        prm = polish_params(iters=2, k=13, w=20, tile_depth=4, band=0, trim=trim, aln_mode=aln_mode, stop_when_stable=1, single_below=64, subgraph_layers=True)
+        _check(gpu_api, oracle, drafts, rs, off, prm, fns=("polish_trace",))
+
+
+def test_subgraph_layers_band_edge_redo(gpu_api, oracle):
+    """the reads carry a 45-base insertion the draft lacks: at band 64 the tracebacks run into the clipped band edge and the tiles are redone at twice the band -
+    HIP == oracle with the rule on, and the library counts redone tiles"""
+    amps, drafts = _amplicons(700, 1, seed=71, insert=45)
+    rs, off = _reads(amps, [90], seed=80, mu=16.0)
+    gpu_api.lib.ngsid_profile_enable(gpu_api.ctx, ctypes.c_int32(1))
+    buf = ctypes.create_string_buffer(1 << 14); gpu_api.lib.ngsid_profile_read(gpu_api.ctx, buf, ctypes.c_uint64(len(buf)))      # reset the counters
+    try:
+        prm = polish_params(iters=1, k=13, w=20, tile_depth=4, band=64, trim=2, aln_mode=2, stop_when_stable=0, single_below=0, subgraph_layers=True)
+        _check(gpu_api, oracle, drafts, rs, off, prm, fns=("polish",))
+        gpu_api.lib.ngsid_profile_read(gpu_api.ctx, buf, ctypes.c_uint64(len(buf)))
+    finally:
+        gpu_api.lib.ngsid_profile_enable(gpu_api.ctx, ctypes.c_int32(0))
+    redo = [int(l.split()[1]) for l in buf.value.decode().splitlines() if l.startswith("poa_band_redo_tiles")]
+    assert redo and redo[0] >= 1, "no tile was redone with a wider band: %s" % buf.value.decode()
+
+
+def test_cli_subgraph_layers_flag(gpu_api, oracle, tmp_path):
+    """--racon_subgraph_layers through the CLI on sample_h1: the HIP library writes the oracle backend's files (logfile.txt aside)"""
+    from ngspeciesid_amd import cli as _cli, fastpath
+    res = {}
+    for name, api in (("hip", gpu_api), ("oracle", SubgraphOracle(oracle))):
+        out = str(tmp_path / ("sub_" + name))
+        args = _cli.build_parser().parse_args(["--ont", "--fastq", os.path.join(GOLD, "sample_h1.fastq"), "--outfolder", out, "--t", "1", "--consensus", "--racon", "--racon_iter", "2", "--racon_subgraph_layers"])
+        args.k, args.w = 13, 20
+        os.makedirs(out, exist_ok=True)
+        fastpath.main(args, api=api)
+        res[name] = {}
+        for root, _, fs in os.walk(out):
+            for f in fs:
+                res[name][os.path.relpath(os.path.join(root, f), out)] = open(os.path.join(root, f), "rb").read()
+    assert sorted(res["hip"]) == sorted(res["oracle"])
+    assert any(k.startswith("consensus_reference_") for k in res["hip"])
+    for k in res["hip"]:
+        if k != "logfile.txt": assert res["hip"][k] == res["oracle"][k], k
