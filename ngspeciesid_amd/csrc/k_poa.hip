@@ -20,12 +20,6 @@
 #include "k_poa.h"
 #include <algorithm>
 
-#ifndef POA_LT
-#define POA_LT 0          // experiment (not kept: slower, register pressure): band starts per anchor from an LDS table instead of three divisions per rank
-#endif
-#ifndef POA_COLD
-#define POA_COLD 1       // round 5: cold fields of the job description read from the kernel-argument segment at their use (poa_tile_body)
-#endif
 #ifndef POA_PHASES
 #define POA_PHASES 0     // round 5: the phase-cycle instrumentation (NGSID_POA_PHASES dev aid) is compiled only into dev builds (-DPOA_PHASES=1, tools/micro/build_variant.sh): its pointer, counters and branches sat in the row paths of the product kernel
 #endif
@@ -594,9 +588,6 @@ __device__ __forceinline__ void poa_row_tail_store(l32 ringrow, LDSP uint8_t* ds
 // All differences between candidates of one cell are the same as in H space, so every maximum and every tie-break is the oracle's.
 // Band columns past the end of the sequence (only when L+1 < BW) see the 0xFF padding and can never beat a real cell.
 #define PBIAS (1 << 28)
-#ifndef POA_SCAN_KEEP
-#define POA_SCAN_KEEP 1
-#endif
 template <int CPL, bool LOCAL>
 __device__ __forceinline__ unsigned poa_row_finish(const int (&X)[CPL], const int (&Dd)[CPL], int floor0, int gp, int (&hout)[CPL])
 {
@@ -605,11 +596,7 @@ __device__ __forceinline__ unsigned poa_row_finish(const int (&X)[CPL], const in
         // the chain iff that value differs from its own candidate, and (local mode) it sits on the floor iff the value equals the floor (the floor grows with the
         // column, so the prefix maximum of the floors is the lane's own).  Same values and directions as the general form below, two instructions less per row.
         const int xf = LOCAL ? max(X[0], floor0) : X[0];
-#if POA_SCAN_KEEP
         const int incl = LOCAL ? wave_incl_max_scan(xf) : wave_incl_max_scan_keep(xf);      // (local mode: xf is a temporary already)
-#else
-        const int incl = wave_incl_max_scan(xf);
-#endif
         int dd = Dd[0];
         if (incl != X[0]) dd = 2;
         if (LOCAL && incl == floor0) dd = 3;
@@ -931,29 +918,6 @@ __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w,
     bestv_out = bestv; bestpk_out = bestpk; nslow_out = nslow;
 }
 
-#ifndef POA_FWD_CALL
-#define POA_FWD_CALL 0      // experiment: the forward pass as a real (non-inlined) function with a register allocation of its own
-#endif
-#if POA_FWD_CALL
-struct FwdOut { int bestv, bestpk, nslow; };
-__device__ __forceinline__ unsigned long long uni64(unsigned long long v) { return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v); }
-template <int CPL, int MODE>
-__device__ __attribute__((noinline)) FwdOut poa_forward_call(unsigned long long gbase, uint32_t s32, uint32_t s64, uint32_t s16, uint32_t s8, uint32_t se16, uint32_t se32, uint32_t sl,
-                                                              unsigned long long hg, unsigned long long dg, unsigned long long dfull, int slen, int V, int nov, int gp, int sm, int sn, int lane)
-{
-    // arguments arrive in VGPRs: make the wave-uniform ones scalar again (once per alignment)
-    GG g; g.base = (uint8_t*)uni64(gbase);
-    g.s32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s32); g.s64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s64); g.s16 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s16); g.s8 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s8);
-    g.se16 = (uint32_t)__builtin_amdgcn_readfirstlane((int)se16); g.se32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)se32); g.sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)sl);
-    LLT<64 * CPL> w; w.sinkbits = nullptr;
-    PSeq S; S.s = nullptr; S.q = nullptr; S.len = __builtin_amdgcn_readfirstlane(slen); S.uw = 0; S.cw = 0; S.mode = MODE; S.a0 = 0; S.a1 = -1;
-    FwdOut o;
-    poa_forward<CPL, MODE>(g, w, (int32_t*)uni64(hg), (uint8_t*)uni64(dg), (uint8_t*)uni64(dfull), S, __builtin_amdgcn_readfirstlane(V), __builtin_amdgcn_readfirstlane(nov),
-                           __builtin_amdgcn_readfirstlane(gp), __builtin_amdgcn_readfirstlane(sm), __builtin_amdgcn_readfirstlane(sn), lane, o.bestv, o.bestpk, o.nslow);
-    return o;
-}
-#endif
-
 // align S to the graph and merge it.  returns 0 = dropped (no valid end cell), 1 = added, 2 = does not fit
 template <int CPL, bool SUB = false>
 __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& w, int32_t* Hg, uint8_t* Dg, uint8_t* Dfull, const PoaJobSet& J, const PSeq& S, TS& st, int lane, int& edge_out)
@@ -984,12 +948,6 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
 #if POA_REPEAT == 1
     for (int rep_ = 0; rep_ < 2; ++rep_) {
 #endif
-    // band start per ANCHOR (anchors are coordinates in the first sequence: 0 .. L0-1): one division per anchor value in a table (the direction block is free
-    // until the forward pass stages its first row) instead of three per rank
-    const bool lt_lds = POA_LT && (unsigned)st.L0 * 2u <= (unsigned)(TBR * BW);
-    const l16 lt = POA_LDS(l16, LLT<BW>::DIRBLK);
-    if (lt_lds) { for (int a = lane; a < st.L0; a += 64) lt[a] = (uint16_t)band_lo(a, bm, BW); lds_sync(); }
-    auto BL = [&](int anchor) __attribute__((always_inline)) -> int { return lt_lds ? (int)lt[anchor] : band_lo(anchor, bm, BW); };
     for (int rb = 0; rb < V; rb += 128) {
         uint32_t ppv[2], arv[2]; int cmv[2], ofv[2], frv[2], lp0[2], lp1[2], smv[2];
 #pragma unroll
@@ -1000,12 +958,12 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
         for (int u = 0; u < 2; ++u) {
             const int r = rb + u * 64 + lane; const bool ok = r < V;          // (no divergent exits: the run lengths below are a wave ballot)
             const int p0 = ppv[u] & 0xffff, p1 = ppv[u] >> 16;
-            const int l0 = BL((int)(arv[u] & 0xffff)); int fl = 0, d0 = 0, d1 = 0, dl0 = 0, dl1 = 0;
+            const int l0 = band_lo((int)(arv[u] & 0xffff), bm, BW); int fl = 0, d0 = 0, d1 = 0, dl0 = 0, dl1 = 0;
             if (ok) {
                 if (p0 == NONE16) fl |= 1;
                 else {
-                    d0 = r - p0; dl0 = l0 - BL(lp0[u]);
-                    if (p1 != NONE16) { d1 = r - p1; dl1 = l0 - BL(lp1[u]); if (cmv[u] & 0x80) fl |= 2; }
+                    d0 = r - p0; dl0 = l0 - band_lo(lp0[u], bm, BW);
+                    if (p1 != NONE16) { d1 = r - p1; dl1 = l0 - band_lo(lp1[u], bm, BW); if (cmv[u] & 0x80) fl |= 2; }
                     if (d0 > 255 || d1 > 255 || dl0 < 0 || dl0 > 255 || dl1 < 0 || dl1 > 255) { fl |= 2; d0 = d1 = dl0 = dl1 = 0; }
                 }
                 if (!ofv[u]) fl |= 4;
@@ -1064,17 +1022,9 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
 #if POA_REPEAT == 2
     for (int rep_ = 0; rep_ < 2; ++rep_)
 #endif
-#if POA_FWD_CALL
-    { FwdOut fo;
-      if (local) fo = poa_forward_call<CPL, NGSID_POA_LOCAL>((unsigned long long)g.base, g.s32, g.s64, g.s16, g.s8, g.se16, g.se32, g.sl, (unsigned long long)Hg, (unsigned long long)Dg, (unsigned long long)Dfull, L, V, st.nov, gp, J.m, J.n, lane);
-      else if (mode == NGSID_POA_SEMI) fo = poa_forward_call<CPL, NGSID_POA_SEMI>((unsigned long long)g.base, g.s32, g.s64, g.s16, g.s8, g.se16, g.se32, g.sl, (unsigned long long)Hg, (unsigned long long)Dg, (unsigned long long)Dfull, L, V, st.nov, gp, J.m, J.n, lane);
-      else fo = poa_forward_call<CPL, NGSID_POA_GLOBAL>((unsigned long long)g.base, g.s32, g.s64, g.s16, g.s8, g.se16, g.se32, g.sl, (unsigned long long)Hg, (unsigned long long)Dg, (unsigned long long)Dfull, L, V, st.nov, gp, J.m, J.n, lane);
-      bestv = fo.bestv; bestpk = fo.bestpk; nslow = fo.nslow; }
-#else
     if (local) poa_forward<CPL, NGSID_POA_LOCAL, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
     else if (mode == NGSID_POA_SEMI) poa_forward<CPL, NGSID_POA_SEMI, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);
     else poa_forward<CPL, NGSID_POA_GLOBAL, SUB>(g, w, Hg, Dg, Dfull, S, V, st.nov, gp, J.m, J.n, lane, bestv, bestpk, nslow);      // (POA_MODE_SUBGRAPH: global on the sub-graph)
-#endif
     if (POA_PHC(J) && lane == 0) { atomicAdd(&PHS(J)[5], (unsigned long long)V); atomicAdd(&PHS(J)[6], (unsigned long long)nslow); }
     mem_sync();                                       // direction rows must have landed before the traceback pulls them back
     PH(J, 1, tph);
@@ -1416,7 +1366,7 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
 }
 
 // LDS bytes of one tile (must match the carve in k_poa_tile)
-size_t poa_lds_bytes(int Vc, int Ec, int Lm, int BW)
+static size_t poa_lds_bytes(int Vc, int Ec, int Lm, int BW)
 {
     (void)Ec;
     const size_t aln = (size_t)HR * (BW + RPADL + RPADR) * 4 + (size_t)TBR * BW + (size_t)TBR * 8 + poa_al16((size_t)Lm + BW + 32);
@@ -1449,16 +1399,12 @@ __device__ __forceinline__ void poa_tile_body(const PoaJobSet& J, uint8_t* gscra
     uint8_t* Dg = J.dirglob + (size_t)blockIdx.x * Vc * BW * 3 / 2;      // packed direction blocks (4 bits per cell) ...
     uint8_t* Dfull = Dg + (size_t)Vc * BW / 2;                            // ... and the byte rows of the ranks with more than two in-edges (sparse)
 
-#if POA_COLD
     // Round 5: the fields of the job description that only the per-tile set-up and the emission read (15 pointers: sequence / tile lists, output arrays, flags) are
     // read from the kernel-argument segment WHERE they are used, through a pointer the compiler cannot see through - kept in SGPRs across the alignment phases they
     // were part of the 172 spilled SGPRs of the 64-column instance (v_writelane / v_readlane pairs = VALU instructions in the row paths).  J is the first kernel argument.
     const PoaJobSet* Jc_ = (const PoaJobSet*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(Jc_));
     const PoaJobSet& JC = *Jc_;
-#else
-    const PoaJobSet& JC = J;
-#endif
     const uint32_t nrun_ = JC.nrun_dev ? (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_nontemporal_load(JC.nrun_dev)) : JC.nrun;      // (written by an earlier kernel of the stream)
     for (;;) {
         // persistent workgroups pull tiles from a queue (tiles differ a lot in cost: depth, graph growth, splits)
@@ -1526,72 +1472,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_poa_tile4_sub(PoaJobSet J, uint8_t* gscratch, size_t gbytes, uint32_t* __restrict__ work_ctr) { poa_tile_body<4, true>(J, gscratch, gbytes, work_ctr); }
 
 // ------------------------------------------------------------------------------------------------ host side
-// one launch of the instance for the band width (sub: the sub-graph instance)
-static int32_t poa_launch_tile(ngsid_ctx* ctx, const PoaJobSet& J, int BW, bool sub, uint32_t nwg, size_t lds, size_t gbytes, uint32_t* work_ctr)
+int32_t poa_check_limits(ngsid_ctx* ctx, const PoaPlan& P, int m, int g)
 {
-    typedef void (*TileFn)(PoaJobSet, uint8_t*, size_t, uint32_t*);
-    const TileFn fn = BW == 64 ? (sub ? k_poa_tile1_sub : k_poa_tile1) : BW == 128 ? (sub ? k_poa_tile2_sub : k_poa_tile2) : (sub ? k_poa_tile4_sub : k_poa_tile4);
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr);
-    HIPCHK(ctx, hipGetLastError());
+#define POA_LIMIT(code, ...) do { if (ctx) snprintf(ctx->err, sizeof(ctx->err), __VA_ARGS__); return (code); } while (0)
+    if (g >= 0) POA_LIMIT(NGSID_ERR_ARG, "POA gap score must be negative");
+    if ((long long)m * P.Lmax >= 65536 || m < 0) POA_LIMIT(NGSID_ERR_TOO_LONG, "POA local score range exceeds 16 bits (match %d x length %d)", m, P.Lmax);
+    if (P.Vcap > 0xFFF0 || P.Ecap > 0xFFF0) POA_LIMIT(NGSID_ERR_TOO_LONG, "POA graph capacity exceeds 16-bit indices (sequence too long for the tile engine)");
+    for (int BW = P.band0; BW <= 256; BW *= 2) {
+        const size_t lds = poa_lds_bytes(P.Vcap, P.Ecap, P.Lmax, BW);
+        if (lds > 160 * 1024) POA_LIMIT(NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);
+    }
+#undef POA_LIMIT
     return NGSID_OK;
 }
-int32_t poa_run_jobs(ngsid_ctx* ctx, PoaJobSet J, int band, bool sub)
+// resident workgroups per CU of the instance for band width BW: what its LDS and its register budget allow, at most ngsid_ctx_option "poa_tiles_per_cu"
+static int poa_per_cu(ngsid_ctx* ctx, const PoaPlan& P, int BW)
 {
-    if (J.njobs == 0) return NGSID_OK;
-    if (!J.job_list) J.nrun = J.njobs;
-    if (J.nrun == 0) return NGSID_OK;
-    const int BW = band <= 64 ? 64 : (band <= 128 ? 128 : 256);
-    if (J.g >= 0) NGSID_FAIL(ctx, NGSID_ERR_ARG, "POA gap score must be negative");
-    if ((long long)J.m * J.Lmax >= 65536 || J.m < 0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA local score range exceeds 16 bits (match %d x length %d)", J.m, J.Lmax);
-    if (J.Vcap > 0xFFF0 || J.Ecap > 0xFFF0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA graph capacity exceeds 16-bit indices (sequence too long for the tile engine)");
-    const size_t lds = poa_lds_bytes(J.Vcap, J.Ecap, J.Lmax, BW);
-    if (lds > 160 * 1024) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);
-    const int wave_cap = BW == 64 ? 4 * POA_W1 : 16;                                  // waves per CU the register budget of the instance allows
-    int per_cu = std::max<int>(1, std::min<int>(wave_cap, (int)((160 * 1024) / lds)));
-    if (ngsid_opt(ctx, "poa_tiles_per_cu", 0) > 0) per_cu = std::max(1, std::min(per_cu, (int)ngsid_opt(ctx, "poa_tiles_per_cu", 0)));
-    uint32_t nwg = (uint32_t)std::min<uint64_t>(J.nrun, (uint64_t)ctx->n_cu * per_cu);
-    const size_t cells = (size_t)J.Vcap * BW;
-    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax, sub);
-    if (ctx->poa_h.n < nwg * cells) HIPCHK(ctx, ctx->poa_h.alloc(nwg * cells));
-    if (ctx->poa_d.n < nwg * cells * 3 / 2) HIPCHK(ctx, ctx->poa_d.alloc(nwg * cells * 3 / 2));
-    if (ctx->poa_g.n < nwg * gbytes) HIPCHK(ctx, ctx->poa_g.alloc(nwg * gbytes));
-    J.Hglob = ctx->poa_h.p; J.dirglob = ctx->poa_d.p; J.covglob = nullptr; J.stat_rows = ctx->prof ? ctx->stat.p : nullptr;
-    if (ctx->poa_ctr.n < 1) HIPCHK(ctx, ctx->poa_ctr.alloc(16));
-    HIPCHK(ctx, hipMemsetAsync(ctx->poa_ctr.p, 0, sizeof(uint32_t), ctx->stream));
-    ProfScope ps_(ctx, sub ? "k_poa_tile_sub" : "k_poa_tile");
-    return poa_launch_tile(ctx, J, BW, sub, nwg, lds, gbytes, ctx->poa_ctr.p);
-}
-
-// ---- device-driven hierarchy (poa_host.hip): one scratch allocation for the main band and the two wider redo instances, launches without host work
-static int poa_per_cu(ngsid_ctx* ctx, int Vc, int Ec, int Lm, int BW)
-{
-    const size_t lds = poa_lds_bytes(Vc, Ec, Lm, BW);
+    const size_t lds = poa_lds_bytes(P.Vcap, P.Ecap, P.Lmax, BW);
     const int wave_cap = BW == 64 ? 4 * POA_W1 : 16;
     int per_cu = std::max<int>(1, std::min<int>(wave_cap, (int)((160 * 1024) / lds)));
     if (ngsid_opt(ctx, "poa_tiles_per_cu", 0) > 0) per_cu = std::max(1, std::min(per_cu, (int)ngsid_opt(ctx, "poa_tiles_per_cu", 0)));
     return per_cu;
 }
-int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs)
+int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs, int m, int g)
 {
-    const int B0 = P.band0 <= 64 ? 64 : (P.band0 <= 128 ? 128 : 256);
-    P.band0 = B0;
-    if (P.Vcap > 0xFFF0 || P.Ecap > 0xFFF0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA graph capacity exceeds 16-bit indices (sequence too long for the tile engine)");
+    { const int32_t rc = poa_check_limits(ctx, P, m, g); if (rc) return rc; }
     const size_t gbytes = poa_graph_bytes(P.Vcap, P.Ecap, P.Lmax, P.sub);
     // resident workgroups per CU; halved when the scratch does not fit (several contexts sharing one GPU, very long reads): the persistent
     // workgroups pull tiles from a queue, so fewer of them only lowers the parallelism
     for (int shrink = 1;; shrink *= 2) {
         size_t need_h = 0, need_d = 0, need_g = 0;
-        for (int BW = B0; BW <= 256; BW *= 2) {
-            const size_t lds = poa_lds_bytes(P.Vcap, P.Ecap, P.Lmax, BW);
-            if (lds > 160 * 1024) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);
+        for (int BW = P.band0; BW <= 256; BW *= 2) {
             uint32_t nwg;
-            if (BW == B0) { nwg = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(max_jobs, 1u), std::max<uint64_t>(1, (uint64_t)ctx->n_cu * poa_per_cu(ctx, P.Vcap, P.Ecap, P.Lmax, BW) / shrink)); P.nwg_main = nwg; }
-            else { nwg = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(max_jobs, 1u), std::max<uint64_t>(1, (uint64_t)ctx->n_cu * std::min(2, poa_per_cu(ctx, P.Vcap, P.Ecap, P.Lmax, BW)) / shrink)); P.nwg_redo = nwg; }       // redone tiles are rare: a small grid keeps the scratch small
+            if (BW == P.band0) { nwg = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(max_jobs, 1u), std::max<uint64_t>(1, (uint64_t)ctx->n_cu * poa_per_cu(ctx, P, BW) / shrink)); P.nwg_main = nwg; }
+            else { nwg = (uint32_t)std::min<uint64_t>(std::max<uint32_t>(max_jobs, 1u), std::max<uint64_t>(1, (uint64_t)ctx->n_cu * std::min(2, poa_per_cu(ctx, P, BW)) / shrink)); P.nwg_redo = nwg; }       // redone tiles are rare: a small grid keeps the scratch small
             const size_t cells = (size_t)P.Vcap * BW;
             need_h = std::max(need_h, nwg * cells); need_d = std::max(need_d, nwg * cells * 3 / 2); need_g = std::max(need_g, nwg * gbytes);
         }
-        if (B0 == 256) P.nwg_redo = 0;
+        if (P.band0 == 256) P.nwg_redo = 0;
         hipError_t e = hipSuccess;
         if (ctx->poa_h.n < need_h) e = ctx->poa_h.alloc(need_h);
         if (e == hipSuccess && ctx->poa_d.n < need_d) e = ctx->poa_d.alloc(need_d);
@@ -1605,14 +1523,16 @@ int32_t poa_prepare(ngsid_ctx* ctx, PoaPlan& P, uint32_t max_jobs)
 int32_t poa_launch(ngsid_ctx* ctx, const PoaPlan& P, PoaJobSet J, int BW, bool redo, uint32_t* work_ctr, bool sub)
 {
     if (sub && !P.sub) NGSID_FAIL(ctx, NGSID_ERR_ARG, "internal: sub-graph POA launch on a plan without its scratch");
-    if (J.g >= 0) NGSID_FAIL(ctx, NGSID_ERR_ARG, "POA gap score must be negative");
-    if ((long long)J.m * J.Lmax >= 65536 || J.m < 0) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA local score range exceeds 16 bits (match %d x length %d)", J.m, J.Lmax);
-    const size_t lds = poa_lds_bytes(J.Vcap, J.Ecap, J.Lmax, BW);
-    if (lds > 160 * 1024) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);      // (the caller checks all three instances before it starts)
     const uint32_t nwg = redo ? P.nwg_redo : P.nwg_main;
     if (nwg == 0) return NGSID_OK;
-    const size_t gbytes = poa_graph_bytes(J.Vcap, J.Ecap, J.Lmax, P.sub);      // (the stride the scratch was allocated with)
+    const size_t lds = poa_lds_bytes(P.Vcap, P.Ecap, P.Lmax, BW);
+    const size_t gbytes = poa_graph_bytes(P.Vcap, P.Ecap, P.Lmax, P.sub);      // (the stride the scratch was allocated with)
     J.Hglob = ctx->poa_h.p; J.dirglob = ctx->poa_d.p; J.covglob = nullptr; J.stat_rows = ctx->prof ? ctx->stat.p : nullptr;
     ProfScope ps_(ctx, sub ? (redo ? "k_poa_tile_sub_redo" : "k_poa_tile_sub") : (redo ? "k_poa_tile_redo" : "k_poa_tile"));
-    return poa_launch_tile(ctx, J, BW, sub, nwg, lds, gbytes, work_ctr);
+    typedef void (*TileFn)(PoaJobSet, uint8_t*, size_t, uint32_t*);
+    const TileFn fn = BW == 64 ? (sub ? k_poa_tile1_sub : k_poa_tile1) : BW == 128 ? (sub ? k_poa_tile2_sub : k_poa_tile2) : (sub ? k_poa_tile4_sub : k_poa_tile4);
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(fn, dim3(nwg), dim3(64), lds, ctx->stream, J, ctx->poa_g.p, gbytes, work_ctr);
+    HIPCHK(ctx, hipGetLastError());
+    return NGSID_OK;
 }

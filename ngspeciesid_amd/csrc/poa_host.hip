@@ -11,7 +11,6 @@
 #include <memory>
 
 namespace {
-#define HT_INIT
 
 struct Unit {                       // one consensus problem: a cluster (spoa stage) or a backbone window (polish)
     std::vector<uint32_t> seqs;     // indices into the CURRENT level's PSeq array, in order
@@ -21,9 +20,21 @@ struct Unit {                       // one consensus problem: a cluster (spoa st
     std::string result; std::vector<uint32_t> cov; bool has_result = false;
 };
 
-struct Level {                      // device buffers of one hierarchy level (kept alive while the next level reads them)
-    DevBuf<PSeq> seqs; DevBuf<uint8_t> out; DevBuf<int32_t> out_len; DevBuf<uint64_t> out_cw; DevBuf<uint32_t> out_n, out_cov;
-};
+// weight of every base of a sequence that stands for w reads (capped like the tile consensuses of the upper levels)
+__host__ __device__ inline int32_t poa_base_weight(uint64_t w) { return w > (1u << 20) ? (1 << 20) : w < 1 ? 1 : (int32_t)w; }
+
+// A tile output as a sequence of the next level (oracle run_hierarchy): cw = the weight of the reads it stands for.  In a window (bb >= 0, wlen = its backbone length)
+// a tile consensus is a layer like the reads it stands for, with span[0..1] = its first and last backbone position: global only if it spans the window with 1 % slack
+// (racon).  wlen is a reference so that the device reads it only for a window.
+__host__ __device__ inline PSeq poa_tile_pseq(const uint8_t* s, uint64_t cw, int32_t len, int mode, int bb, const int32_t& wlen, const int32_t* span)
+{
+    PSeq S; S.s = s; S.q = nullptr; S.len = len; S.uw = poa_base_weight(cw); S.cw = (uint32_t)(cw > 0xffffffffull ? 0xffffffffull : cw); S.mode = mode; S.a0 = 0; S.a1 = -1;
+    if (bb >= 0) {
+        const int offset = (int)(0.01 * (double)wlen), begin = span[0], end = span[1];
+        if (end >= begin) { S.a0 = begin; S.a1 = end; S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : NGSID_POA_SEMI; }
+    }
+    return S;
+}
 
 __global__ void k_make_pseq_reads(const uint8_t* seq, const uint8_t* qual, const uint64_t* off, uint64_t n, int mode, const uint32_t* weight, PSeq* out)
 {
@@ -31,12 +42,80 @@ __global__ void k_make_pseq_reads(const uint8_t* seq, const uint8_t* qual, const
     if (i >= n) return;
     PSeq S; S.s = seq + off[i]; S.q = qual ? qual + off[i] : nullptr; S.len = (int32_t)(off[i + 1] - off[i]); S.uw = 1; S.cw = 1; S.mode = mode; S.a0 = 0; S.a1 = -1;
     if (weight) {        // a sequence that stands for weight[i] reads (ngsid_poa_consensus_weighted): unit weights of that size, like the tile consensuses of the upper levels
-        const uint32_t wv = weight[i]; S.q = nullptr; S.cw = wv; S.uw = (int32_t)(wv > (1u << 20) ? (1u << 20) : (wv < 1u ? 1u : wv));
+        const uint32_t wv = weight[i]; S.q = nullptr; S.cw = wv; S.uw = poa_base_weight(wv);
     }
     out[i] = S;
 }
 
 struct HierParams { int m, n, g, band, node_cap, D, upper_mode; bool want_cov; int trim_tiles; int single_below = 0; bool sub = false; };      // single_below: ngsid_poa_params_t.single_below (units the caller marked with single_maxlen); sub: level 0 may hold POA_MODE_SUBGRAPH layers (the sub-graph tile instances run it)
+
+// Tile lists of a level: the sequences of every unfinished unit in tiles of hp.D (poa_ntiles), unit after unit.  The host arrays are kept across levels and
+// calls (a million entries per level; fresh allocations would page-fault every time).
+struct TileLists {
+    PinVec<uint32_t> job_off, seq_idx, job_unit; PinVec<int32_t> job_bb; PinVec<uint8_t> job_final /* tiles that end their unit (trim 3) */;
+    uint32_t maxD, maxn; int maxbb; bool any_nobb;      // largest tile, largest unit, longest backbone (0 if none), a unit without a backbone
+    uint32_t njobs() const { return (uint32_t)job_unit.size(); }
+};
+// unit_rec != null: per unit its sequence count | first tile | tile count (3 x units.size() entries).  Units without sequences are marked done.
+void build_tiles(TileLists& T, std::vector<Unit>& units, const std::vector<int>& bb_len, int D, uint32_t* unit_rec)
+{
+    T.job_off.assign(1, 0); T.seq_idx.clear(); T.job_unit.clear(); T.job_bb.clear(); T.job_final.clear();
+    T.maxD = 0; T.maxn = 0; T.maxbb = 0; T.any_nobb = false;
+    { size_t tot = 0; for (const Unit& U : units) if (!U.done) tot += U.seqs.size(); T.seq_idx.reserve(tot); }
+    const size_t nu = units.size();
+    for (size_t u = 0; u < nu; ++u) {
+        Unit& U = units[u];
+        const uint32_t ncur = U.done ? 0u : (uint32_t)U.seqs.size(), job0 = T.njobs();
+        if (ncur == 0) U.done = true;
+        else {
+            const uint32_t Dl = D > 0 ? (uint32_t)D : ncur, nt = poa_ntiles(ncur, Dl), base = (uint32_t)T.seq_idx.size();
+            T.seq_idx.insert(T.seq_idx.end(), U.seqs.begin(), U.seqs.end());          // the unit's sequences in one block copy: its tiles are consecutive slices of it
+            for (uint32_t t = 0; t < nt; ++t) {
+                const uint32_t a = t * Dl, b = t + 1 == nt ? ncur : a + Dl;
+                T.job_off.push_back(base + b); T.job_bb.push_back(U.bb); T.job_unit.push_back((uint32_t)u); T.job_final.push_back(nt == 1 ? 1 : 0);
+                T.maxD = std::max(T.maxD, b - a);
+            }
+            if (U.bb >= 0) T.maxbb = std::max(T.maxbb, bb_len[U.bb]); else T.any_nobb = true;
+            T.maxn = std::max(T.maxn, ncur);
+        }
+        if (unit_rec) { unit_rec[u] = ncur; unit_rec[nu + u] = job0; unit_rec[2 * nu + u] = T.njobs() - job0; }
+    }
+}
+// the tile lists to the level buffers B (job_final with trim 3; job_unit for the device-driven levels)
+int32_t upload_tiles(ngsid_ctx* ctx, const TileLists& T, ngsid_ctx::PoaLevelBufs& B, bool final_, bool unit)
+{
+    HIPCHK(ctx, B.job_off.reserve(T.job_off.size())); HIPCHK(ctx, B.seq_idx.reserve(T.seq_idx.size())); HIPCHK(ctx, B.job_bb.reserve(T.job_bb.size()));
+    HIPCHK(ctx, hipMemcpyAsync(B.job_off.p, T.job_off.data(), 4 * T.job_off.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(B.seq_idx.p, T.seq_idx.data(), 4 * T.seq_idx.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(B.job_bb.p, T.job_bb.data(), 4 * T.job_bb.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (final_) { HIPCHK(ctx, B.job_final.reserve(T.job_final.size())); HIPCHK(ctx, hipMemcpyAsync(B.job_final.p, T.job_final.data(), T.job_final.size(), hipMemcpyHostToDevice, ctx->stream)); }
+    if (unit) { HIPCHK(ctx, B.job_unit.reserve(T.job_unit.size())); HIPCHK(ctx, hipMemcpyAsync(B.job_unit.p, T.job_unit.data(), 4 * T.job_unit.size(), hipMemcpyHostToDevice, ctx->stream)); }
+    return NGSID_OK;
+}
+
+// Launch geometry: graph capacity by the oracle rule for the longest first sequence or backbone L0 (at least the longest member Lm + 1, a multiple of 8), Lm rounded up to 16
+PoaPlan poa_plan(const HierParams& hp, int L0, uint32_t Lm, bool sub)
+{
+    long long capV = (long long)L0 * (hp.node_cap > 0 ? hp.node_cap : 28) / 16; capV = std::max<long long>(capV, L0 + 64); capV = std::max<long long>(capV, (long long)Lm + 1);
+    capV = (capV + 7) & ~7ll;
+    PoaPlan P{};
+    P.Vcap = (int)capV; P.Ecap = (int)(3 * capV / 2); P.Lmax = (int)((std::max<uint32_t>(Lm, 1) + 15) & ~15u);
+    P.band0 = hp.band <= 64 ? 64 : (hp.band <= 128 ? 128 : 256); P.sub = sub;
+    return P;
+}
+
+// the job set of a level's tiles in the level buffers ctx->poa_lv[level & 1]; flags: dropped, slot_overflow.  The caller says which tiles a launch runs (nrun, job_list, nrun_dev).
+PoaJobSet level_jobs(ngsid_ctx* ctx, const HierParams& hp, const PoaPlan& P, int level, int slots, const PSeq* seqs, const PSeq* bbs, const uint32_t* seq_idx, uint32_t njobs, uint32_t* flags)
+{
+    const ngsid_ctx::PoaLevelBufs& B = ctx->poa_lv[level & 1];
+    PoaJobSet J{};
+    J.seqs = seqs; J.bbs = bbs; J.seq_idx = seq_idx; J.job_off = B.job_off.p; J.job_bb = B.job_bb.p; J.njobs = njobs;
+    J.m = hp.m; J.n = hp.n; J.g = hp.g; J.Vcap = P.Vcap; J.Ecap = P.Ecap; J.Lmax = P.Lmax; J.D = slots; J.node_cap = hp.node_cap;
+    J.trim_tiles = (hp.trim_tiles & 1) | ((level > 0 && (hp.trim_tiles & 1)) ? 2 : 0); J.job_final = (hp.trim_tiles & 4) ? B.job_final.p : nullptr;
+    J.out = B.out.p; J.out_len = B.out_len.p; J.out_cw = B.out_cw.p; J.out_n = B.out_n.p; J.out_cov = (hp.want_cov || hp.trim_tiles) ? B.out_cov.p : nullptr; J.out_span = B.out_span.p;
+    J.dropped = flags; J.slot_overflow = flags + 1;
+    return J;
+}
 
 // Runs all units to completion.  level0: device PSeq array (nseq0 entries) whose max length is maxlen0;
 // bbs: device backbone PSeqs (may be null), maxbb = longest backbone.
@@ -46,58 +125,39 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
     const PSeq* cur = d_level0; uint32_t cur_maxlen = maxlen0;
     int slots_cap = 0;
     HostTimer ht(ctx->stream, "hierarchy");
+    if (ctx->poa_ctr.n < 1) HIPCHK(ctx, ctx->poa_ctr.alloc(16));
     for (int level = 0;; ++level) {
         // ---- jobs of this level
-        // host lists of a level: kept across levels and calls (a million entries per level; fresh allocations would page-fault every time)
-        static thread_local PinVec<uint32_t> job_off, seq_idx; static thread_local std::vector<uint32_t> job_unit; static thread_local PinVec<int32_t> job_bb;
-        job_off.clear(); job_off.push_back(0); seq_idx.clear(); job_unit.clear(); job_bb.clear();
-        static thread_local PinVec<uint8_t> job_final; job_final.clear();      // trim 3 (hp.trim_tiles & 4): tiles that end their unit
-        { size_t tot = 0; for (const Unit& U : units) if (!U.done) tot += U.seqs.size(); seq_idx.reserve(tot); }
-        uint32_t maxD = 0; int maxL0 = 1; bool any_nobb = false;
-        for (size_t u = 0; u < units.size(); ++u) {
-            Unit& U = units[u]; if (U.done) continue;
-            const uint32_t ncur = (uint32_t)U.seqs.size();
-            if (ncur == 0) { U.done = true; continue; }
-            const uint32_t Dl = hp.D > 0 ? (uint32_t)hp.D : ncur; const uint32_t nt = poa_ntiles(ncur, Dl);
-            for (uint32_t t = 0; t < nt; ++t) {
-                const uint32_t a = t * Dl, b = t + 1 == nt ? ncur : a + Dl;
-                for (uint32_t x = a; x < b; ++x) seq_idx.push_back(U.seqs[x]);
-                job_off.push_back((uint32_t)seq_idx.size()); job_bb.push_back(U.bb); job_unit.push_back((uint32_t)u); job_final.push_back(nt == 1 ? 1 : 0);
-                maxD = std::max(maxD, b - a);
-            }
-            if (U.bb >= 0) maxL0 = std::max(maxL0, bb_len[U.bb]); else any_nobb = true;
-        }
-        const uint32_t njobs = (uint32_t)job_unit.size();
+        static thread_local TileLists T;
+        build_tiles(T, units, bb_len, hp.D, nullptr);
+        const uint32_t njobs = T.njobs(), maxD = T.maxD;
         if (njobs == 0) break;
         if (level == 0) ht.mark("L0 host job lists");
-        if (any_nobb) maxL0 = std::max<int>(maxL0, (int)cur_maxlen);   // without a backbone the first member sets L0 (<= the longest member)
-        // capacity (LDS sizing): the largest per-job capacity the oracle rule can produce
-        long long capV = (long long)maxL0 * (hp.node_cap > 0 ? hp.node_cap : 28) / 16; capV = std::max<long long>(capV, maxL0 + 64); capV = std::max<long long>(capV, (long long)cur_maxlen + 1);
-        capV = (capV + 7) & ~7ll;
-        const int Lmax = (int)((std::max<uint32_t>(cur_maxlen, 1) + 15) & ~15u);
+        // capacity (LDS sizing): the largest per-job capacity the oracle rule can produce; without a backbone the first member sets L0 (<= the longest member)
+        PoaPlan plan = poa_plan(hp, std::max({1, T.maxbb, T.any_nobb ? (int)cur_maxlen : 0}), cur_maxlen, hp.sub && level == 0);
+        { int32_t rc = poa_prepare(ctx, plan, njobs, hp.m, hp.g); if (rc) return rc; }
+        const int capV = plan.Vcap;
         ngsid_ctx::PoaLevelBufs* Lv = &ctx->poa_lv[level & 1];      // level L+1 reads what level L wrote: two alternating, grow-only buffer sets
-        DevBuf<uint32_t>& d_job_off = Lv->job_off; DevBuf<uint32_t>& d_seq_idx = Lv->seq_idx; DevBuf<uint32_t>& d_flags = Lv->flags; DevBuf<int32_t>& d_job_bb = Lv->job_bb;
-        HIPCHK(ctx, d_job_off.reserve(job_off.size())); HIPCHK(ctx, d_seq_idx.reserve(seq_idx.size())); HIPCHK(ctx, d_job_bb.reserve(job_bb.size())); HIPCHK(ctx, d_flags.reserve(4));
-        HIPCHK(ctx, hipMemcpyAsync(d_job_off.p, job_off.data(), 4 * job_off.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_seq_idx.p, seq_idx.data(), 4 * seq_idx.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_job_bb.p, job_bb.data(), 4 * job_bb.size(), hipMemcpyHostToDevice, ctx->stream));
-        if (hp.trim_tiles & 4) { HIPCHK(ctx, Lv->job_final.reserve(job_final.size())); HIPCHK(ctx, hipMemcpyAsync(Lv->job_final.p, job_final.data(), job_final.size(), hipMemcpyHostToDevice, ctx->stream)); }
+        DevBuf<uint32_t>& d_flags = Lv->flags;
+        { int32_t rc = upload_tiles(ctx, T, *Lv, hp.trim_tiles & 4, false); if (rc) return rc; }
+        HIPCHK(ctx, d_flags.reserve(4));
         int slots = slots_cap ? slots_cap : (int)std::min<uint32_t>(maxD, (uint32_t)std::max<long long>(1, ngsid_opt(ctx, "poa_out_slots", 4)));
         static thread_local PinVec<uint32_t> h_out_n; static thread_local PinVec<int32_t> h_out_len, h_out_span; static thread_local PinVec<uint64_t> h_out_cw;
         const bool need_cov = hp.want_cov || hp.trim_tiles;
+        auto launch = [&](const PoaJobSet& J, int bw, bool redo) -> int32_t {
+            HIPCHK(ctx, hipMemsetAsync(ctx->poa_ctr.p, 0, sizeof(uint32_t), ctx->stream));      // the work queue of every launch starts at its first tile
+            return poa_launch(ctx, plan, J, bw, redo, ctx->poa_ctr.p, plan.sub);
+        };
         for (;;) {      // retry with more output slots if a tile had to split more often than `slots`
             HIPCHK(ctx, Lv->out.reserve((size_t)njobs * slots * capV)); HIPCHK(ctx, Lv->out_len.reserve((size_t)njobs * slots)); HIPCHK(ctx, Lv->out_cw.reserve((size_t)njobs * slots)); HIPCHK(ctx, Lv->out_n.reserve(njobs)); HIPCHK(ctx, Lv->out_span.reserve((size_t)njobs * slots * 2));
             if (need_cov) HIPCHK(ctx, Lv->out_cov.reserve((size_t)njobs * slots * capV));
             HIPCHK(ctx, hipMemsetAsync(d_flags.p, 0, 16, ctx->stream));
-            PoaJobSet J{};
-            J.seqs = cur; J.bbs = d_bbs; J.seq_idx = d_seq_idx.p; J.job_off = d_job_off.p; J.job_bb = d_job_bb.p; J.njobs = njobs;
-            J.m = hp.m; J.n = hp.n; J.g = hp.g; J.Vcap = (int)capV; J.Ecap = (int)(3 * capV / 2); J.Lmax = Lmax; J.D = slots; J.node_cap = hp.node_cap; J.trim_tiles = (hp.trim_tiles & 1) | ((level > 0 && (hp.trim_tiles & 1)) ? 2 : 0); J.job_final = (hp.trim_tiles & 4) ? Lv->job_final.p : nullptr;
-            J.out = Lv->out.p; J.out_len = Lv->out_len.p; J.out_cw = Lv->out_cw.p; J.out_n = Lv->out_n.p; J.out_cov = need_cov ? Lv->out_cov.p : nullptr; J.out_span = Lv->out_span.p;
-            J.dropped = d_flags.p; J.slot_overflow = d_flags.p + 1;
+            PoaJobSet J = level_jobs(ctx, hp, plan, level, slots, cur, d_bbs, Lv->seq_idx.p, njobs, d_flags.p);
+            J.nrun = njobs;
             DevBuf<unsigned long long> d_ph; static const bool want_ph = getenv("NGSID_POA_PHASES") != nullptr;
             if (want_ph) { HIPCHK(ctx, d_ph.alloc(24 * 256)); HIPCHK(ctx, hipMemsetAsync(d_ph.p, 0, 192 * 256, ctx->stream)); J.phase_cycles = d_ph.p; J.phase_detail = atoi(getenv("NGSID_POA_PHASES")) >= 2; }
             if (level == 0) ht.mark("L0 alloc + upload");
-            int32_t rc = poa_run_jobs(ctx, J, hp.band, hp.sub && level == 0); if (rc) return rc;
+            int32_t rc = launch(J, plan.band0, false); if (rc) return rc;
             if (level == 0) ht.mark("L0 kernel");
             uint32_t h_flags[4];
             h_out_n.resize(njobs); h_out_len.resize((size_t)njobs * slots); h_out_cw.resize((size_t)njobs * slots); h_out_span.resize((size_t)njobs * slots * 2);
@@ -112,7 +172,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
             };
             rc = download(); if (rc) return rc;
             // band-edge check (oracle run_tile): tiles in which a traceback touched a clipped edge of its band run again, whole, with twice the band
-            for (int bw = hp.band <= 64 ? 64 : (hp.band <= 128 ? 128 : 256); bw < 256 && !h_flags[1] && !h_flags[2];) {
+            for (int bw = plan.band0; bw < 256 && !h_flags[1] && !h_flags[2];) {
                 static thread_local PinVec<uint32_t> redo; redo.clear();
                 for (uint32_t j = 0; j < njobs; ++j) if (h_out_n[j] & 0x80000000u) redo.push_back(j);
                 if (redo.empty()) break;
@@ -120,7 +180,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
                 HIPCHK(ctx, Lv->job_list.reserve(redo.size()));
                 HIPCHK(ctx, hipMemcpyAsync(Lv->job_list.p, redo.data(), 4 * redo.size(), hipMemcpyHostToDevice, ctx->stream));
                 J.job_list = Lv->job_list.p; J.nrun = (uint32_t)redo.size();
-                rc = poa_run_jobs(ctx, J, bw, hp.sub && level == 0); if (rc) return rc;
+                rc = launch(J, bw, true); if (rc) return rc;
                 rc = download(); if (rc) return rc;
                 ctx->poa_redo_tiles += redo.size();
             }
@@ -134,7 +194,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
         if (level == 0) ht.mark("L0 download");
         // ---- distribute outputs to units
         std::vector<std::vector<uint32_t>> outs(units.size());         // flat slot indices (job*slots + s) in job order
-        for (uint32_t j = 0; j < njobs; ++j) for (uint32_t s = 0; s < h_out_n[j]; ++s) outs[job_unit[j]].push_back(j * (uint32_t)slots + s);
+        for (uint32_t j = 0; j < njobs; ++j) for (uint32_t s = 0; s < h_out_n[j]; ++s) outs[T.job_unit[j]].push_back(j * (uint32_t)slots + s);
         static thread_local PinVec<PSeq> next; uint32_t next_maxlen = 0;
         { size_t tot = 0; for (uint32_t j = 0; j < njobs; ++j) tot += h_out_n[j]; next.clear(); next.reserve(tot); }
         for (size_t u = 0; u < units.size(); ++u) {
@@ -154,14 +214,7 @@ int32_t run_hierarchy_host(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen
             }
             U.seqs.clear();
             for (uint32_t sl : O) {
-                const uint64_t cw = h_out_cw[sl];
-                PSeq S; S.s = Lv->out.p + (size_t)sl * capV; S.q = nullptr; S.len = h_out_len[sl];
-                S.uw = cw > (1u << 20) ? (1 << 20) : (int)cw; if (S.uw < 1) S.uw = 1;
-                S.cw = (uint32_t)(cw > 0xffffffffull ? 0xffffffffull : cw); S.mode = hp.upper_mode; S.a0 = 0; S.a1 = -1;
-                if (U.bb >= 0) {     // a tile consensus is a layer of the window like the reads it stands for (oracle run_hierarchy): global only if it spans the window
-                    const int wlen = bb_len[U.bb], offset = (int)(0.01 * (double)wlen), begin = h_out_span[2 * (size_t)sl], end = h_out_span[2 * (size_t)sl + 1];
-                    if (end >= begin) { S.a0 = begin; S.a1 = end; S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : NGSID_POA_SEMI; }
-                }
+                const PSeq S = poa_tile_pseq(Lv->out.p + (size_t)sl * capV, h_out_cw[sl], h_out_len[sl], hp.upper_mode, U.bb, U.bb >= 0 ? bb_len[U.bb] : 0, &h_out_span[2 * (size_t)sl]);
                 U.seqs.push_back((uint32_t)next.size()); next.push_back(S); next_maxlen = std::max<uint32_t>(next_maxlen, (uint32_t)S.len);
             }
         }
@@ -330,14 +383,8 @@ __global__ __launch_bounds__(256) void k_poa_fill_next(HierDev H, LevelDev Lv, i
     const uint32_t n = Lv.out_n[j] & 0x7fffffffu;
     if (pick == -2) {
         if ((uint32_t)lane < n) {
-            const size_t sl = (size_t)j * H.slots + lane; const uint64_t cw = Lv.out_cw[sl];
-            PSeq S; S.s = Lv.out + sl * (size_t)H.capV; S.q = nullptr; S.len = Lv.out_len[sl];
-            S.uw = cw > (1u << 20) ? (1 << 20) : (int)cw; if (S.uw < 1) S.uw = 1;
-            S.cw = (uint32_t)(cw > 0xffffffffull ? 0xffffffffull : cw); S.mode = H.upper_mode; S.a0 = 0; S.a1 = -1;
-            if (H.unit_bb[u] >= 0) {     // a tile consensus is a layer of the window like the reads it stands for: global only if it spans the window (oracle run_hierarchy)
-                const int wlen = H.unit_wlen[u], offset = (int)(0.01 * (double)wlen), begin = Lv.out_span[2 * sl], end = Lv.out_span[2 * sl + 1];
-                if (end >= begin) { S.a0 = begin; S.a1 = end; S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : NGSID_POA_SEMI; }
-            }
+            const size_t sl = (size_t)j * H.slots + lane;
+            const PSeq S = poa_tile_pseq(Lv.out + sl * (size_t)H.capV, Lv.out_cw[sl], Lv.out_len[sl], H.upper_mode, H.unit_bb[u], H.unit_wlen[u], Lv.out_span + 2 * sl);
             if (S.len > H.Lmax) atomicExch(&H.ctrl[C_OVERFLOW], 1u);       // longer than the launch geometry was planned for: the host-driven loop takes over
             Lv.seqs[H.unit_seq0[u] + Lv.job_pos[j] + (uint32_t)lane] = S;
         }
@@ -378,41 +425,17 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
     const uint32_t U = (uint32_t)units.size();
     HostTimer ht(ctx->stream, "hierarchy (device levels)");
     // ---- level-0 tile lists (as in the host-driven loop) + per-unit records
-    static thread_local PinVec<uint32_t> job_off, seq_idx, job_unit, u_u32; static thread_local PinVec<int32_t> job_bb, u_i32; static thread_local PinVec<uint8_t> job_final;
-    job_off.clear(); job_off.push_back(0); seq_idx.clear(); job_unit.clear(); job_bb.clear(); job_final.clear();
-    { size_t tot = 0; for (const Unit& Un : units) if (!Un.done) tot += Un.seqs.size(); seq_idx.reserve(tot); }
+    static thread_local TileLists T; static thread_local PinVec<uint32_t> u_u32; static thread_local PinVec<int32_t> u_i32;
     u_u32.assign(3ull * U, 0); u_i32.assign(3ull * U, 0);        // ncur | job0 | njobs   and   bb | wlen | pick
-    uint32_t maxD = 0; int maxbb = 0; bool any_nobb = false; uint64_t maxn = 0;
-    for (uint32_t u = 0; u < U; ++u) {
-        const Unit& Un = units[u];
-        const uint32_t ncur = Un.done ? 0u : (uint32_t)Un.seqs.size();
-        u_u32[u] = ncur; u_u32[U + u] = (uint32_t)job_unit.size(); u_i32[u] = Un.bb; u_i32[U + u] = Un.bb >= 0 ? bb_len[Un.bb] : 0; u_i32[2ull * U + u] = -2;
-        if (ncur) {
-            const uint32_t Dl = hp.D > 0 ? (uint32_t)hp.D : ncur;
-            const uint32_t base = (uint32_t)seq_idx.size();
-            seq_idx.insert(seq_idx.end(), Un.seqs.begin(), Un.seqs.end());          // the unit's sequences in one block copy: its tiles are consecutive slices of it
-            const uint32_t nt = poa_ntiles(ncur, Dl);
-            for (uint32_t t = 0; t < nt; ++t) {
-                const uint32_t a = t * Dl, b = t + 1 == nt ? ncur : a + Dl;
-                job_off.push_back(base + b); job_bb.push_back(Un.bb); job_unit.push_back(u); job_final.push_back(nt == 1 ? 1 : 0);
-                maxD = std::max(maxD, b - a);
-            }
-            if (Un.bb >= 0) maxbb = std::max(maxbb, bb_len[Un.bb]); else any_nobb = true;
-            maxn = std::max<uint64_t>(maxn, ncur);
-        }
-        u_u32[2ull * U + u] = (uint32_t)job_unit.size() - u_u32[U + u];
-    }
-    const uint32_t njobs0 = (uint32_t)job_unit.size();
-    if (njobs0 == 0) return NGSID_OK;                       // (the host loop marks the empty units)
+    build_tiles(T, units, bb_len, hp.D, u_u32.data());
+    for (uint32_t u = 0; u < U; ++u) { const int bb = units[u].bb; u_i32[u] = bb; u_i32[U + u] = bb >= 0 ? bb_len[bb] : 0; u_i32[2ull * U + u] = -2; }
+    const uint32_t njobs0 = T.njobs(), maxD = T.maxD; const uint64_t maxn = T.maxn;
+    if (njobs0 == 0) return NGSID_OK;
     // ---- one launch geometry for all levels: members of the upper levels are tile consensus sequences, planned for up to 5/4 of the longest input
-    const int Lb = std::max<int>((int)maxlen0, maxbb), Lb2 = Lb + Lb / 4 + 16;
-    const int maxL0 = std::max(maxbb, any_nobb ? Lb2 : 1);
-    long long capV = (long long)maxL0 * (hp.node_cap > 0 ? hp.node_cap : 28) / 16; capV = std::max<long long>(capV, maxL0 + 64); capV = std::max<long long>(capV, (long long)Lb2 + 1);
-    capV = (capV + 7) & ~7ll;
-    const int Lmax = (int)(((uint32_t)std::max(Lb2, 1) + 15) & ~15u);
-    const int band0 = hp.band <= 64 ? 64 : (hp.band <= 128 ? 128 : 256);
-    if (capV > 0xFFF0 || 3 * capV / 2 > 0xFFF0 || (long long)hp.m * Lmax >= 65536 || hp.m < 0 || hp.g >= 0) return NGSID_OK;      // the host loop reports what is wrong (or fits where this margin does not)
-    for (int bw = band0; bw <= 256; bw *= 2) if (poa_lds_bytes((int)capV, (int)(3 * capV / 2), Lmax, bw) > 160 * 1024) return NGSID_OK;
+    const int Lb = std::max<int>((int)maxlen0, T.maxbb), Lb2 = Lb + Lb / 4 + 16;
+    PoaPlan plan = poa_plan(hp, std::max(T.maxbb, T.any_nobb ? Lb2 : 1), (uint32_t)Lb2, hp.sub);
+    if (poa_check_limits(nullptr, plan, hp.m, hp.g)) return NGSID_OK;      // the host loop reports what is wrong (or fits where this margin does not)
+    const int band0 = plan.band0; const long long capV = plan.Vcap;
     const int slots = (int)std::min<uint32_t>(maxD, (uint32_t)std::max<long long>(1, ngsid_opt(ctx, "poa_out_slots", 4)));      // output slots per tile of the first attempt (a tile that closes its graph more often falls back to the host-driven loop, which retries with more)
     // levels the LARGEST unit needs when every tile returns one consensus (the tile counts of poa_ntiles, level by level).  Round 6: exactly that many are enqueued before the first
     // synchronisation (it used to be two more - an off-by-one and a spare - i.e. 2 x 9 empty dispatches per hierarchy); a tile that closes its graph early and returns two
@@ -421,8 +444,7 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
     levels_est = std::min(std::max(levels_est, 1), C_MAXLV - 2);
     uint32_t cap[2]; cap[0] = njobs0;
     { const uint64_t e1 = hp.D > 0 ? (njobs0 + (uint64_t)hp.D - 1) / (uint64_t)hp.D * (uint64_t)slots + U : U; cap[1] = (uint32_t)std::min<uint64_t>(njobs0, e1 + e1 / 4 + 1024); }
-    PoaPlan plan{(int)capV, (int)(3 * capV / 2), Lmax, 0, 0, band0, hp.sub};
-    { int32_t rc = poa_prepare(ctx, plan, njobs0); if (rc) return rc; }
+    { int32_t rc = poa_prepare(ctx, plan, njobs0, hp.m, hp.g); if (rc) return rc; }
     // ---- buffers
     const bool need_cov = hp.want_cov || hp.trim_tiles;
     LevelDev L[2];
@@ -434,12 +456,11 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
         HIPCHK(ctx, B->job_unit.reserve(cap[q])); HIPCHK(ctx, B->job_pos.reserve(cap[q])); HIPCHK(ctx, B->job_final.reserve(cap[q]));
         L[q] = LevelDev{(PSeq*)B->seqs.p, B->out.p, B->out_len.p, B->out_span.p, B->out_cw.p, B->out_n.p, need_cov ? B->out_cov.p : nullptr, B->job_off.p, B->job_bb.p, B->job_unit.p, B->job_pos.p, B->job_list.p, B->job_final.p};
     }
-    HIPCHK(ctx, ctx->poa_lv[0].seq_idx.reserve(seq_idx.size()));
     DevBuf<uint32_t> d_u32, d_ctrl, d_res_off, d_res_cov; DevBuf<int32_t> d_i32, d_res_len; DevBuf<uint8_t> d_res;
     HIPCHK(ctx, d_u32.alloc(9ull * U + 4)); HIPCHK(ctx, d_i32.alloc(3ull * U)); HIPCHK(ctx, d_ctrl.alloc(C_WORDS)); HIPCHK(ctx, d_res_off.alloc(U)); HIPCHK(ctx, d_res_len.alloc(U));
     HIPCHK(ctx, d_res.alloc((size_t)U * capV)); if (hp.want_cov) HIPCHK(ctx, d_res_cov.alloc((size_t)U * capV));
     HierDev H{};
-    H.U = U; H.D = hp.D; H.slots = slots; H.capV = (int)capV; H.upper_mode = hp.upper_mode; H.want_cov = hp.want_cov ? 1 : 0; H.Lmax = Lmax; H.keep_final = (hp.trim_tiles & 4) ? 1 : 0; H.cap_jobs[0] = cap[0]; H.cap_jobs[1] = cap[1];
+    H.U = U; H.D = hp.D; H.slots = slots; H.capV = (int)capV; H.upper_mode = hp.upper_mode; H.want_cov = hp.want_cov ? 1 : 0; H.Lmax = plan.Lmax; H.keep_final = (hp.trim_tiles & 4) ? 1 : 0; H.cap_jobs[0] = cap[0]; H.cap_jobs[1] = cap[1];
     H.unit_bb = d_i32.p; H.unit_wlen = d_i32.p + U; H.unit_pick = d_i32.p + 2ull * U;
     H.unit_ncur = d_u32.p; H.unit_job0[0] = d_u32.p + U; H.unit_njobs[0] = d_u32.p + 2ull * U + 1; H.unit_job0[1] = d_u32.p + 3ull * U + 1; H.unit_njobs[1] = d_u32.p + 4ull * U + 2; H.unit_seq0 = d_u32.p + 5ull * U + 2; H.unit_tmp = d_u32.p + 6ull * U + 2;
     H.res_off = d_res_off.p; H.res_len = d_res_len.p; H.res = d_res.p; H.res_cov = hp.want_cov ? d_res_cov.p : nullptr; H.ctrl = d_ctrl.p;
@@ -449,11 +470,7 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
     HIPCHK(ctx, hipMemcpyAsync(H.unit_job0[0], u_u32.data() + U, 4ull * U, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(H.unit_njobs[0], u_u32.data() + 2ull * U, 4ull * U, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_i32.p, u_i32.data(), 12ull * U, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(L[0].job_off, job_off.data(), 4 * job_off.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->poa_lv[0].seq_idx.p, seq_idx.data(), 4 * seq_idx.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(L[0].job_bb, job_bb.data(), 4 * job_bb.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(L[0].job_unit, job_unit.data(), 4 * job_unit.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (hp.trim_tiles & 4) HIPCHK(ctx, hipMemcpyAsync(L[0].job_final, job_final.data(), job_final.size(), hipMemcpyHostToDevice, ctx->stream));
+    { int32_t rc = upload_tiles(ctx, T, ctx->poa_lv[0], hp.trim_tiles & 4, true); if (rc) return rc; }       // (within the sizes reserved above: the pointers in L stay valid)
     static thread_local PinVec<uint32_t> h_nj; h_nj.assign(1, njobs0);
     HIPCHK(ctx, hipMemcpyAsync(d_ctrl.p + C_NJOBS, h_nj.data(), 4, hipMemcpyHostToDevice, ctx->stream));
     ht.mark("L0 lists + upload");
@@ -463,12 +480,8 @@ int32_t run_hierarchy_dev(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0
         const int batch_end = std::min(C_MAXLV - 1, level + (level == 0 ? levels_est : 3));
         for (; level < batch_end; ++level) {
             const int par = level & 1; LevelDev& Lv = L[par]; LevelDev& Nx = L[par ^ 1];
-            PoaJobSet J{};
-            J.seqs = level == 0 ? d_level0 : (const PSeq*)Nx.seqs; J.bbs = d_bbs; J.seq_idx = level == 0 ? ctx->poa_lv[0].seq_idx.p : nullptr; J.job_off = Lv.job_off; J.job_bb = Lv.job_bb; J.njobs = cap[par];
-            J.m = hp.m; J.n = hp.n; J.g = hp.g; J.Vcap = (int)capV; J.Ecap = (int)(3 * capV / 2); J.Lmax = Lmax; J.D = slots; J.node_cap = hp.node_cap; J.trim_tiles = (hp.trim_tiles & 1) | ((level > 0 && (hp.trim_tiles & 1)) ? 2 : 0); J.job_final = (hp.trim_tiles & 4) ? Lv.job_final : nullptr;
-            J.out = Lv.out; J.out_len = Lv.out_len; J.out_cw = Lv.out_cw; J.out_n = Lv.out_n; J.out_cov = Lv.out_cov; J.out_span = Lv.out_span;
-            J.dropped = d_ctrl.p + C_FLAGS; J.slot_overflow = d_ctrl.p + C_FLAGS + 1;
-            J.job_list = nullptr; J.nrun = 0; J.nrun_dev = d_ctrl.p + C_NJOBS + par;
+            PoaJobSet J = level_jobs(ctx, hp, plan, level, slots, level == 0 ? d_level0 : (const PSeq*)Nx.seqs, d_bbs, level == 0 ? ctx->poa_lv[0].seq_idx.p : nullptr, cap[par], d_ctrl.p + C_FLAGS);
+            J.nrun_dev = d_ctrl.p + C_NJOBS + par;
             int32_t rc = poa_launch(ctx, plan, J, band0, false, d_ctrl.p + C_WORK + 3 * level, hp.sub && level == 0); if (rc) return rc;
             int stage = 0;
             for (int bw = band0 * 2; bw <= 256; bw *= 2, ++stage) {          // band-edge check (oracle run_tile): flagged tiles run again, whole, with twice the band

@@ -158,14 +158,15 @@ def test_short_tail_window_parity(gpu_api, oracle, L):
         assert a == b and np.array_equal(ua, ub), tail
 
 
-def test_device_driven_levels_equal_host_driven_levels(gpu_api, oracle):
+def test_device_driven_levels_equal_host_driven_levels(gpu_api, oracle, capfd, monkeypatch):
     """round 3: the hierarchy levels are chained on the device (tile counts, next-level sequence descriptors and tile lists built by small kernels,
     one synchronisation per hierarchy).  The host-driven loop (ngsid_ctx_option poa_host_levels = 1, also the fall-back when the planned launch
     geometry does not fit) must give the same bytes: draft consensus with coverage over many groups of very different sizes (1 .. 400 reads,
-    empty groups, more groups than one scan block), polishing with early stop, depth 6 / 8 / 3 / one-tile, band redo."""
+    empty groups, more groups than one scan block), polishing with early stop, depth 6 / 8 / 3 / one-tile, band redo, and the fall-back itself."""
     from ngspeciesid_amd import runtime
     host = runtime.new_api(options={"poa_host_levels": 1})
     small = runtime.new_api(options={"poa_level_budget_mb": 1})       # round 5: units are batched under a byte budget (here: nearly one batch per unit) - same bytes
+    tight = runtime.new_api(options={"poa_out_slots": 1})             # one output slot per tile: a tile that closes its graph overflows it
     try:
         rng = np.random.default_rng(3)
         sizes = [1, 2, 0, 7, 400, 13, 6, 36, 37, 0, 216, 5] + [int(x) for x in rng.integers(1, 30, 1200)]
@@ -187,6 +188,16 @@ def test_device_driven_levels_equal_host_driven_levels(gpu_api, oracle):
             if prm.tile_depth in (4, 6, 3):
                 c = small.poa_consensus_cov(rs, goff, prm)
                 assert [x[0] for x in a] == [y[0] for y in c] and all(np.array_equal(x[1], y[1]) for x, y in zip(a, c))
+        # the fall-back: room for only 64 nodes more than the first read, so tiles of four close their graph and emit two consensuses.  With one output slot the
+        # device-driven levels give up and the host-driven loop runs the call again, with more slots - the bytes of the default context
+        prm = poa_params(tile_depth=4, band=0, trim=1, node_cap=16)
+        a = gpu_api.poa_consensus_cov(rs, goff, prm)
+        capfd.readouterr()
+        monkeypatch.setenv("NGSID_HOST_TIMERS", "1")
+        c = tight.poa_consensus_cov(rs, goff, prm)
+        monkeypatch.delenv("NGSID_HOST_TIMERS")
+        assert "gave up (geometry)" in capfd.readouterr().err
+        assert [x[0] for x in a] == [y[0] for y in c] and all(np.array_equal(x[1], y[1]) for x, y in zip(a, c))
         first = [0, 1, 3, 4]                                   # groups checked against the oracle as well (the whole set would take the scalar oracle minutes)
         sub_off = np.concatenate(([0], np.cumsum([sizes[g] for g in first]))).astype(np.uint64)
         order = np.concatenate([np.arange(int(goff[g]), int(goff[g + 1])) for g in first]).astype(np.uint32)
@@ -206,7 +217,7 @@ def test_device_driven_levels_equal_host_driven_levels(gpu_api, oracle):
             assert x == z and np.array_equal(ux, uz)
             assert x == [sp[g].tobytes().decode() for g in big]
     finally:
-        host.close(); small.close()
+        host.close(); small.close(); tight.close()
 
 
 def test_minimizer_cache_is_keyed_by_content(gpu_api, oracle):

@@ -113,11 +113,13 @@ def test_subgraph_layers_equal_the_oracle_three_windows(gpu_api, oracle):
         _check(gpu_api, oracle, drafts, rs, off, prm, fns=("polish_trace",))
 
 
-def test_subgraph_layers_band_edge_redo(gpu_api, oracle):
+@pytest.mark.parametrize("host_levels", [0, 1])
+def test_subgraph_layers_band_edge_redo(gpu_api, oracle, host_levels):
     """the reads carry a 45-base insertion the draft lacks: at band 64 the tracebacks run into the clipped band edge and the tiles are redone at twice the band -
-    HIP == oracle with the rule on, and the library counts redone tiles"""
+    HIP == oracle with the rule on, with device-driven and with host-driven levels, and the library counts redone tiles"""
     amps, drafts = _amplicons(700, 1, seed=71, insert=45)
     rs, off = _reads(amps, [90], seed=80, mu=16.0)
+    gpu_api.lib.ngsid_ctx_option(gpu_api.ctx, b"poa_host_levels", ctypes.c_int64(host_levels))
     gpu_api.lib.ngsid_profile_enable(gpu_api.ctx, ctypes.c_int32(1))
     buf = ctypes.create_string_buffer(1 << 14); gpu_api.lib.ngsid_profile_read(gpu_api.ctx, buf, ctypes.c_uint64(len(buf)))      # reset the counters
     try:
@@ -126,6 +128,7 @@ def test_subgraph_layers_band_edge_redo(gpu_api, oracle):
         gpu_api.lib.ngsid_profile_read(gpu_api.ctx, buf, ctypes.c_uint64(len(buf)))
     finally:
         gpu_api.lib.ngsid_profile_enable(gpu_api.ctx, ctypes.c_int32(0))
+        gpu_api.lib.ngsid_ctx_option(gpu_api.ctx, b"poa_host_levels", ctypes.c_int64(0))
     redo = [int(l.split()[1]) for l in buf.value.decode().splitlines() if l.startswith("poa_band_redo_tiles")]
     assert redo and redo[0] >= 1, "no tile was redone with a wider band: %s" % buf.value.decode()
 

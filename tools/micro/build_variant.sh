@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev helper (build container): build_alt/libngsid_hip_<name>.so = the library with ONE source (default k_poa.hip; SRC=k_ed_align.hip ...) compiled with extra -D flags.
-#   tools/micro/build_variant.sh lt -DPOA_LT=1        SRC=k_ed_align.hip tools/micro/build_variant.sh ck8 -DED_CK=8
+#   tools/micro/build_variant.sh ph -DPOA_PHASES=1       SRC=k_ed_align.hip tools/micro/build_variant.sh ck8 -DED_CK=8
 set -e
 NAME=$1; shift
 SRC=${SRC:-k_poa.hip}; BASE=${SRC%.hip}
