@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """bench.py - reads/s end-to-end (cluster + spoa-style consensus + racon-style polish x3) on synthetic 750 bp ONT reads.
 
-    python bench.py --gpus 1 --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W [--full]        (N>1: launched by torch.distributed.run, one rank per GPU)
 
 One step = one pass of the hot path over the whole batch of synthetic reads, inputs resident in HBM.
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how roofline / cpu_baseline are obtained.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints `value` with what the timed steps recorded themselves (stage and
+kernel times, device memory).  --full adds every other leg and check after the timed steps: the quality checks (config.check), the roofline, the step with
+the early stop and the one-lane step, host buffers in, the CLI legs and the CPU baseline.  See DESIGN.md "Measurement" for how roofline / cpu_baseline are obtained.
 """
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -116,22 +118,28 @@ def main():
     ap.add_argument("--tile-depth", type=int, default=4, help="reads per POA tile (pipeline / CLI default 4 since round 5)")
     ap.add_argument("--band", type=int, default=0, help="POA band width in columns of the first attempt (64 / 128 / 256); 0 = library default (64 for reads up to 3 000 bases)")
     ap.add_argument("--node-cap", type=int, default=0, help="POA graph capacity in 1/16 of the first sequence length (0 = library default)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run and report everything beside the headline: config.check (cluster purity, consensus against the amplicons), roofline, "
+                    "config.with_stable_stop and the one-lane step, config.host_buffers_in, config.cli, cpu_baseline (each leg has a --no-... switch of its own); a run without it stops at the headline")
     ap.add_argument("--cpu-sample", type=int, default=1500, help="reads per worker process of the cpu_baseline leg")
     ap.add_argument("--cpu-cores", type=int, default=0, help="worker processes of the cpu_baseline leg (0 = all host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-step", action="store_true", help="skip the extra step with stop_when_stable (profiling runs that count per-step traffic)")
-    ap.add_argument("--no-cli", action="store_true", help="skip the file-in -> files-out leg (the drop-in CLI on the same reads, reported as config.cli)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-extra-step", action="store_true", help="--full without the extra step with stop_when_stable, the one-lane step and the host-buffers leg")
+    ap.add_argument("--no-cli", action="store_true", help="--full without the file-in -> files-out leg (the drop-in CLI on the same reads, reported as config.cli)")
     ap.add_argument("--cli-t", type=int, default=1, help="--t of the CLI leg (the reference's batch count; 1 = one clustering pass)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="default: strong for --config c4 / c5 with --gpus N > 1 (BASELINE quotes them as ONE global set over 8 GPUs), weak otherwise.  weak: --reads per GPU, an independent set per rank.  strong: ONE global score-sorted set of --reads reads, rank g gets batch g+1 of the "
                          "reference's `--t N` partition (parallelize.batch_list total_nt), so the N-GPU membership is the reference's --t N membership of that set")
-    ap.add_argument("--check-membership", action="store_true", help="strong scaling: after the timed region rank 0 replays the `--t N` schedule on one GPU and compares the membership")
+    ap.add_argument("--check-membership", action="store_true", help="--full, strong scaling: after the timed region rank 0 replays the `--t N` schedule on one GPU and compares the membership")
     ap.add_argument("--master-port", type=int, default=0, help="--gpus N > 1 started directly: the rendezvous port of the ranks this process launches (0 = a free one)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all; a fixed, seeded sample of the per-read arrays beyond 1 M reads)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.check_membership and not args.full:
+        ap.error("--check-membership is one of the checks of --full")
+    # what runs after the timed steps: nothing in a plain run, every leg that is not switched off in a --full one
+    extra_step, cli_legs, cpu_leg = args.full and not args.no_extra_step, args.full and not args.no_cli, args.full and not args.no_cpu_baseline
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` IS the N-GPU run: a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>`,
         # one rank per GPU over RCCL (backend nccl; NGSID_DIST_BACKEND=gloo only as a dev aid for more ranks than GPUs).  stdout is inherited, so rank 0's JSON line is this command's.
@@ -255,14 +263,14 @@ def main():
         if nm_ in kern: kern[nm_] = max((d_.get(nm_, (0, 0.0)) for d_ in kern_per_ctx), key=lambda v_: v_[0])
     # one extra (untimed for `value`) step with the library default: polishing of a cluster stops once an iteration leaves it unchanged
     res_stop, dt_stop = None, 0.0
-    if not args.no_extra_step:
+    if extra_step:
         barrier(); t1 = time.perf_counter()
         res_stop = step(polish_stop_when_stable=True)
         barrier(); dt_stop = time.perf_counter() - t1
     # with lanes (config.lanes) the launches of two contexts overlap on the device and the HIP-event bracket of a launch includes what it waited for the other lane: one more
     # untimed step in ONE context gives every kernel's time alone (roofline.one_lane: the figures the committed counter passes and rocprof summaries of a single lane match)
     one_lane = None
-    if n_lanes > 1 and not args.no_extra_step:
+    if n_lanes > 1 and extra_step:
         saved_ = api.lanes; api.lanes = 1; api.profile_enable(True)
         try: step()
         finally: api.lanes = saved_
@@ -307,16 +315,19 @@ def main():
         return
     stop_same = None if res_stop is None else [c[3] for c in res_stop["centers"]] == [c[3] for c in res["centers"]]
     reads_per_s = n_total * args.steps / dt
-    # ---- quality / property checks at full size (size-independent): cluster purity, consensus vs generating amplicon
-    spc = rd["species"].cpu().numpy(); rep_of = res["rep_of"]
-    big = [c for c in res["centers"]]
-    purity = float(sum(np.bincount(spc[rep_of == r]).max() for r in np.unique(rep_of)) / n)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from util_seq import edit_distance
-    truths = [s.tobytes().decode() for s in sp]
-    ed = []; tset = set(truths)
-    for c in big:           # exact hits first (50 species x 50 truths x 16 end trims of a row-vectorised edit distance would take minutes)
-        ed.append(0 if c[3] in tset else min(min(edit_distance(c[3][a:len(c[3]) - b if b else None], t) for a in range(4) for b in range(4)) for t in truths))
+    check = None
+    if args.full:
+        # ---- quality / property checks at full size (size-independent): cluster purity, consensus vs generating amplicon
+        spc = rd["species"].cpu().numpy(); rep_of = res["rep_of"]
+        big = [c for c in res["centers"]]
+        purity = float(sum(np.bincount(spc[rep_of == r]).max() for r in np.unique(rep_of)) / n)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from util_seq import edit_distance
+        truths = [s.tobytes().decode() for s in sp]
+        ed = []; tset = set(truths)
+        for c in big:           # exact hits first (50 species x 50 truths x 16 end trims of a row-vectorised edit distance would take minutes)
+            ed.append(0 if c[3] in tset else min(min(edit_distance(c[3][a:len(c[3]) - b if b else None], t) for a in range(4) for b in range(4)) for t in truths))
+        check = {"cluster_purity": round(purity, 5), "centers": len(big), "consensus_edit_distance_vs_truth": ed, "membership_equals_reference_t_n": membership_ok, "sharded_consensus_equals_single_process": single_same}
     # ---- roofline of the dominant kernel (HIP-event times on the library's own stream)
     redo_tiles = kern.pop("poa_band_redo_tiles", (0, 0.0))[0]
     mem_parts = {k_[4:]: round(kern.pop(k_)[0] / 1e9, 2) for k_ in [x for x in kern if x.startswith("mem_")]}      # grow-only scratch of the context by purpose (GB)
@@ -333,13 +344,14 @@ def main():
     alg_step = {"k_sg_align": f_aln * n * 4 * L, "k_poa_tile": 4.0 * n * 2 * L, "k_ed_align": 3.0 * n_pol * 4 * L, "k_hpc_minimizers": n * (2 * L + 12 * M),
                 "k_count_hits": n * (12 * M + 8), "k_decide_map": n * (12 * M + 8), "k_aln_next": n * 8.0}
     tj, tj_file = None, None
-    try:    # HBM bytes per step from the committed PMC passes of THIS round (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs, tools/r06_profiles.sh): a counter pass
-            # cannot run inside this process, so the figure is a measurement of the recorded commit on the recorded workload, not of this run
-        tj_file = next(f for f in ("r06_hbm_traffic.json", "r05_hbm_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
-        tj = json.load(open(os.path.join(ROOT, "profiles", tj_file)))
-        if not (tj.get("workload_reads") == args.reads and tj.get("config", "c3") == args.config and tj.get("tile_depth", args.tile_depth) == args.tile_depth): tj = None
-    except Exception:
-        tj = None
+    if args.full:
+        try:    # HBM bytes per step from the committed PMC passes of THIS round (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs, tools/r06_profiles.sh): a counter pass
+                # cannot run inside this process, so the figure is a measurement of the recorded commit on the recorded workload, not of this run
+            tj_file = next(f for f in ("r06_hbm_traffic.json", "r05_hbm_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", f)))
+            tj = json.load(open(os.path.join(ROOT, "profiles", tj_file)))
+            if not (tj.get("workload_reads") == args.reads and tj.get("config", "c3") == args.config and tj.get("tile_depth", args.tile_depth) == args.tile_depth): tj = None
+        except Exception:
+            tj = None
     def kernel_line(nm):
         cnt, ms = kern[nm]
         alg = alg_step.get(nm, n * 2.0 * L) * args.steps           # bytes over the timed steps
@@ -352,7 +364,7 @@ def main():
                       "traffic_GBps": round(tb * args.steps / sec / 1e9, 1) if sec > 0 else None, "traffic_frac_of_peak": round(tb * args.steps / sec / 8e12, 4) if sec > 0 else None})
         return v
     roof = None
-    if dom[0]:
+    if dom[0] and args.full:
         cnt, ms = dom[1]
         alg_bytes_per_launch = alg_step.get(dom[0], n * 2.0 * L) * args.steps / max(cnt, 1)
         avg_s = ms / 1e3 / max(cnt, 1)
@@ -427,7 +439,7 @@ def main():
                 roof["one_lane"] = ol
     # ---- host buffers in (the C-ABI takes either): ONE copy of the read set over PCIe (ngsid_reads_upload) + one pass of the hot path on it; reported beside `value`, never as it
     host_leg = None
-    if not args.no_extra_step and world == 1:
+    if extra_step and world == 1:
         try:
             hrs_ = ReadSet(rd["seq"].cpu().numpy(), rd["qual"].cpu().numpy(), rd["off"].cpu().numpy().astype(np.uint64))
             torch.cuda.synchronize(); t_ = time.perf_counter()
@@ -442,7 +454,7 @@ def main():
             host_leg = {"error": repr(e)}
     # ---- the drop-in surface (runs before the CPU baseline leg): FASTQ file in -> the reference's output files out (python -m ngspeciesid_amd ...), same reads, same flags as C3
     cli_leg = None
-    if not args.no_cli and world == 1:
+    if cli_legs and world == 1:
         import shutil, tempfile, argparse as _ap
         from ngspeciesid_amd import fastio, fastpath, cli as _cli
         base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
@@ -503,7 +515,7 @@ def main():
     # ---- CPU baseline: the oracle (a scalar port of the same algorithms) on a bounded sample of the same workload: one core, and all host cores
     #      with one batch per core like the reference's `--t N` worker processes (merge rounds not included: they are O(representatives))
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if cpu_leg and world == 1:
         import subprocess, tempfile, shutil
         from oracle_lib import load_oracle
         from ngspeciesid_amd import parallelize
@@ -574,14 +586,14 @@ def main():
                       "poa_single_below": pipeline.SINGLE_BELOW, "reads_clustered_per_gpu": n, "f_aln": round(f_aln, 4), "stage_s_per_step": {k_: round(v / args.steps, 4) for k_, v in T.items()}, "stage_s_per_step_max_over_ranks": None if stage_max is None else {k_: round(v / args.steps, 4) for k_, v in stage_max.items()},
                       "kernel_ms_per_step": {k_: round(v[1] / args.steps, 2) for k_, v in kern.items()}, "kernel_ms_per_step_one_lane": None if not one_lane else {k_: round(v_, 2) for k_, v_ in one_lane.items()}, "lanes": n_lanes, "library_host_ms_per_step": {k_: round(v[1] / args.steps, 2) for k_, v in host_lines.items()}, "poa_tiles_redone_with_wider_band_per_step": round(redo_tiles / args.steps, 1),
                       "hbm_gb": {"peak_in_timed_steps": round(hbm_peak / 1e9, 2), "held_after": round(hbm_live / 1e9, 2), "what": "bytes handed out by the library's device allocator, whole process (read set included)", "context_scratch_by_purpose": mem_parts},
-                      "check": {"cluster_purity": round(purity, 5), "centers": len(big), "consensus_edit_distance_vs_truth": ed, "membership_equals_reference_t_n": membership_ok, "sharded_consensus_equals_single_process": single_same}},
+                      "check": check},
            "roofline": roof, "cpu_baseline": cpu}
     if dist is not None:
         out["config"]["ranks"] = {"world_size": world, "ranks_in_the_all_reduce": ranks_seen, "distinct_gpus": gpus_seen, "backend": backend + (" (= RCCL)" if backend == "nccl" else " (dev aid: collectives on the host, ranks may share a GPU)")}
     if world > 1:
         out["config"]["baseline_config_of_this_line"] = ("%s of BASELINE.json, %s" % (args.config.upper(), "ONE global set split into the reference's `--t %d` batches (strong scaling)" % world if args.scaling == "strong" else
                                                          "its per-GPU shape repeated on every GPU with an independent read set per rank (weak scaling%s)" % ("; C3 is BASELINE's 1-GPU configuration" if args.config == "c3" else "")))
-        out["config"]["eight_gpu_configurations"] = "BASELINE.json quotes C4 (10 M x 750 bp, 50 species) and C5 (2 M x 2 kb CCS, 20 species) on 8 GPUs as ONE global set: python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --config c4 --scaling strong --check-membership   (likewise --config c5)"
+        out["config"]["eight_gpu_configurations"] = "BASELINE.json quotes C4 (10 M x 750 bp, 50 species) and C5 (2 M x 2 kb CCS, 20 species) on 8 GPUs as ONE global set: python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --config c4 --scaling strong --full --check-membership   (likewise --config c5)"
     if dumped is not None: out["config"]["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if cli_leg is not None: out["config"]["cli"] = cli_leg
     if host_leg is not None: out["config"]["host_buffers_in"] = host_leg

@@ -1,6 +1,7 @@
 """bench.py --dump-outputs: what the timed path returned, written as float32 / float64 .npy files that give the result back exactly, the whole dump under
-64 MB with a seeded (repeatable) sample of larger outputs.  The hot path runs on the oracle backend here; bench.py itself needs the GPU."""
-import importlib.util, os
+64 MB with a seeded (repeatable) sample of larger outputs.  The hot path runs on the oracle backend here; bench.py itself needs the GPU
+(its usage errors do not)."""
+import importlib.util, os, subprocess, sys
 import numpy as np
 from ngspeciesid_amd import synth, pipeline
 from ngspeciesid_amd._capi import ReadSet
@@ -57,3 +58,9 @@ def test_large_outputs_are_a_seeded_sample_under_64_mb(tmp_path):
     assert np.array_equal(a["rep_of"], res["rep_of"][ri]) and np.array_equal(a["hpc_err"], res["hpc_err"][ri])
     ci = a["center_index"].astype(np.int64)
     assert 0 < len(ci) < 20000 and np.array_equal(a["center_id"], ci) and len(a["center_polished"]) == 999 * len(ci)
+
+
+def test_check_membership_is_refused_without_full():
+    """the membership replay is one of the checks of --full: a plain run that asks for it is a usage error (before anything touches a GPU)"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--check-membership"], timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert p.returncode == 2 and "--full" in p.stderr and p.stdout == ""

@@ -63,7 +63,7 @@ def test_strong_scaling_ranks_on_one_gpu_membership_equals_t_n(world, lanes_unde
     if lanes_under_ranks: env["NGSID_LANES_FORCE"] = "1"                   # every rank deals its consensus calls to two contexts, as it does on a GPU of its own (bench.py turns the lanes off when ranks share a device)
     # world 2: `python bench.py --gpus 2 ...` as the driver types it - bench.py starts its own ranks; world 4: under the launcher, as the contract's N > 1 command
     head = [sys.executable] if (world == 2 and not lanes_under_ranks) else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29530 + world + (10 if lanes_under_ranks else 0))]
-    cmd = head + [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--reads", "240000", "--scaling", "strong", "--check-membership",
+    cmd = head + [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "0", "--reads", "240000", "--scaling", "strong", "--full", "--check-membership",
            "--no-cpu-baseline", "--no-extra-step"]
     p = subprocess.run(cmd, env=env, timeout=1200, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.splitlines() if "Error" in l and "ChildFailed" not in l)[:3000] + "\n...\n" + p.stderr[-1500:]
@@ -82,7 +82,7 @@ def test_rccl_collectives_single_rank_strong_scaling():
     (NGSID_FORCE_DIST=1 - the test box has one GPU; 2-, 4- and 8-rank runs use gloo).  Payloads travel device -> all_gather_into_tensor -> host as they will on a node."""
     env = dict(os.environ); env["MASTER_ADDR"] = "127.0.0.1"; env["NGSID_FORCE_DIST"] = "1"; env.pop("NGSID_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29571",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--reads", "200000", "--scaling", "strong", "--check-membership", "--no-cpu-baseline", "--no-extra-step", "--no-cli"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--reads", "200000", "--scaling", "strong", "--full", "--check-membership", "--no-cpu-baseline", "--no-extra-step", "--no-cli"]
     p = subprocess.run(cmd, env=env, timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

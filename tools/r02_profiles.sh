@@ -3,13 +3,13 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r2; mkdir -p $O
 # 1. the bench line (defaults)
-python $R/bench.py > $O/r02_bench_1m.json 2> $O/r02_bench_1m.err
+python $R/bench.py --full > $O/r02_bench_1m.json 2> $O/r02_bench_1m.err
 # 2. kernel trace + stats of the same command (no CPU / CLI legs: they add no kernels of interest)
-rm -rf $O/prof_stats; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o r02 -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-cli > $O/prof_stats.log 2>&1
+rm -rf $O/prof_stats; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o r02 -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-cli > $O/prof_stats.log 2>&1
 cp $(find $O/prof_stats -name "*kernel_stats.csv" | head -1) $O/r02_rocprofv3_kernel_stats_1m.csv 2>/dev/null
 # 3. HBM traffic: separate FETCH_SIZE / WRITE_SIZE passes, one bench step
 for C in FETCH_SIZE WRITE_SIZE; do
-  rm -rf $O/pmc_$C; timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -o pmc -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-step --no-cli > $O/pmc_$C.log 2>&1
+  rm -rf $O/pmc_$C; timeout 900 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -o pmc -- python $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra-step --no-cli > $O/pmc_$C.log 2>&1
 done
 cd $R
 python - <<PY

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3m; mkdir -p $O
 rocprofv3 --list-avail > $O/avail.txt 2>&1 || rocprofv3 -L > $O/avail.txt 2>&1
-BARGS="--no-cpu-baseline --no-cli --no-extra-step"
+BARGS="--full --no-cpu-baseline --no-cli --no-extra-step"
 have() { grep -q -w "$1" $O/avail.txt; }
 pass() {   # name, counters...
   n=$1; shift; sel=""

@@ -3,11 +3,11 @@
 # ONE phase twice (tools/micro/build_repeat.sh); a time run and an SQ-counter run each.  -> gpurun_out/r4/phase_cost.json
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4; mkdir -p $O
-BARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-cli --no-extra-step"
+BARGS="--steps 1 --warmup 1 --full --no-cpu-baseline --no-cli --no-extra-step"
 for V in base rep1 rep2 rep3 rep4; do
   LIB=$R/build_alt/libngsid_hip_$V.so; [ $V = base ] && LIB=$R/ngspeciesid_amd/libngsid_hip.so
   timeout 600 python $R/tools/micro/bench_with_lib.py $LIB $BARGS > $O/pc_$V.json 2> $O/pc_$V.err
-  rm -rf $O/pc_pmc_$V; timeout 900 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pc_pmc_$V -o pmc -- python $R/tools/micro/bench_with_lib.py $LIB --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-extra-step > $O/pc_pmc_$V.log 2>&1
+  rm -rf $O/pc_pmc_$V; timeout 900 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pc_pmc_$V -o pmc -- python $R/tools/micro/bench_with_lib.py $LIB --steps 1 --warmup 0 --full --no-cpu-baseline --no-cli --no-extra-step > $O/pc_pmc_$V.log 2>&1
 done
 cd $R
 python - <<PY

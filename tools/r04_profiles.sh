@@ -3,9 +3,9 @@
 # (counters never together with traces other than --kernel-trace).  Usage: NGSID_COMMIT=<git rev> bash tools/r04_profiles.sh
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4; mkdir -p $O
-BARGS="--no-cpu-baseline --no-cli"
+BARGS="--full --no-cpu-baseline --no-cli"
 # 1. the bench line (defaults: C3, 1 GPU)
-timeout 900 python $R/bench.py > $O/r04_bench_1m.json 2> $O/r04_bench_1m.err
+timeout 900 python $R/bench.py --full > $O/r04_bench_1m.json 2> $O/r04_bench_1m.err
 # 2. kernel trace + stats of the same command
 rm -rf $O/prof_stats; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o r04 -- python $R/bench.py --steps 2 --warmup 1 $BARGS > $O/prof_stats.log 2>&1
 cp $(find $O/prof_stats -name "*kernel_stats.csv" | head -1) $O/r04_rocprofv3_kernel_stats_1m.csv 2>/dev/null
@@ -34,7 +34,7 @@ for C in ("FETCH_SIZE","WRITE_SIZE"):
         k=cls(r["Kernel_Name"])
         if k and r["Counter_Name"]==C: agg[k]+=float(r["Counter_Value"]); disp[k].add(r["Dispatch_Id"])
     for k in agg: res[k][C]=agg[k]; res[k]["launches_"+C]=len(disp[k])
-out={"_how":"tools/r04_profiles.sh on the GPU box: rocprofv3 --pmc FETCH_SIZE --kernel-trace and (separate pass) --pmc WRITE_SIZE -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-step --no-cli (C3: 1 M reads, POA tile depth 6, device-driven hierarchy levels)",
+out={"_how":"tools/r04_profiles.sh on the GPU box: rocprofv3 --pmc FETCH_SIZE --kernel-trace and (separate pass) --pmc WRITE_SIZE -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra-step --no-cli (C3: 1 M reads, POA tile depth 6, device-driven hierarchy levels)",
      "_units":"counter values are KiB summed over all dispatches of the kernel in ONE bench step; FETCH_SIZE on gfx950 under-reports wide coalesced reads by 2x (MI355X_MICROARCH.md, HBM section): hbm_bytes_per_step = 2 x fetch + write",
      "workload_reads":1000000,"config":"c3","commit":commit}
 for k,v in res.items():
@@ -64,7 +64,7 @@ if sq and rows:
        "kernel_ns_under_the_counter_pass":dur,
        "pipe_busy":round(sq["SQ_INSTS_VALU"]*4/(1024*(sq["SQ_BUSY_CYCLES"]/32.0)),3) if sq.get("SQ_BUSY_CYCLES") else None,
        "raw":{k:int(v) for k,v in sq.items()},
-       "_how":"rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM --kernel-trace -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-extra-step, summed over every k_poa_tile1 dispatch of the step; rows = DP rows of the same step from NGSID_POA_PHASES=1 (r04_poa_phases.txt); pipe_busy = VALU instructions x 4 cycles / (1 024 SIMDs x busy cycles per shader engine)"}
+       "_how":"rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM --kernel-trace -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-cli --no-extra-step, summed over every k_poa_tile1 dispatch of the step; rows = DP rows of the same step from NGSID_POA_PHASES=1 (r04_poa_phases.txt); pipe_busy = VALU instructions x 4 cycles / (1 024 SIMDs x busy cycles per shader engine)"}
     json.dump(j,open("gpurun_out/r4/r04_pmc_poa_tile.json","w"),indent=1); print(json.dumps({k:v for k,v in j.items() if k not in ("raw","_how")}))
 PY
 python - <<PY

@@ -4,7 +4,7 @@
 # -> gpurun_out/r4/r04_timeline.json.   Usage: bash tools/r04_timeline.sh [extra bench args]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4; mkdir -p $O
-rm -rf $O/prof_tl; timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/prof_tl -o tl -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cli --no-extra-step "$@" > $O/prof_tl.log 2>&1
+rm -rf $O/prof_tl; timeout 900 rocprofv3 --kernel-trace --output-format csv -d $O/prof_tl -o tl -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-cli --no-extra-step "$@" > $O/prof_tl.log 2>&1
 cd $R
 python - <<PY
 import csv, glob, json, collections, re
@@ -28,7 +28,7 @@ wall = busy_end - step[0][0]
 kern = collections.Counter(); kc = collections.Counter()
 for s, e, nm in step: kern[short(nm)] += e - s; kc[short(nm)] += 1
 poa = [round((e - s) / 1e6, 3) for s, e, nm in step if "k_poa_tile" in nm]
-out = {"_how": "tools/r04_timeline.sh: rocprofv3 --kernel-trace -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cli --no-extra-step; the timed step = dispatches from the last clustering call's k_hpc_minimizers launch on; gap = start of a dispatch minus the latest end of all earlier ones",
+out = {"_how": "tools/r04_timeline.sh: rocprofv3 --kernel-trace -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-cli --no-extra-step; the timed step = dispatches from the last clustering call's k_hpc_minimizers launch on; gap = start of a dispatch minus the latest end of all earlier ones",
        "step_wall_ms": round(wall / 1e6, 2), "gpu_idle_ms": round(tot_gap / 1e6, 2), "dispatches": len(step),
        "idle_ms_by_transition": {"%s -> %s" % k: [round(v / 1e6, 2), cnt[k]] for k, v in per.most_common(25)},
        "kernel_ms": {k: [round(v / 1e6, 2), kc[k]] for k, v in kern.most_common(30)},

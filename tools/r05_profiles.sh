@@ -3,9 +3,9 @@
 # (counters never together with traces other than --kernel-trace).  Usage: NGSID_COMMIT=<git rev> bash tools/r05_profiles.sh
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5; mkdir -p $O
-BARGS="--no-cpu-baseline --no-cli"
+BARGS="--full --no-cpu-baseline --no-cli"
 # 1. the bench line (defaults: C3, 1 GPU)
-timeout 900 python $R/bench.py > $O/r05_bench_1m.json 2> $O/r05_bench_1m.err
+timeout 900 python $R/bench.py --full > $O/r05_bench_1m.json 2> $O/r05_bench_1m.err
 # 2. kernel trace + stats of the same command
 rm -rf $O/prof_stats; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o r04 -- python $R/bench.py --steps 2 --warmup 1 $BARGS > $O/prof_stats.log 2>&1
 cp $(find $O/prof_stats -name "*kernel_stats.csv" | head -1) $O/r05_rocprofv3_kernel_stats_1m.csv 2>/dev/null
@@ -34,7 +34,7 @@ for C in ("FETCH_SIZE","WRITE_SIZE"):
         k=cls(r["Kernel_Name"])
         if k and r["Counter_Name"]==C: agg[k]+=float(r["Counter_Value"]); disp[k].add(r["Dispatch_Id"])
     for k in agg: res[k][C]=agg[k]; res[k]["launches_"+C]=len(disp[k])
-out={"_how":"tools/r05_profiles.sh on the GPU box: rocprofv3 --pmc FETCH_SIZE --kernel-trace and (separate pass) --pmc WRITE_SIZE -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-step --no-cli (C3: 1 M reads, POA tile depth 4, device-driven hierarchy levels)",
+out={"_how":"tools/r05_profiles.sh on the GPU box: rocprofv3 --pmc FETCH_SIZE --kernel-trace and (separate pass) --pmc WRITE_SIZE -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-extra-step --no-cli (C3: 1 M reads, POA tile depth 4, device-driven hierarchy levels)",
      "_units":"counter values are KiB summed over all dispatches of the kernel in ONE bench step; FETCH_SIZE on gfx950 under-reports wide coalesced reads by 2x (MI355X_MICROARCH.md, HBM section): hbm_bytes_per_step = 2 x fetch + write",
      "workload_reads":1000000,"config":"c3","commit":commit}
 for k,v in res.items():
@@ -53,7 +53,7 @@ if fs2:
     for k,v in acc.items():
         raw2[k]={a:int(b) for a,b in v.items()}
         if v.get("SQ_BUSY_CU_CYCLES"): pb[k]=round(v["SQ_ACTIVE_INST_VALU"]/v["SQ_BUSY_CU_CYCLES"],4)      # both in quad-cycles per SIMD (see _units of profiles/r05_pmc_pipe_busy.json)
-    json.dump({"_how":"rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_INSTS_FLAT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-extra-step; counters summed over all dispatches of the kernel family in the step","commit":commit,"active_valu_over_busy":pb,"raw":raw2},open("gpurun_out/r5/r05_pmc_pipe_busy.json","w"),indent=1)
+    json.dump({"_how":"rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_INSTS_FLAT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-cli --no-extra-step; counters summed over all dispatches of the kernel family in the step","commit":commit,"active_valu_over_busy":pb,"raw":raw2},open("$O/r05_pmc_pipe_busy.json","w"),indent=1)
     print(json.dumps({"active_valu_over_busy":pb}))
 # SQ counters of k_poa_tile1 over the step
 fs=glob.glob("gpurun_out/r5/pmc_sq/**/*counter_collection.csv",recursive=True)
@@ -82,7 +82,7 @@ if sq and rows:
        "pipe_busy":pb.get("k_poa_tile1"),"pipe_busy_how":"second counter pass (pmc_sq2): SQ_ACTIVE_INST_VALU / SQ_BUSY_CU_CYCLES summed over the kernel's dispatches (both in quad-cycles per SIMD: no cycle count per instruction is assumed); see raw_second_pass and profiles/r05_pmc_pipe_busy.json",
        "raw_second_pass":raw2.get("k_poa_tile1"),
        "raw":{k:int(v) for k,v in sq.items()},
-       "_how":"rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM --kernel-trace -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-cli --no-extra-step, summed over every k_poa_tile1 dispatch of the step; rows = DP rows the kernels counted in the same run (poa_dp_rows); pipe_busy = SQ_ACTIVE_INST_VALU / SQ_BUSY_CYCLES of a second counter pass"}
+       "_how":"rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM --kernel-trace -- python bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-cli --no-extra-step, summed over every k_poa_tile1 dispatch of the step; rows = DP rows the kernels counted in the same run (poa_dp_rows); pipe_busy = SQ_ACTIVE_INST_VALU / SQ_BUSY_CYCLES of a second counter pass"}
     json.dump(j,open("gpurun_out/r5/r05_pmc_poa_tile.json","w"),indent=1); print(json.dumps({k:v for k,v in j.items() if k not in ("raw","_how")}))
 PY
 python - <<PY

@@ -4,7 +4,7 @@
 # -> gpurun_out/r6/r06_timeline.json.   Usage: bash tools/r06_timeline.sh [extra bench args]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6; mkdir -p $O
-rm -rf $O/prof_tl; timeout 900 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/prof_tl -o tl -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cli --no-extra-step "$@" > $O/prof_tl.log 2>&1
+rm -rf $O/prof_tl; timeout 900 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/prof_tl -o tl -- python $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-cli --no-extra-step "$@" > $O/prof_tl.log 2>&1
 cd $R
 python - <<PY
 import csv, glob, json, collections, re
@@ -37,7 +37,7 @@ poa = [round((e - s) / 1e6, 3) for s, e, nm in step if nm.startswith("k_poa_tile
 gaps.sort(reverse=True)
 hist = collections.Counter()
 for g, *_ in gaps: hist["<20us" if g < 20e3 else "<100us" if g < 100e3 else "<1ms" if g < 1e6 else ">=1ms"] += g
-out = {"_how": "tools/r06_timeline.sh: rocprofv3 --kernel-trace --memory-copy-trace -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-cli --no-extra-step; the timed step = operations from the last clustering call's k_hpc_minimizers launch on; gap = start of an operation minus the latest end of all earlier ones",
+out = {"_how": "tools/r06_timeline.sh: rocprofv3 --kernel-trace --memory-copy-trace -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-cli --no-extra-step; the timed step = operations from the last clustering call's k_hpc_minimizers launch on; gap = start of an operation minus the latest end of all earlier ones",
        "step_wall_ms": round(wall / 1e6, 2), "gpu_idle_ms": round(tot_gap / 1e6, 2), "kernel_dispatches": sum(1 for r in step if not r[2].startswith("copy:")), "copies": sum(1 for r in step if r[2].startswith("copy:")),
        "idle_ms_by_gap_size": {k: round(v / 1e6, 2) for k, v in hist.items()},
        "idle_ms_by_transition": {"%s -> %s" % k: [round(v / 1e6, 2), cnt[k]] for k, v in per.most_common(30)},
