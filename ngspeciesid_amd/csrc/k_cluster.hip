@@ -4,15 +4,18 @@
 //
 // Data in HBM
 //   reads            CSR (bases, qualities, uint64 offsets), score order = greedy order
-//   minimizers       (code u64, pos u32) written sparsely at the read's base offset by k_hpc_minimizers
+//   minimizers       (code u64, pos u32) as a compact CSR of the context: those of read r start at mzoff[r] (ngsid_minimizers_csr)
 //   representatives  slot -> read id; per slot the SORTED UNIQUE codes of its minimizers (pool + offsets)
 //   index "DB"       all (code, slot) pairs sorted by code = minimizer_database (cluster.py:329-334)
 //   hit matrix       block_items x stride uint64, each cell = n_hits<<48 | sum(pos)  (get_all_hits :43-62)
-// Exactness of the parallel form: a block of reads is evaluated against a database snapshot; the first
-// read (in greedy order) that founds a new cluster is committed together with everything before it, its
-// minimizers are merged into the index, only the DELTA (hits against that one representative) is added to
-// the hit matrix of the later reads, and those are re-decided.  Aligner results are cached per
-// (read, representative) since they do not depend on the database.
+// Exactness of the parallel form: a block of reads is evaluated against a database snapshot.  The first reads
+// (in greedy order) that found new clusters - up to 64 per restart round - are built as TENTATIVE representatives
+// and the later items of the block are counted against each of them (one new hit-matrix column per representative).
+// Everything before the first item that one of them could affect is final; the tentative representatives before
+// that item are committed (merged into the index), the columns of the others are cleared, and of the rest of the
+// block only the items whose decision a committed representative can change (rep_can_matter) are decided again.
+// A block that keeps restarting is cut short: the items behind the cut are decided from scratch by the next block.
+// Aligner results are cached per (read, representative) since they do not depend on the database.
 #include "ngsid_internal.h"
 #include "../../include/ngsid_tables.h"
 #include <math.h>
@@ -57,10 +60,9 @@ __global__ void k_eidx(const double* __restrict__ herr, const double* __restrict
 // ---- hit counting: one wave per item, lanes over the read's minimizers, binary search in the sorted index
 __global__ __launch_bounds__(256)
 void k_count_hits(ClDev D, const uint32_t* __restrict__ items, uint32_t it_lo, uint32_t it_hi, uint32_t row0,
-                  const uint64_t* __restrict__ db_code, const uint32_t* __restrict__ db_slot, uint32_t const_slot, uint64_t n_db,
+                  const uint64_t* __restrict__ db_code, const uint32_t* __restrict__ db_slot, uint64_t n_db,
                   uint64_t* __restrict__ cnt, uint32_t stride)
 {
-    // db_slot == nullptr: the index is one representative's own sorted unique codes (delta pass), slot = const_slot
     const int lane = threadIdx.x & 63;
     const uint32_t it = it_lo + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (it >= it_hi || n_db == 0) return;
@@ -74,7 +76,7 @@ void k_count_hits(ClDev D, const uint32_t* __restrict__ items, uint32_t it_lo, u
         uint64_t lo = 0, hi = n_db;
         while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (db_code[mid] < code) lo = mid + 1; else hi = mid; }
         for (uint64_t p = lo; p < n_db && db_code[p] == code; ++p)
-            atomicAdd(&row[db_slot ? db_slot[p] : const_slot], (1ull << 48) + (unsigned long long)pos);
+            atomicAdd(&row[db_slot[p]], (1ull << 48) + (unsigned long long)pos);
     }
 }
 
@@ -264,33 +266,6 @@ __global__ void k_newrep_mask(const int32_t* __restrict__ dec, const uint32_t* _
     if (blockIdx.x == 0 && threadIdx.x == 0) { mask[w_tail] = ((unsigned long long)(unsigned)*eflag << 32) | (unsigned long long)*nreq; *nreq = 0u; }
 }
 
-// hits of the block items [it_lo,it_hi) against ONE freshly built representative (its sorted unique codes in the pool; the offsets are read on the
-// device, so tentative representatives need no host round trip)
-__global__ __launch_bounds__(256)
-void k_count_hits_rep(ClDev D, const uint32_t* __restrict__ items, uint32_t it_lo, uint32_t it_hi, uint32_t row0, uint32_t slot, uint64_t* __restrict__ cnt, uint32_t stride)
-{
-    const int lane = threadIdx.x & 63;
-    const uint32_t it = it_lo + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (it >= it_hi) return;
-    const uint32_t read = items[it];
-    if (D.hlen[read] < (uint32_t)D.k) return;
-    const uint64_t* __restrict__ rc = D.pool + D.pool_off[slot];
-    const uint32_t n = (uint32_t)(D.pool_off[slot + 1] - D.pool_off[slot]);
-    const uint32_t M = D.mzcnt[read];
-    const uint64_t base = D.mzoff[read];
-    unsigned long long* cell = (unsigned long long*)(cnt + (uint64_t)(it - row0) * stride + slot);
-    unsigned long long acc = 0;
-    for (uint32_t a = lane; a < M; a += 64) {
-        const uint64_t code = D.mzcode[base + a];
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rc[mid] < code) lo = mid + 1; else hi = mid; }
-        if (lo < n && rc[lo] == code) acc += (1ull << 48) + (unsigned long long)D.mzpos[base + a];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
-    if (lane == 0 && acc) *cell += acc;
-}
-
 // Can a representative that shares nm minimizers with `read` change the decision the read took WITHOUT it?  Only if the reference would ever look at it: get_best_cluster walks
 // the candidates by hit count and stops at the first one below min_shared or below min_fraction x top (cluster.py:82,88), the alignment stage only takes candidates AT the top count
 // (:181) - so a representative below that bound is never visited and, being below the top, does not move the top either.  D.top[read] is the top count over the committed
@@ -320,52 +295,13 @@ void k_first_affected(ClDev D, const uint32_t* __restrict__ items, uint32_t it_l
     if (__ballot(hit) != 0ull && lane == 0) atomicMin(out, it);
 }
 
-// sort + unique the minimizer codes of one read into the representative pool (single workgroup, bitonic in LDS);
-// also registers the slot: rep_read[slot] = read, pool_off[slot+1] = pool_off[slot] + #unique
-__global__ __launch_bounds__(256)
-void k_rep_build(const uint64_t* __restrict__ mzcode, uint64_t base, uint32_t M, uint32_t P2, uint64_t* __restrict__ pool, uint64_t* __restrict__ pool_off,
-                 uint32_t* __restrict__ rep_read, uint32_t slot, uint32_t read, uint32_t* __restrict__ out_count)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t* a = (uint64_t*)smem;
-    for (uint32_t i = threadIdx.x; i < P2; i += 256) a[i] = i < M ? mzcode[base + i] : ~0ull;
-    __syncthreads();
-    for (uint32_t k2 = 2; k2 <= P2; k2 <<= 1)
-        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < P2; i += 256) {
-                const uint32_t l = i ^ j;
-                if (l > i) { const uint64_t x = a[i], y = a[l]; const bool up = (i & k2) == 0; if ((x > y) == up) { a[i] = y; a[l] = x; } }
-            }
-            __syncthreads();
-        }
-    if (threadIdx.x == 0) {
-        uint64_t* dst = pool + pool_off[slot];
-        uint32_t c = 0; for (uint32_t i = 0; i < M; ++i) if (i == 0 || a[i] != a[i - 1]) dst[c++] = a[i];
-        pool_off[slot + 1] = pool_off[slot] + c; rep_read[slot] = read; *out_count = c;
-    }
-}
-
-__global__ void k_db_merge(const uint64_t* __restrict__ oc, const uint32_t* __restrict__ os, uint64_t n_old,
-                           const uint64_t* __restrict__ rc, uint32_t n_new, uint32_t slot, uint64_t* __restrict__ nc, uint32_t* __restrict__ ns)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_old) {
-        const uint64_t code = oc[i]; uint32_t lo = 0, hi = n_new;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (rc[mid] < code) lo = mid + 1; else hi = mid; }   // rep codes < old code
-        nc[i + lo] = code; ns[i + lo] = os[i];
-    } else if (i < n_old + n_new) {
-        const uint32_t j = (uint32_t)(i - n_old); const uint64_t code = rc[j]; uint64_t lo = 0, hi = n_old;
-        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (oc[mid] <= code) lo = mid + 1; else hi = mid; }  // old codes <= rep code
-        nc[j + lo] = code; ns[j + lo] = slot;
-    }
-}
-
-// ---- batched variants (up to 64 representatives per launch): one launch builds them, one counts the block against them, one merges them
+// ---- new representatives, up to 64 per launch: one launch builds them, one counts the block against them, one merges them
 struct RepBatch { uint32_t read[64]; uint32_t M[64]; uint64_t base[64]; };
 struct PosBatch { uint32_t pos[64]; };
 
 // workgroup t sorts + uniques the codes of read t (bitonic in LDS) and appends them to the pool behind workgroup t-1: the offsets are chained
-// through `chain` (zero before the launch; all <= 64 workgroups are resident, so waiting on the predecessor cannot deadlock)
+// through `chain` (zero before the launch; all <= 64 workgroups are resident, so waiting on the predecessor cannot deadlock).
+// Also registers the slot: rep_read[slot0 + t] = read t, pool_off[slot0 + t + 1] = pool_off[slot0 + t] + #unique
 __global__ __launch_bounds__(256)
 void k_rep_build_batch(const uint64_t* __restrict__ mzcode, RepBatch B, uint64_t* __restrict__ pool, uint64_t* __restrict__ pool_off,
                        uint32_t* __restrict__ rep_read, uint32_t slot0, uint32_t* __restrict__ chain)
@@ -427,7 +363,7 @@ void k_count_hits_reps(ClDev D, const uint32_t* __restrict__ items, uint32_t it_
 }
 
 // merges the sorted code lists of the c consecutive slots slot0 .. slot0+c-1 (contiguous in the pool) into the sorted index in one pass; the
-// result equals c successive k_db_merge calls: equal codes keep the order old entries, then ascending slot
+// result equals merging them one after the other: equal codes keep the order old entries, then ascending slot
 __global__ void k_db_merge_batch(const uint64_t* __restrict__ oc, const uint32_t* __restrict__ os, uint64_t n_old,
                                  const uint64_t* __restrict__ pool, const uint64_t* __restrict__ pool_off, uint32_t slot0, uint32_t c,
                                  uint64_t* __restrict__ nc, uint32_t* __restrict__ ns)
@@ -508,15 +444,12 @@ __global__ void k_finalize(ClDev D, uint64_t n, const uint8_t* __restrict__ seed
 // ------------------------------------------------------------------------------------------------ host driver
 namespace {
 struct RepStore {
-    ngsid_ctx* ctx; uint32_t R = 0, Rcap = 0;
+    uint32_t R = 0, Rcap = 0;
     DevBuf<uint32_t> rep_read; DevBuf<uint64_t> pool, pool_off; std::vector<uint64_t> h_pool_off;
     DevBuf<uint64_t> dbc[2]; DevBuf<uint32_t> dbs[2]; int cur = 0; uint64_t n_db = 0;
     DevBuf<uint32_t> d_count;
 };
-}
 
-// Builds the representatives of `reads` in the slots S.R, S.R+1, ... (pool offsets chained on the device) without registering them on the host:
-// the caller copies pool_off[S.R .. S.R+n] back and commits a prefix.  A slot that is not committed is simply overwritten by the next build.
 // Builds the representatives of `reads` in the slots S.R, S.R+1, ... (pool offsets chained on the device) without registering them on the host:
 // the caller copies pool_off[S.R .. S.R+n] back and commits a prefix.  A slot that is not committed is simply overwritten by the next build.
 static int32_t build_reps(ngsid_ctx* ctx, RepStore& S, const uint32_t* reads, uint32_t n, const uint64_t* d_mzcode, const uint64_t* h_off, const uint32_t* h_mzcnt)
@@ -561,6 +494,304 @@ static int32_t commit_reps(ngsid_ctx* ctx, RepStore& S, uint32_t c, const uint64
     return NGSID_OK;
 }
 
+// launch of a kernel that takes one wave per item, four items per workgroup (ny: grid rows, one per tentative representative)
+#define LAUNCH_WAVE_PER_ITEM(ctx, kern, n_items, ny, ...) \
+    do { hipLaunchKernelGGL(kern, dim3(((n_items) + 3) / 4, ny), dim3(256), 0, (ctx)->stream, __VA_ARGS__); HIPCHK(ctx, hipGetLastError()); } while (0)
+
+// ---- max tolerated run of non-shared minimizers per (e1,e2): largest g with p_err^g >= min_prob_no_hits,
+//      p_err^g by left-to-right repeated multiplication exactly like reduce(mul,[p]*g,1)  (cluster.py:97-105)
+static void max_gap_table(const ngsid_cluster_params_t* prm, int32_t out[225])
+{
+    for (int i = 0; i < 225; ++i) {
+        const double ps = prm->p_shared[i];
+        if (ps != ps) { out[i] = -2; continue; }
+        const double perr = 1.0 - ps; double pr = 1.0; int g = -1;
+        for (int t = 0; t < (1 << 20); ++t) { if (pr < prm->min_prob_no_hits) break; g = t; pr = pr * perr; }
+        out[i] = g;
+    }
+}
+
+constexpr uint32_t TMAX = 64;             // new representatives committed per pass (one lane per tentative column in k_first_affected)
+
+// One speculative block: the items [b0, b1) of the greedy order, of which [b0, lo) are final
+struct Block {
+    uint32_t b0, b1, lo;                      // lo: first uncommitted item
+    bool need_full = true;                    // the hit matrix of [lo, b1) has to be counted against the whole index
+    uint32_t rounds = 0, newreps = 0;         // restart rounds / new representatives of this block
+    uint64_t aln_first = 0, aln_total = 0; bool first_round = true;      // pairs aligned in the block's first alignment round / in all of them (round 6: the block size follows the share of RE-alignments)
+};
+
+// The three scheduling rules of the block loop (host only; results do not depend on them, tested)
+struct BlockPolicy {
+    // speculative block size: adaptive - blocks grow while new representatives are rare (bigger aligner launches, fewer round trips) and
+    // shrink when they are frequent (every new representative re-decides the rest of its block)
+    // capacity of the per-block buffers = the largest speculative block.  Round 6: 1 M items (262 144 until round 5) - while new representatives are rare a block costs nothing for being
+    // large, and every block ends in the tail of a persistent aligner launch (one work item = two pairs = ~2 ms of a wave): fewer, larger launches.  "cluster_block_cap" sets it (tests).
+    uint32_t BLK = 1u << 20;
+    uint32_t blk = 32768;
+    bool blk_fixed = false;
+    uint32_t trunc = 32768;                  // cap of a restarting block's rest (below); "cluster_trunc" sets it (0 = off) - tests use small values to cut blocks of small sets
+    uint32_t tcur = 1;                       // tentative representatives built by the next restart round
+    explicit BlockPolicy(const ngsid_ctx* ctx)
+    {
+        { const long v = (long)ngsid_opt(ctx, "cluster_block_cap", 0); if (v >= 8192 && v <= (1l << 22)) BLK = (uint32_t)v; }
+        { const long v = (long)ngsid_opt(ctx, "cluster_block", 0); if (v >= 64 && v <= (long)BLK) { blk = (uint32_t)v; blk_fixed = true; } }     // dev / test knob: the result must not depend on it
+        { const long v = (long)ngsid_opt(ctx, "cluster_trunc", -1); if (v >= 0) trunc = (uint32_t)std::min<long>(v, 1l << 22); }
+    }
+    void speculated(uint32_t c, uint32_t T) { tcur = c == T ? std::min<uint32_t>(TMAX, tcur * 2) : std::max<uint32_t>(1, c); }      // a restart round built T and committed c of them: speculate wider only while it pays
+    // Round 6: a block that keeps restarting is cut short.  Every restart round runs five kernels over the rest of the block (reset, decide, alignment cursor, mask, hit
+    // counts of the next tentative representatives), so its cost grows with that rest, and the NUMBER of rounds is given by the data (one per stretch between dependent
+    // new representatives) - the noisy tail of a score-ordered set brings thousands of them at once (mu = 14: 2 196 new representatives in the last 408 k reads, after
+    // 540 k reads with none, i.e. in a block that had grown to its largest size).  From the third round on the rest is capped at `trunc` items; the items behind the cut
+    // go back to "undecided" and are decided from scratch by the next block, which starts at that size.  Results do not depend on where blocks end (tested).
+    uint32_t cut_restarting(const Block& B)      // the block's new end (B.b1: no cut)
+    {
+        if (!(trunc && B.rounds >= 3 && B.b1 - B.lo > trunc)) return B.b1;
+        if (!blk_fixed) blk = std::max<uint32_t>(trunc, 8192);
+        return B.lo + trunc;
+    }
+    void next_block(const Block& B, uint32_t R, uint32_t stride)      // size of the block after B (R representatives, hit matrix of `stride` columns)
+    {
+        if (blk_fixed) return;
+        // blocks grow while new representatives are rare and shrink when they are frequent (every new representative re-decides part of the rest of its block)
+        const double waste = B.aln_first ? (double)(B.aln_total - B.aln_first) / (double)B.aln_first : (B.aln_total ? 1.0 : 0.0);
+        static const bool trace_blocks = getenv("NGSID_CLUSTER_TRACE") != nullptr;      // dev aid: one line per block on stderr
+        if (trace_blocks) fprintf(stderr, "[ngsid cluster] block ending at %u: %u restart rounds, %u new representatives (R = %u), pairs aligned in the first round %llu, later %llu (%.3f)\n", B.b1, B.rounds, B.newreps, R, (unsigned long long)B.aln_first, (unsigned long long)(B.aln_total - B.aln_first), waste);
+        // (a rule by restart ROUNDS instead of new representatives was measured in round 6 and lost: 0.45 against 0.41 s at mu = 14 - small blocks stay the better ones while
+        // representatives keep coming, whatever the number of rounds they take)
+        constexpr uint32_t SHRINK_REPS = 32, BLOCK_FLOOR = 4096;      // a block with more new representatives than SHRINK_REPS halves the next one, down to BLOCK_FLOOR items
+        if (B.newreps <= 2) blk = std::min<uint32_t>(blk * 2, BLK); else if (B.newreps > SHRINK_REPS) blk = std::max<uint32_t>(blk / 2, BLOCK_FLOOR);
+        // the hit matrix of a block is rows x (representatives + room) x 8 bytes: a noisy set with thousands of representatives keeps its blocks under 12 GB of it
+        const uint64_t cols = std::max<uint64_t>(stride, ((uint64_t)R + 256 + 63) / 64 * 64);
+        while (blk > 8192 && (uint64_t)blk * cols * 8 > ((uint64_t)12 << 30)) blk /= 2;
+    }
+};
+
+// What one call of ngsid_cluster_greedy owns: constructed once, destroyed once at the end of the call (the destructor of a DevBuf waits for the stream - none is
+// created or destroyed inside the block loop).  The members are declared in the order in which the call fills them.
+struct ClusterRun {
+    ngsid_ctx* ctx; uint64_t N = 0; uint32_t NI = 0; int k = 0;
+    DevReads RD;
+    DevBuf<uint32_t> d_acc; DevBuf<double> herr0, herr, rawerr, d_known; DevBuf<uint8_t> eidx; DevBuf<int> flag;
+    const uint32_t *h_hlen = nullptr, *h_mzcnt = nullptr, *h_items = nullptr;      // the thread's pinned host mirrors (prepare)
+    int32_t h_maxgap[225]; DevBuf<int32_t> d_maxgap;
+    std::vector<uint8_t> h_seeded; DevBuf<uint32_t> d_items; DevBuf<uint8_t> d_seeded;
+    DevBuf<int32_t> dec, top, cache_slot, cache_region; DevBuf<uint8_t> kind, alnflag, cache_ptr; DevBuf<uint64_t> cur_hi, cur_lo;      // per read state
+    RepStore S; std::vector<uint64_t> h_po;
+    ClDev D{};
+    DevBuf<uint64_t>& cnt; uint32_t stride = 0;      // (kept in the context: a block's matrix is up to a few GB, a fresh allocation of it costs 20+ ms)
+    DevBuf<uint32_t> req_q, req_t, req_slot, d_scal; DevBuf<int32_t> req_open, req_mid, req_region;
+    DevBuf<unsigned long long> d_mask; PinVec<unsigned long long> h_mask;
+    explicit ClusterRun(ngsid_ctx* c) : ctx(c), cnt(c->cl_cnt) {}
+    void refresh() { D.rep_read = S.rep_read.p; D.pool = S.pool.p; D.pool_off = S.pool_off.p; }      // the three pointers of D that move when S grows
+    // ---- per-read preprocessing (a1-a3), the max-gap table, the items to process and the per-read state
+    int32_t prepare(const ngsid_cluster_params_t* prm, const uint32_t* acc_rank, const int32_t* prev_batch, const double* known_err)
+    {
+        const int w = prm->w; int32_t rc;
+        DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen;      // the minimizers themselves go to the compact CSR of the context (12 bytes per minimizer, grow-only): ctx->pol_mzcode / pol_mzpos, offsets in ctx->mz_off / ctx->h_mzoff
+        ctx->mzc.valid = false;
+        HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N));
+        HIPCHK(ctx, herr0.alloc(N)); HIPCHK(ctx, herr.alloc(N)); HIPCHK(ctx, rawerr.alloc(N)); HIPCHK(ctx, eidx.alloc(N)); HIPCHK(ctx, flag.alloc(2)); HIPCHK(ctx, d_acc.alloc(N));
+        HIPCHK(ctx, hipMemsetAsync(flag.p, 0, 2 * sizeof(int), ctx->stream));
+        static thread_local PinVec<uint32_t> v_hlen, v_mzcnt;      // host mirrors are kept across calls (fresh multi-megabyte vectors page-fault on every call)
+        v_hlen.resize(N); v_mzcnt.resize(N); h_hlen = v_hlen.data(); h_mzcnt = v_mzcnt.data();
+        {
+            long long bad = -1;
+            rc = ngsid_minimizers_csr(ctx, RD, k, w, ngsid_ctx_mz(ctx), mzcnt.p, hlen.p, herr0.p, rawerr.p, v_mzcnt.data(), v_hlen.data(), &bad); if (rc) return rc;
+            if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "read %lld: base outside ACGTN", bad);
+        }
+        if (k <= 21 && N >= 1024) {       // key of the minimizer cache (the polisher's strand detection may be handed the same reads next); small sets are not worth the fingerprint
+            unsigned long long fp = 0; rc = ngsid_reads_fingerprint(ctx, RD, &fp); if (rc) return rc;
+            ctx->mzc.n = N; ctx->mzc.total = RD.total; ctx->mzc.k = k; ctx->mzc.w = w; ctx->mzc.fp = fp; ctx->mzc.valid = true;
+        }
+        if (known_err) { HIPCHK(ctx, d_known.alloc(N)); HIPCHK(ctx, hipMemcpyAsync(d_known.p, known_err, 8 * N, hipMemcpyHostToDevice, ctx->stream)); }
+        hipLaunchKernelGGL(k_eidx, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, herr0.p, known_err ? d_known.p : nullptr, N, herr.p, eidx.p);
+        HIPCHK(ctx, hipGetLastError());
+        if (acc_rank) HIPCHK(ctx, hipMemcpyAsync(d_acc.p, acc_rank, 4 * N, hipMemcpyHostToDevice, ctx->stream));
+        else { std::vector<uint32_t> id(N); for (uint64_t i = 0; i < N; ++i) id[i] = (uint32_t)i; HIPCHK(ctx, hipMemcpyAsync(d_acc.p, id.data(), 4 * N, hipMemcpyHostToDevice, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+
+        max_gap_table(prm, h_maxgap);
+        HIPCHK(ctx, d_maxgap.alloc(225));
+        HIPCHK(ctx, hipMemcpyAsync(d_maxgap.p, h_maxgap, 225 * 4, hipMemcpyHostToDevice, ctx->stream));
+
+        // ---- items (reads to process) and seeded representatives
+        int lowest = 1;
+        if (prev_batch) { int mn = prev_batch[0]; for (uint64_t i = 1; i < N; ++i) mn = std::min(mn, prev_batch[i]); lowest = std::max(1, mn); }
+        static thread_local PinVec<uint32_t> v_items; v_items.clear(); v_items.reserve(N);
+        if (prev_batch) { h_seeded.assign(N, 0); for (uint64_t i = 0; i < N; ++i) { if (prev_batch[i] == lowest) h_seeded[i] = 1; else v_items.push_back((uint32_t)i); } }
+        else for (uint64_t i = 0; i < N; ++i) v_items.push_back((uint32_t)i);
+        NI = (uint32_t)v_items.size(); h_items = v_items.data();
+        HIPCHK(ctx, d_items.alloc(NI)); if (NI) HIPCHK(ctx, hipMemcpyAsync(d_items.p, v_items.data(), 4ull * NI, hipMemcpyHostToDevice, ctx->stream));
+        if (prev_batch) { HIPCHK(ctx, d_seeded.alloc(N)); HIPCHK(ctx, hipMemcpyAsync(d_seeded.p, h_seeded.data(), N, hipMemcpyHostToDevice, ctx->stream)); }
+
+        // ---- state
+        HIPCHK(ctx, dec.alloc(N)); HIPCHK(ctx, top.alloc(N)); HIPCHK(ctx, cache_slot.alloc(N * NCACHE)); HIPCHK(ctx, cache_region.alloc(N * NCACHE));
+        HIPCHK(ctx, kind.alloc(N)); HIPCHK(ctx, alnflag.alloc(N)); HIPCHK(ctx, cache_ptr.alloc(N)); HIPCHK(ctx, cur_hi.alloc(N)); HIPCHK(ctx, cur_lo.alloc(N));
+        HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)dec.p, (int)DEC_UNDEC, N, ctx->stream));      // undecided: k_decide_map takes every item with this value
+        HIPCHK(ctx, hipMemsetAsync(cache_slot.p, 0xff, 4 * N * NCACHE, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(cache_ptr.p, 0, N, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(alnflag.p, 0, N, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(kind.p, 0, N, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(top.p, 0, 4 * N, ctx->stream));            // (read by rep_can_matter for reads that never reached k_decide_map's top pass: short reads)
+        return NGSID_OK;
+    }
+    // ---- the empty representative store and, in a merge round, the seeded representatives
+    int32_t seed_representatives(bool seeded)
+    {
+        S.h_pool_off.push_back(0);
+        HIPCHK(ctx, S.d_count.alloc(4)); HIPCHK(ctx, S.rep_read.alloc(1024)); HIPCHK(ctx, S.pool_off.alloc(1025)); S.Rcap = 1024;
+        HIPCHK(ctx, hipMemsetAsync(S.pool_off.p, 0, 8, ctx->stream));
+        HIPCHK(ctx, S.pool.alloc(1 << 16)); HIPCHK(ctx, S.dbc[0].alloc(1 << 16)); HIPCHK(ctx, S.dbs[0].alloc(1 << 16)); HIPCHK(ctx, S.dbc[1].alloc(1 << 16)); HIPCHK(ctx, S.dbs[1].alloc(1 << 16));
+        if (seeded) {       // the seeded representatives, built in chunks (one host round trip per chunk)
+            std::vector<uint32_t> seeds;
+            for (uint64_t i = 0; i < N; ++i) if (h_seeded[i] && h_hlen[i] >= (uint32_t)k) seeds.push_back((uint32_t)i);
+            for (size_t s0 = 0; s0 < seeds.size(); s0 += 512) {
+                const uint32_t nch = (uint32_t)std::min<size_t>(512, seeds.size() - s0);
+                int32_t rc = build_reps(ctx, S, seeds.data() + s0, nch, ctx->pol_mzcode.p, ctx->h_mzoff.data(), h_mzcnt); if (rc) return rc;
+                h_po.resize(nch + 1);
+                HIPCHK(ctx, hipMemcpyAsync(h_po.data(), S.pool_off.p + S.R, 8ull * (nch + 1), hipMemcpyDeviceToHost, ctx->stream));
+                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+                rc = commit_reps(ctx, S, nch, h_po.data()); if (rc) return rc;
+            }
+        }
+        return NGSID_OK;
+    }
+    // ---- the kernels' view of the run and the buffers sized by the largest block (BLK items): alignment requests, the new-representative mask
+    int32_t alloc_block_buffers(const ngsid_cluster_params_t* prm, uint32_t BLK)
+    {
+        D.seq = RD.seq; D.qual = RD.qual; D.off = RD.off; D.n = N; D.hlen = ctx->mzc_hlen.p; D.mzcnt = ctx->mzc_cnt.p; D.herr = herr.p; D.rawerr = rawerr.p; D.eidx = eidx.p; D.accrank = d_acc.p;
+        D.mzcode = ctx->pol_mzcode.p; D.mzpos = ctx->pol_mzpos.p; D.mzoff = ctx->mz_off.p; D.maxgap = d_maxgap.p; D.k = k; D.min_shared = prm->min_shared; D.symmetric = prm->symmetric;
+        D.min_fraction = prm->min_fraction; D.mapped_threshold = prm->mapped_threshold; D.aligned_threshold = prm->aligned_threshold;
+        D.dec = dec.p; D.kind = kind.p; D.alnflag = alnflag.p; D.top = top.p; D.cur_hi = cur_hi.p; D.cur_lo = cur_lo.p;
+        D.cache_slot = cache_slot.p; D.cache_region = cache_region.p; D.cache_ptr = cache_ptr.p; D.errflag = flag.p + 1;
+        HIPCHK(ctx, req_q.alloc(BLK)); HIPCHK(ctx, req_t.alloc(BLK)); HIPCHK(ctx, req_slot.alloc(BLK)); HIPCHK(ctx, req_open.alloc(BLK)); HIPCHK(ctx, req_mid.alloc(BLK)); HIPCHK(ctx, req_region.alloc(BLK));
+        HIPCHK(ctx, d_scal.alloc(4)); HIPCHK(ctx, hipMemsetAsync(d_scal.p, 0, 16, ctx->stream));
+        HIPCHK(ctx, d_mask.alloc(BLK / 64 + 1)); h_mask.resize(BLK / 64 + 1);
+        return NGSID_OK;
+    }
+    // ---- hit matrix for items [lo,b1) against the whole index; stride leaves room for new representatives
+    int32_t count_block(Block& B)
+    {
+        const uint32_t want = ((S.R + 256 + 63) / 64) * 64;
+        // rows = the items of THIS block (blocks shrink when representatives are frequent, so rows x columns stays moderate: a noisy read
+        // set with 50 k representatives would otherwise ask for BLK x 50 k x 8 B = 100 GB)
+        stride = std::max(stride, want);
+        { const uint64_t need = (uint64_t)(B.b1 - B.b0) * stride; if (!cnt.p || cnt.cap < need) HIPCHK(ctx, cnt.alloc(need + need / 4)); }
+        HIPCHK(ctx, hipMemsetAsync(cnt.p, 0, 8ull * (uint64_t)(B.b1 - B.b0) * stride, ctx->stream));
+        { ProfScope ps_(ctx, "k_count_hits"); LAUNCH_WAVE_PER_ITEM(ctx, k_count_hits, B.b1 - B.lo, 1, D, d_items.p, B.lo, B.b1, B.b0, S.dbc[S.cur].p, S.dbs[S.cur].p, S.n_db, cnt.p, stride); }
+        B.need_full = false;
+        return NGSID_OK;
+    }
+    // ---- alignment rounds over the items [lo,b1): resolve from cache or request pairs, align, cache, repeat  (d_scal[0] is zero here: set at the start, reset by k_newrep_mask).
+    // Leaves the new-representative mask of [lo,b1) in h_mask; one host round trip per round.
+    int32_t align_rounds(Block& B)
+    {
+        const uint32_t b0 = B.b0, lo = B.lo, b1 = B.b1;
+        const uint32_t w0 = (lo - b0) >> 6, w1 = (b1 - b0 + 63) >> 6;
+        int eflag = 0;
+        for (;;) {
+            { ProfScope ps_(ctx, "k_aln_next"); hipLaunchKernelGGL(k_aln_next, dim3((b1 - lo + 15) / 16), dim3(1024), 0, ctx->stream, D, d_items.p, lo, b1, b0, cnt.p, stride, S.R,
+                               req_q.p, req_t.p, req_slot.p, req_open.p, req_mid.p, d_scal.p); }
+            HIPCHK(ctx, hipGetLastError());
+            // the new-representative mask of the block is computed and fetched in the SAME round trip as the request count: when no pair is requested every item
+            // of [lo, b1) is decided and the mask is the one the next step needs (most rounds of a noisy tail; one host round trip less per round); when pairs are
+            // requested it is recomputed after the alignments
+            uint32_t nreq = 0;
+            hipLaunchKernelGGL(k_newrep_mask, dim3(((w1 - w0) * 64 + 255) / 256), dim3(256), 0, ctx->stream, dec.p, d_items.p, b0 + w0 * 64, lo, b1, b0, d_mask.p, w1, d_scal.p, flag.p + 1);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(h_mask.data() + w0, d_mask.p + w0, 8ull * (w1 - w0 + 1), hipMemcpyDeviceToHost, ctx->stream));      // mask words + the tail word (nreq | eflag << 32)
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+            nreq = (uint32_t)(h_mask[w1] & 0xffffffffull); eflag = (int)(h_mask[w1] >> 32);
+            if (!nreq) break;
+            B.aln_total += nreq; if (B.first_round) B.aln_first += nreq;
+            AlignJob J{};
+            J.qseq = RD.seq; J.qoff = RD.off; J.tseq = RD.seq; J.toff = RD.off; J.qidx = req_q.p; J.tidx = req_t.p; J.npairs = nreq;
+            J.match = 2; J.mismatch = -2; J.ext = 1; J.k = k; J.open = req_open.p; J.match_id = req_mid.p;     // cluster.py:130
+            J.region = req_region.p; J.window = 1;
+            const int32_t rc = ngsid_launch_align(ctx, J, RD.maxlen, RD.maxlen, 5, RD.minlen); if (rc) return rc;     // gap open is 2..5 (cluster.py:189-196)
+            hipLaunchKernelGGL(k_cache_insert, dim3((nreq + 255) / 256), dim3(256), 0, ctx->stream, D, req_q.p, req_slot.p, req_region.p, nreq);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        B.first_round = false;
+        if (eflag) NGSID_FAIL(ctx, NGSID_ERR_NO_PTABLE, "no p_shared entry for an (e1,e2) pair met during mapping (KeyError in cluster.py:367)");
+        return NGSID_OK;
+    }
+    // ---- one speculation step on the mask align_rounds left: the first items of [lo,b1) that decided "new representative" become representatives, B.lo moves to the
+    // first item that has to be decided again (B.b1: none, the block is done).  One host round trip.
+    int32_t commit_speculative(BlockPolicy& P, Block& B)
+    {
+        const uint32_t b0 = B.b0, b1 = B.b1;
+        const uint32_t w0 = (B.lo - b0) >> 6, w1 = (b1 - b0 + 63) >> 6;
+        // ---- the items that decided "new representative", in block order (bit mask of the block, fetched with the last request count, scanned on the host)
+        uint32_t C[TMAX + 1]; uint32_t nC = 0;
+        for (uint32_t wd = w0; wd < w1 && nC <= TMAX; ++wd) {
+            unsigned long long m = h_mask[wd];
+            while (m && nC <= TMAX) { C[nC++] = b0 + wd * 64 + (uint32_t)__builtin_ctzll(m); m &= m - 1; }
+        }
+        if (nC == 0) { B.lo = b1; return NGSID_OK; }
+        // ---- up to TMAX of them become representatives at once.  All are built (slots R, R+1, ...) and the later items are counted against
+        // each; everything before the first item that shares >= min_shared minimizers with an EARLIER tentative representative is final
+        // (such an item is the only kind whose decision can change), the tentative representatives before that item are committed, the
+        // rest of the block is decided again.  With one new representative per pass this is the plain greedy restart.
+        const uint32_t T = std::min<uint32_t>(std::min<uint32_t>(P.tcur, nC), stride - S.R);
+        const uint32_t next_c = nC > T ? C[T] : 0xffffffffu;
+        uint32_t creads[TMAX];
+        for (uint32_t t = 0; t < T; ++t) creads[t] = h_items[C[t]];
+        int32_t rc = build_reps(ctx, S, creads, T, ctx->pol_mzcode.p, ctx->h_mzoff.data(), h_mzcnt); if (rc) return rc;
+        refresh();
+        if (C[0] + 1 < b1) {
+            PosBatch PB; for (uint32_t t = 0; t < 64; ++t) PB.pos[t] = t < T ? C[t] : 0xffffffffu;
+            ProfScope ps_(ctx, "k_count_hits");
+            LAUNCH_WAVE_PER_ITEM(ctx, k_count_hits_reps, b1 - C[0] - 1, T, D, d_items.p, C[0] + 1, b1, b0, S.R, PB, cnt.p, stride);
+        }
+        uint32_t cut = 0xffffffffu;
+        HIPCHK(ctx, hipMemsetAsync(d_scal.p + 1, 0xff, 4, ctx->stream));
+        if (C[0] + 1 < b1) LAUNCH_WAVE_PER_ITEM(ctx, k_first_affected, b1 - C[0] - 1, 1, D, d_items.p, C[0] + 1, b1, b0, cnt.p, stride, S.R, T, d_scal.p + 1);
+        h_po.resize(T + 1);
+        HIPCHK(ctx, hipMemcpyAsync(&cut, d_scal.p + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_po.data(), S.pool_off.p + S.R, 8ull * (T + 1), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        cut = std::min(cut, next_c);
+        uint32_t c = 0; while (c < T && C[c] < cut) ++c;                 // >= 1: the affected item lies behind C[0]
+        const uint32_t R_before = S.R;
+        rc = commit_reps(ctx, S, c, h_po.data()); if (rc) return rc;
+        B.newreps += c;
+        P.speculated(c, T);
+        if (cut >= b1) { B.lo = b1; return NGSID_OK; }
+        B.lo = cut;
+        // the columns of the tentative representatives that were not committed go back to zero (their entries sit in rows >= cut)
+        if (c < T) HIPCHK(ctx, hipMemset2DAsync(cnt.p + (uint64_t)(B.lo - b0) * stride + S.R, (size_t)stride * 8, 0, (size_t)(T - c) * 8, b1 - B.lo, ctx->stream));
+        refresh();
+        if (S.R + 1 > stride) B.need_full = true;
+        hipLaunchKernelGGL(k_reset_items, dim3((b1 - B.lo + 255) / 256), dim3(256), 0, ctx->stream, D, d_items.p, B.lo, b1, b0, cnt.p, stride, R_before, c);
+        HIPCHK(ctx, hipGetLastError());
+        return NGSID_OK;
+    }
+    // ---- results
+    int32_t finalize(HostTimer& ht, bool seeded, int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4])
+    {
+        DevBuf<int32_t> d_rep; DevBuf<uint8_t> d_status; DevBuf<double> d_herr_out; DevBuf<unsigned long long> d_counters;
+        HIPCHK(ctx, d_rep.alloc(N)); HIPCHK(ctx, d_status.alloc(N)); HIPCHK(ctx, d_herr_out.alloc(N)); HIPCHK(ctx, d_counters.alloc(4));
+        HIPCHK(ctx, hipMemsetAsync(d_counters.p, 0, 32, ctx->stream));
+        refresh();
+        hipLaunchKernelGGL(k_finalize, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, D, N, seeded ? d_seeded.p : nullptr, d_rep.p, d_status.p, d_herr_out.p, d_counters.p);
+        HIPCHK(ctx, hipGetLastError());
+        static thread_local PinVec<uint8_t> h_status; static thread_local PinVec<double> h_herr; static thread_local PinVec<int32_t> h_rep; h_status.resize(N); h_herr.resize(N); h_rep.resize(N); unsigned long long h_cnt[4];
+        HIPCHK(ctx, hipMemcpyAsync(h_rep.data(), d_rep.p, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_status.data(), d_status.p, N, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_herr.data(), d_herr_out.p, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_cnt, d_counters.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        ht.mark("finalize + download");
+        memcpy(rep_of_read, h_rep.data(), 4 * N);
+        if (status_out) memcpy(status_out, h_status.data(), N);
+        if (hpc_err_out) memcpy(hpc_err_out, h_herr.data(), 8 * N);
+        if (counters) for (int i = 0; i < 4; ++i) counters[i] = h_cnt[i];
+        return NGSID_OK;
+    }
+};
+}
+
 extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_cluster_params_t* prm,
                                         const uint32_t* acc_rank, const int32_t* prev_batch, const double* known_err,
                                         int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4])
@@ -571,262 +802,40 @@ extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* rea
     const int k = prm->k, w = prm->w;
     if (k < 1 || k > NGSID_MAX_K || w < k) NGSID_FAIL(ctx, NGSID_ERR_ARG, "bad k/w (k=%d, w=%d; k <= %d)", k, w, NGSID_MAX_K);
     HostTimer ht(ctx->stream, "cluster");
-    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, true); if (rc) return rc;
+    ClusterRun run(ctx);
+    int32_t rc = ngsid_upload_reads(ctx, reads, &run.RD, true); if (rc) return rc;
     ht.mark("upload");
-    const uint64_t N = RD.n;
+    run.N = run.RD.n; run.k = k;
     if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
-    if (N == 0) return NGSID_OK;
-    if (N > 0x7fffffffull) NGSID_FAIL(ctx, NGSID_ERR_ARG, "too many reads");
+    if (run.N == 0) return NGSID_OK;
+    if (run.N > 0x7fffffffull) NGSID_FAIL(ctx, NGSID_ERR_ARG, "too many reads");
     if (!g_cl_tables[ctx->device & 15]) { HIPCHK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_round2_t), NGSID_ROUND2_T, sizeof(double) * 15)); g_cl_tables[ctx->device & 15] = true; }
 
-    // ---- per-read preprocessing (a1-a3)
-    DevBuf<uint64_t>& mzcode = ctx->pol_mzcode; DevBuf<uint32_t>& mzpos = ctx->pol_mzpos;      // compact CSR of the context (12 bytes per minimizer, grow-only), offsets in ctx->mz_off / ctx->h_mzoff
-    DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen; DevBuf<uint32_t> d_acc; DevBuf<double> herr0, herr, rawerr, d_known; DevBuf<uint8_t> eidx; DevBuf<int> flag;
-    ctx->mzc.valid = false;
-    HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N));
-    HIPCHK(ctx, herr0.alloc(N)); HIPCHK(ctx, herr.alloc(N)); HIPCHK(ctx, rawerr.alloc(N)); HIPCHK(ctx, eidx.alloc(N)); HIPCHK(ctx, flag.alloc(2)); HIPCHK(ctx, d_acc.alloc(N));
-    HIPCHK(ctx, hipMemsetAsync(flag.p, 0, 2 * sizeof(int), ctx->stream));
-    static thread_local PinVec<uint32_t> h_hlen, h_mzcnt;      // host mirrors are kept across calls (fresh multi-megabyte vectors page-fault on every call)
-    h_hlen.resize(N); h_mzcnt.resize(N);
-    {
-        long long bad = -1;
-        rc = ngsid_minimizers_csr(ctx, RD, k, w, ngsid_ctx_mz(ctx), mzcnt.p, hlen.p, herr0.p, rawerr.p, h_mzcnt.data(), h_hlen.data(), &bad); if (rc) return rc;
-        if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "read %lld: base outside ACGTN", bad);
-    }
-    if (k <= 21 && N >= 1024) {       // key of the minimizer cache (the polisher's strand detection may be handed the same reads next); small sets are not worth the fingerprint
-        unsigned long long fp = 0; rc = ngsid_reads_fingerprint(ctx, RD, &fp); if (rc) return rc;
-        ctx->mzc.n = N; ctx->mzc.total = RD.total; ctx->mzc.k = k; ctx->mzc.w = w; ctx->mzc.fp = fp; ctx->mzc.valid = true;
-    }
-    if (known_err) { HIPCHK(ctx, d_known.alloc(N)); HIPCHK(ctx, hipMemcpyAsync(d_known.p, known_err, 8 * N, hipMemcpyHostToDevice, ctx->stream)); }
-    hipLaunchKernelGGL(k_eidx, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, herr0.p, known_err ? d_known.p : nullptr, N, herr.p, eidx.p);
-    HIPCHK(ctx, hipGetLastError());
-    if (acc_rank) HIPCHK(ctx, hipMemcpyAsync(d_acc.p, acc_rank, 4 * N, hipMemcpyHostToDevice, ctx->stream));
-    else { std::vector<uint32_t> id(N); for (uint64_t i = 0; i < N; ++i) id[i] = (uint32_t)i; HIPCHK(ctx, hipMemcpyAsync(d_acc.p, id.data(), 4 * N, hipMemcpyHostToDevice, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
-
-    // ---- max tolerated run of non-shared minimizers per (e1,e2): largest g with p_err^g >= min_prob_no_hits,
-    //      p_err^g by left-to-right repeated multiplication exactly like reduce(mul,[p]*g,1)  (cluster.py:97-105)
-    std::vector<int32_t> h_maxgap(225);
-    for (int i = 0; i < 225; ++i) {
-        const double ps = prm->p_shared[i];
-        if (ps != ps) { h_maxgap[i] = -2; continue; }
-        const double perr = 1.0 - ps; double pr = 1.0; int g = -1;
-        for (int t = 0; t < (1 << 20); ++t) { if (pr < prm->min_prob_no_hits) break; g = t; pr = pr * perr; }
-        h_maxgap[i] = g;
-    }
-    DevBuf<int32_t> d_maxgap; HIPCHK(ctx, d_maxgap.alloc(225));
-    HIPCHK(ctx, hipMemcpyAsync(d_maxgap.p, h_maxgap.data(), 225 * 4, hipMemcpyHostToDevice, ctx->stream));
-
-    // ---- items (reads to process) and seeded representatives
-    int lowest = 1;
-    if (prev_batch) { int mn = prev_batch[0]; for (uint64_t i = 1; i < N; ++i) mn = std::min(mn, prev_batch[i]); lowest = std::max(1, mn); }
-    static thread_local PinVec<uint32_t> h_items; h_items.clear(); h_items.reserve(N);
-    std::vector<uint8_t> h_seeded;
-    if (prev_batch) { h_seeded.assign(N, 0); for (uint64_t i = 0; i < N; ++i) { if (prev_batch[i] == lowest) h_seeded[i] = 1; else h_items.push_back((uint32_t)i); } }
-    else for (uint64_t i = 0; i < N; ++i) h_items.push_back((uint32_t)i);
-    const uint32_t NI = (uint32_t)h_items.size();
-    DevBuf<uint32_t> d_items; DevBuf<uint8_t> d_seeded;
-    HIPCHK(ctx, d_items.alloc(NI)); if (NI) HIPCHK(ctx, hipMemcpyAsync(d_items.p, h_items.data(), 4ull * NI, hipMemcpyHostToDevice, ctx->stream));
-    if (prev_batch) { HIPCHK(ctx, d_seeded.alloc(N)); HIPCHK(ctx, hipMemcpyAsync(d_seeded.p, h_seeded.data(), N, hipMemcpyHostToDevice, ctx->stream)); }
-
-    // ---- state
-    DevBuf<int32_t> dec, top, cache_slot, cache_region; DevBuf<uint8_t> kind, alnflag, cache_ptr; DevBuf<uint64_t> cur_hi, cur_lo;
-    HIPCHK(ctx, dec.alloc(N)); HIPCHK(ctx, top.alloc(N)); HIPCHK(ctx, cache_slot.alloc(N * NCACHE)); HIPCHK(ctx, cache_region.alloc(N * NCACHE));
-    HIPCHK(ctx, kind.alloc(N)); HIPCHK(ctx, alnflag.alloc(N)); HIPCHK(ctx, cache_ptr.alloc(N)); HIPCHK(ctx, cur_hi.alloc(N)); HIPCHK(ctx, cur_lo.alloc(N));
-    HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)dec.p, (int)DEC_UNDEC, N, ctx->stream));      // undecided: k_decide_map takes every item with this value
-    HIPCHK(ctx, hipMemsetAsync(cache_slot.p, 0xff, 4 * N * NCACHE, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(cache_ptr.p, 0, N, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(alnflag.p, 0, N, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(kind.p, 0, N, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(top.p, 0, 4 * N, ctx->stream));            // (read by rep_can_matter for reads that never reached k_decide_map's top pass: short reads)
-
-    RepStore S; S.ctx = ctx; S.h_pool_off.push_back(0);
-    HIPCHK(ctx, S.d_count.alloc(4)); HIPCHK(ctx, S.rep_read.alloc(1024)); HIPCHK(ctx, S.pool_off.alloc(1025)); S.Rcap = 1024;
-    HIPCHK(ctx, hipMemsetAsync(S.pool_off.p, 0, 8, ctx->stream));
-    HIPCHK(ctx, S.pool.alloc(1 << 16)); HIPCHK(ctx, S.dbc[0].alloc(1 << 16)); HIPCHK(ctx, S.dbs[0].alloc(1 << 16)); HIPCHK(ctx, S.dbc[1].alloc(1 << 16)); HIPCHK(ctx, S.dbs[1].alloc(1 << 16));
-    std::vector<uint64_t> h_po;
-    if (prev_batch) {       // the seeded representatives, built in chunks (one host round trip per chunk)
-        std::vector<uint32_t> seeds;
-        for (uint64_t i = 0; i < N; ++i) if (h_seeded[i] && h_hlen[i] >= (uint32_t)k) seeds.push_back((uint32_t)i);
-        for (size_t s0 = 0; s0 < seeds.size(); s0 += 512) {
-            const uint32_t nch = (uint32_t)std::min<size_t>(512, seeds.size() - s0);
-            rc = build_reps(ctx, S, seeds.data() + s0, nch, mzcode.p, ctx->h_mzoff.data(), h_mzcnt.data()); if (rc) return rc;
-            h_po.resize(nch + 1);
-            HIPCHK(ctx, hipMemcpyAsync(h_po.data(), S.pool_off.p + S.R, 8ull * (nch + 1), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            rc = commit_reps(ctx, S, nch, h_po.data()); if (rc) return rc;
-        }
-    }
-
-    ClDev D{};
-    D.seq = RD.seq; D.qual = RD.qual; D.off = RD.off; D.n = N; D.hlen = hlen.p; D.mzcnt = mzcnt.p; D.herr = herr.p; D.rawerr = rawerr.p; D.eidx = eidx.p; D.accrank = d_acc.p;
-    D.mzcode = mzcode.p; D.mzpos = mzpos.p; D.mzoff = ctx->mz_off.p; D.maxgap = d_maxgap.p; D.k = k; D.min_shared = prm->min_shared; D.symmetric = prm->symmetric;
-    D.min_fraction = prm->min_fraction; D.mapped_threshold = prm->mapped_threshold; D.aligned_threshold = prm->aligned_threshold;
-    D.dec = dec.p; D.kind = kind.p; D.alnflag = alnflag.p; D.top = top.p; D.cur_hi = cur_hi.p; D.cur_lo = cur_lo.p;
-    D.cache_slot = cache_slot.p; D.cache_region = cache_region.p; D.cache_ptr = cache_ptr.p; D.errflag = flag.p + 1;
-
-    // speculative block size: adaptive - blocks grow while new representatives are rare (bigger aligner launches, fewer round trips) and
-    // shrink when they are frequent (every new representative re-decides the rest of its block)
-    // capacity of the per-block buffers = the largest speculative block.  Round 6: 1 M items (262 144 until round 5) - while new representatives are rare a block costs nothing for being
-    // large, and every block ends in the tail of a persistent aligner launch (one work item = two pairs = ~2 ms of a wave): fewer, larger launches.  "cluster_block_cap" sets it (tests).
-    uint32_t BLK = 1u << 20;
-    { const long v = (long)ngsid_opt(ctx, "cluster_block_cap", 0); if (v >= 8192 && v <= (1l << 22)) BLK = (uint32_t)v; }
-    uint32_t blk = 32768;
-    bool blk_fixed = false;
-    { const long v = (long)ngsid_opt(ctx, "cluster_block", 0); if (v >= 64 && v <= (long)BLK) { blk = (uint32_t)v; blk_fixed = true; } }     // dev / test knob: the result must not depend on it
-    uint32_t trunc = 32768;                  // cap of a restarting block's rest (below); "cluster_trunc" sets it (0 = off) - tests use small values to cut blocks of small sets
-    { const long v = (long)ngsid_opt(ctx, "cluster_trunc", -1); if (v >= 0) trunc = (uint32_t)std::min<long>(v, 1l << 22); }
-    DevBuf<uint64_t>& cnt = ctx->cl_cnt; uint32_t stride = 0;      // (kept in the context: a block's matrix is up to a few GB, a fresh allocation of it costs 20+ ms)
-    DevBuf<uint32_t> req_q, req_t, req_slot, d_scal; DevBuf<int32_t> req_open, req_mid, req_region;
-    HIPCHK(ctx, req_q.alloc(BLK)); HIPCHK(ctx, req_t.alloc(BLK)); HIPCHK(ctx, req_slot.alloc(BLK)); HIPCHK(ctx, req_open.alloc(BLK)); HIPCHK(ctx, req_mid.alloc(BLK)); HIPCHK(ctx, req_region.alloc(BLK));
-    HIPCHK(ctx, d_scal.alloc(4)); HIPCHK(ctx, hipMemsetAsync(d_scal.p, 0, 16, ctx->stream));
-    uint32_t tcur = 1;
-    constexpr uint32_t TMAX = 64;             // new representatives committed per pass (one lane per tentative column in k_first_affected)
-    DevBuf<unsigned long long> d_mask; HIPCHK(ctx, d_mask.alloc(BLK / 64 + 1)); PinVec<unsigned long long> h_mask(BLK / 64 + 1);
-    auto refresh = [&]() { D.rep_read = S.rep_read.p; D.pool = S.pool.p; D.pool_off = S.pool_off.p; };
-
+    rc = run.prepare(prm, acc_rank, prev_batch, known_err); if (rc) return rc;
+    rc = run.seed_representatives(prev_batch != nullptr); if (rc) return rc;
+    BlockPolicy policy(ctx);
+    rc = run.alloc_block_buffers(prm, policy.BLK); if (rc) return rc;
     ht.mark("setup");
-    for (uint32_t b0 = 0; b0 < NI; ) {
-        uint32_t b1 = std::min<uint32_t>(NI, b0 + blk);
-        uint32_t rounds = 0;                      // restart rounds of this block
-        uint32_t lo = b0;                         // first uncommitted item
-        uint32_t newreps = 0;
-        uint64_t aln_first = 0, aln_total = 0; bool first_round = true;      // pairs aligned in the block's first alignment round / in all of them (round 6: the block size follows the share of RE-alignments)
-        bool need_full = true;
-        while (lo < b1) {
-            refresh();
-            if (need_full) {
-                // hit matrix for items [lo,b1) against the whole index; stride leaves room for new representatives
-                const uint32_t want = ((S.R + 256 + 63) / 64) * 64;
-                // rows = the items of THIS block (blocks shrink when representatives are frequent, so rows x columns stays moderate: a noisy read
-                // set with 50 k representatives would otherwise ask for BLK x 50 k x 8 B = 100 GB)
-                stride = std::max(stride, want);
-                { const uint64_t need = (uint64_t)(b1 - b0) * stride; if (!cnt.p || cnt.cap < need) HIPCHK(ctx, cnt.alloc(need + need / 4)); }
-                HIPCHK(ctx, hipMemsetAsync(cnt.p, 0, 8ull * (uint64_t)(b1 - b0) * stride, ctx->stream));
-                { ProfScope ps_(ctx, "k_count_hits"); hipLaunchKernelGGL(k_count_hits, dim3((b1 - lo + 3) / 4), dim3(256), 0, ctx->stream, D, d_items.p, lo, b1, b0,
-                                   S.dbc[S.cur].p, S.dbs[S.cur].p, 0u, S.n_db, cnt.p, stride); }
+    for (uint32_t b0 = 0; b0 < run.NI; ) {
+        Block B; B.b0 = B.lo = b0; B.b1 = std::min<uint32_t>(run.NI, b0 + policy.blk);
+        while (B.lo < B.b1) {
+            run.refresh();
+            if (B.need_full) { rc = run.count_block(B); if (rc) return rc; }
+            { ProfScope ps_(ctx, "k_decide_map"); LAUNCH_WAVE_PER_ITEM(ctx, k_decide_map, B.b1 - B.lo, 1, run.D, run.d_items.p, B.lo, B.b1, B.b0, run.cnt.p, run.stride, run.S.R); }
+            rc = run.align_rounds(B); if (rc) return rc;
+            rc = run.commit_speculative(policy, B); if (rc) return rc;
+            if (B.lo >= B.b1) break;      // nothing left to decide again: not a restart
+            ++B.rounds;
+            const uint32_t nb1 = policy.cut_restarting(B);
+            if (nb1 < B.b1) {
+                hipLaunchKernelGGL(k_undecide, dim3((B.b1 - nb1 + 255) / 256), dim3(256), 0, ctx->stream, run.D, run.d_items.p, nb1, B.b1);
                 HIPCHK(ctx, hipGetLastError());
-                need_full = false;
-            }
-            { ProfScope ps_(ctx, "k_decide_map"); hipLaunchKernelGGL(k_decide_map, dim3((b1 - lo + 3) / 4), dim3(256), 0, ctx->stream, D, d_items.p, lo, b1, b0, cnt.p, stride, S.R); }
-            HIPCHK(ctx, hipGetLastError());
-            const uint32_t w0 = (lo - b0) >> 6, w1 = (b1 - b0 + 63) >> 6;
-            int eflag = 0;
-            for (;;) {      // alignment rounds: resolve from cache or request pairs, align, cache, repeat  (d_scal[0] is zero here: set at the start, reset by k_newrep_mask)
-                { ProfScope ps_(ctx, "k_aln_next"); hipLaunchKernelGGL(k_aln_next, dim3((b1 - lo + 15) / 16), dim3(1024), 0, ctx->stream, D, d_items.p, lo, b1, b0, cnt.p, stride, S.R,
-                                   req_q.p, req_t.p, req_slot.p, req_open.p, req_mid.p, d_scal.p); }
-                HIPCHK(ctx, hipGetLastError());
-                // the new-representative mask of the block is computed and fetched in the SAME round trip as the request count: when no pair is requested every item
-                // of [lo, b1) is decided and the mask is the one the next step needs (most rounds of a noisy tail; one host round trip less per round); when pairs are
-                // requested it is recomputed after the alignments
-                uint32_t nreq = 0;
-                hipLaunchKernelGGL(k_newrep_mask, dim3(((w1 - w0) * 64 + 255) / 256), dim3(256), 0, ctx->stream, dec.p, d_items.p, b0 + w0 * 64, lo, b1, b0, d_mask.p, w1, d_scal.p, flag.p + 1);
-                HIPCHK(ctx, hipGetLastError());
-                HIPCHK(ctx, hipMemcpyAsync(h_mask.data() + w0, d_mask.p + w0, 8ull * (w1 - w0 + 1), hipMemcpyDeviceToHost, ctx->stream));      // mask words + the tail word (nreq | eflag << 32)
-                HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-                nreq = (uint32_t)(h_mask[w1] & 0xffffffffull); eflag = (int)(h_mask[w1] >> 32);
-                if (!nreq) break;
-                aln_total += nreq; if (first_round) aln_first += nreq;
-                AlignJob J{};
-                J.qseq = RD.seq; J.qoff = RD.off; J.tseq = RD.seq; J.toff = RD.off; J.qidx = req_q.p; J.tidx = req_t.p; J.npairs = nreq;
-                J.match = 2; J.mismatch = -2; J.ext = 1; J.k = k; J.open = req_open.p; J.match_id = req_mid.p;     // cluster.py:130
-                J.score = nullptr; J.ncols = nullptr; J.nmatch = nullptr; J.region = req_region.p; J.bp = nullptr; J.bp_windows = 0; J.window = 1; J.span = nullptr;
-                rc = ngsid_launch_align(ctx, J, RD.maxlen, RD.maxlen, 5, RD.minlen); if (rc) return rc;     // gap open is 2..5 (cluster.py:189-196)
-                hipLaunchKernelGGL(k_cache_insert, dim3((nreq + 255) / 256), dim3(256), 0, ctx->stream, D, req_q.p, req_slot.p, req_region.p, nreq);
-                HIPCHK(ctx, hipGetLastError());
-            }
-            first_round = false;
-            // ---- the items that decided "new representative", in block order (bit mask of the block, fetched with the last request count above, scanned on the host)
-            if (eflag) NGSID_FAIL(ctx, NGSID_ERR_NO_PTABLE, "no p_shared entry for an (e1,e2) pair met during mapping (KeyError in cluster.py:367)");
-            uint32_t C[TMAX + 1]; uint32_t nC = 0;
-            for (uint32_t wd = w0; wd < w1 && nC <= TMAX; ++wd) {
-                unsigned long long m = h_mask[wd];
-                while (m && nC <= TMAX) { C[nC++] = b0 + wd * 64 + (uint32_t)__builtin_ctzll(m); m &= m - 1; }
-            }
-            if (nC == 0) { lo = b1; break; }
-            // ---- up to TMAX of them become representatives at once.  All are built (slots R, R+1, ...) and the later items are counted against
-            // each; everything before the first item that shares >= min_shared minimizers with an EARLIER tentative representative is final
-            // (such an item is the only kind whose decision can change), the tentative representatives before that item are committed, the
-            // rest of the block is decided again.  With one new representative per pass this is the plain greedy restart.
-            const uint32_t T = std::min<uint32_t>(std::min<uint32_t>(tcur, nC), stride - S.R);
-            const uint32_t next_c = nC > T ? C[T] : 0xffffffffu;
-            uint32_t creads[TMAX];
-            for (uint32_t t = 0; t < T; ++t) creads[t] = h_items[C[t]];
-            rc = build_reps(ctx, S, creads, T, mzcode.p, ctx->h_mzoff.data(), h_mzcnt.data()); if (rc) return rc;
-            refresh();
-            if (C[0] + 1 < b1) {
-                PosBatch PB; for (uint32_t t = 0; t < 64; ++t) PB.pos[t] = t < T ? C[t] : 0xffffffffu;
-                ProfScope ps_(ctx, "k_count_hits");
-                hipLaunchKernelGGL(k_count_hits_reps, dim3((b1 - C[0] - 1 + 3) / 4, T), dim3(256), 0, ctx->stream, D, d_items.p, C[0] + 1, b1, b0, S.R, PB, cnt.p, stride);
-            }
-            HIPCHK(ctx, hipGetLastError());
-            uint32_t cut = 0xffffffffu;
-            HIPCHK(ctx, hipMemsetAsync(d_scal.p + 1, 0xff, 4, ctx->stream));
-            if (C[0] + 1 < b1) hipLaunchKernelGGL(k_first_affected, dim3((b1 - C[0] - 1 + 3) / 4), dim3(256), 0, ctx->stream, D, d_items.p, C[0] + 1, b1, b0, cnt.p, stride, S.R, T, d_scal.p + 1);
-            HIPCHK(ctx, hipGetLastError());
-            h_po.resize(T + 1);
-            HIPCHK(ctx, hipMemcpyAsync(&cut, d_scal.p + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(h_po.data(), S.pool_off.p + S.R, 8ull * (T + 1), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            cut = std::min(cut, next_c);
-            uint32_t c = 0; while (c < T && C[c] < cut) ++c;                 // >= 1: the affected item lies behind C[0]
-            const uint32_t R_before = S.R;
-            rc = commit_reps(ctx, S, c, h_po.data()); if (rc) return rc;
-            newreps += c;
-            tcur = c == T ? std::min<uint32_t>(TMAX, tcur * 2) : std::max<uint32_t>(1, c);      // speculate wider only while it pays
-            if (cut >= b1) { lo = b1; break; }
-            lo = cut;
-            // the columns of the tentative representatives that were not committed go back to zero (their entries sit in rows >= cut)
-            if (c < T) HIPCHK(ctx, hipMemset2DAsync(cnt.p + (uint64_t)(lo - b0) * stride + S.R, (size_t)stride * 8, 0, (size_t)(T - c) * 8, b1 - lo, ctx->stream));
-            refresh();
-            if (S.R + 1 > stride) need_full = true;
-            hipLaunchKernelGGL(k_reset_items, dim3((b1 - lo + 255) / 256), dim3(256), 0, ctx->stream, D, d_items.p, lo, b1, b0, cnt.p, stride, R_before, c);
-            HIPCHK(ctx, hipGetLastError());
-            // Round 6: a block that keeps restarting is cut short.  Every restart round runs five kernels over the rest of the block (reset, decide, alignment cursor, mask, hit
-            // counts of the next tentative representatives), so its cost grows with that rest, and the NUMBER of rounds is given by the data (one per stretch between dependent
-            // new representatives) - the noisy tail of a score-ordered set brings thousands of them at once (mu = 14: 2 196 new representatives in the last 408 k reads, after
-            // 540 k reads with none, i.e. in a block that had grown to its largest size).  From the third round on the rest is capped at `trunc` items; the items behind the cut
-            // go back to "undecided" and are decided from scratch by the next block, which starts at that size.  Results do not depend on where blocks end (tested).
-            ++rounds;
-            if (trunc && rounds >= 3 && b1 - lo > trunc) {
-                const uint32_t nb1 = lo + trunc;
-                hipLaunchKernelGGL(k_undecide, dim3((b1 - nb1 + 255) / 256), dim3(256), 0, ctx->stream, D, d_items.p, nb1, b1);
-                HIPCHK(ctx, hipGetLastError());
-                b1 = nb1; if (!blk_fixed) blk = std::max<uint32_t>(trunc, 8192);
+                B.b1 = nb1;
             }
         }
-        b0 = b1;
-        if (!blk_fixed) {
-            // blocks grow while new representatives are rare and shrink when they are frequent (every new representative re-decides part of the rest of its block)
-            const double waste = aln_first ? (double)(aln_total - aln_first) / (double)aln_first : (aln_total ? 1.0 : 0.0);
-            static const bool trace_blocks = getenv("NGSID_CLUSTER_TRACE") != nullptr;      // dev aid: one line per block on stderr
-            if (trace_blocks) fprintf(stderr, "[ngsid cluster] block ending at %u: %u restart rounds, %u new representatives (R = %u), pairs aligned in the first round %llu, later %llu (%.3f)\n", b1, rounds, newreps, S.R, (unsigned long long)aln_first, (unsigned long long)(aln_total - aln_first), waste);
-            // (a rule by restart ROUNDS instead of new representatives was measured in round 6 and lost: 0.45 against 0.41 s at mu = 14 - small blocks stay the better ones while
-            // representatives keep coming, whatever the number of rounds they take)
-            const long s_reps = (long)ngsid_opt(ctx, "cluster_shrink_reps", 32); const uint32_t floor_blk = (uint32_t)ngsid_opt(ctx, "cluster_block_floor", 4096);
-            if (newreps <= 2) blk = std::min<uint32_t>(blk * 2, BLK); else if ((long)newreps > s_reps) blk = std::max<uint32_t>(blk / 2, floor_blk);
-            // the hit matrix of a block is rows x (representatives + room) x 8 bytes: a noisy set with thousands of representatives keeps its blocks under 12 GB of it
-            const uint64_t cols = std::max<uint64_t>(stride, ((uint64_t)S.R + 256 + 63) / 64 * 64);
-            while (blk > 8192 && (uint64_t)blk * cols * 8 > ((uint64_t)12 << 30)) blk /= 2;
-        }
+        policy.next_block(B, run.S.R, run.stride);
+        b0 = B.b1;
     }
     ht.mark("blocks");
-    // ---- results
-    DevBuf<int32_t> d_rep; DevBuf<uint8_t> d_status; DevBuf<double> d_herr_out; DevBuf<unsigned long long> d_counters;
-    HIPCHK(ctx, d_rep.alloc(N)); HIPCHK(ctx, d_status.alloc(N)); HIPCHK(ctx, d_herr_out.alloc(N)); HIPCHK(ctx, d_counters.alloc(4));
-    HIPCHK(ctx, hipMemsetAsync(d_counters.p, 0, 32, ctx->stream));
-    refresh();
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, D, N, prev_batch ? d_seeded.p : nullptr, d_rep.p, d_status.p, d_herr_out.p, d_counters.p);
-    HIPCHK(ctx, hipGetLastError());
-    static thread_local PinVec<uint8_t> h_status; static thread_local PinVec<double> h_herr; static thread_local PinVec<int32_t> h_rep; h_status.resize(N); h_herr.resize(N); h_rep.resize(N); unsigned long long h_cnt[4];
-    HIPCHK(ctx, hipMemcpyAsync(h_rep.data(), d_rep.p, 4 * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_status.data(), d_status.p, N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_herr.data(), d_herr_out.p, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_cnt, d_counters.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ht.mark("finalize + download");
-    memcpy(rep_of_read, h_rep.data(), 4 * N);
-    if (status_out) memcpy(status_out, h_status.data(), N);
-    if (hpc_err_out) memcpy(hpc_err_out, h_herr.data(), 8 * N);
-    if (counters) for (int i = 0; i < 4; ++i) counters[i] = h_cnt[i];
-    return NGSID_OK;
+    return run.finalize(ht, prev_batch != nullptr, rep_of_read, hpc_err_out, status_out, counters);
 }
