@@ -387,6 +387,33 @@ class Api:
         if rc: self._err(rc)
         return rep, herr, st, cnt
 
+    def cluster_greedy_segmented(self, rs: ReadSet, prm: ClusterParams, seg_off, acc_rank=None):
+        """include/ngsid_batch.h: reads [seg_off[s], seg_off[s+1]) are sample s, clustered as if alone -> (rep_of, herr, status, counters[n_segments, 4]), rep_of
+        indexing the whole set.  A library without the entry point (the test oracle) runs cluster_greedy once per segment: that loop is the definition of the call."""
+        n = rs.n
+        so = np.ascontiguousarray(seg_off, dtype=np.uint64); ns = len(so) - 1
+        ar = None if acc_rank is None else np.ascontiguousarray(acc_rank, dtype=np.uint32)
+        rep = np.zeros(n, dtype=np.int32); herr = np.zeros(n); st = np.zeros(n, dtype=np.uint8); cnt = np.zeros((max(ns, 0), 4), dtype=np.uint64)
+        if hasattr(self.lib, self.prefix + "cluster_greedy_segmented"):
+            if ns < 0: self._seg_err("seg_off is empty")
+            rc = self._call("cluster_greedy_segmented", C.byref(rs.c), C.byref(prm), _p(ar), _p(so), C.c_uint64(ns), _p(rep), _p(herr), _p(st), _p(cnt))
+            if rc: self._err(rc)
+            return rep, herr, st, cnt
+        if ns < 0 or int(so[0]) != 0 or int(so[-1]) != n or (np.diff(so.astype(np.int64)) < 0).any():
+            self._seg_err("seg_off must start at 0, end at the number of reads and not decrease")
+        if rs.mem != MEM_HOST: raise ValueError("the per-segment fallback takes a host read set")
+        from .hostutil import subset_reads
+        for s in range(ns):
+            a, b = int(so[s]), int(so[s + 1])
+            if a == b: continue
+            r, h, t, c = self.cluster_greedy(subset_reads(rs, np.arange(a, b)), prm, acc_rank=None if ar is None else ar[a:b])
+            rep[a:b] = r + a; herr[a:b] = h; st[a:b] = t; cnt[s] = c
+        return rep, herr, st, cnt
+
+    @staticmethod
+    def _seg_err(text):
+        raise NgsidError(-2, text)
+
     def merge_representatives(self, reps: ReadSet, prm: ClusterParams, score, hpc_err, batch, n_batches, acc_rank=None):
         """merge rounds of parallel_clustering on gathered representatives -> rep_of [R] (index of the final representative)"""
         R = reps.n

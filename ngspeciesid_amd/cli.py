@@ -39,6 +39,10 @@ def write_fastq(args):
                 out.write("@{0}\n{1}\n+\n{2}\n".format(acc, seq, qual))
 
 
+FASTQ_DIR_NEEDS_T1 = ("--fastq_dir requires --t 1: with --t N the cluster membership depends on the batch schedule of every sample, and merge rounds are not "
+                      "batched across samples. Run with --t 1, or run the samples one by one with --fastq.")
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -47,6 +51,7 @@ def build_parser():
     rf = p.add_mutually_exclusive_group(required=True)
     rf.add_argument('--fastq', type=str)
     rf.add_argument('--use_old_sorted_file', action='store_true')
+    rf.add_argument('--fastq_dir', type=str, help='extension: a folder of demultiplexed FASTQ files; every *.fastq / *.fq directly under it is one sample (sorted name order) and gets <outfolder>/<file name without extension>/ with the files a run of --fastq on it writes; all samples are clustered in one pass (needs --t 1)')
     p.add_argument('--t', dest="nr_cores", type=int, default=8, help='Number of score-ordered batches (the reference\'s cores); the cluster membership depends on it exactly like in the reference')
     p.add_argument('--d', dest="print_output", type=int, default=10000)
     p.add_argument('--q', dest="quality_threshold", type=float, default=7.0)
@@ -101,6 +106,13 @@ def cli(argv=None):
         args.k, args.w = 15, 50
     elif args.ont:
         args.k, args.w = 13, 20
+    if getattr(args, "fastq_dir", None):
+        if args.nr_cores != 1:
+            logging.error(FASTQ_DIR_NEEDS_T1); sys.exit(1)
+        if not args.outfolder:
+            logging.error("--fastq_dir needs --outfolder (one sub-folder per sample is written there)."); sys.exit(1)
+        if not os.path.isdir(args.fastq_dir):
+            logging.error("--fastq_dir %s is not a folder." % args.fastq_dir); sys.exit(1)
     if args.medaka:
         logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
     if args.k > 32 or args.k < 1:

@@ -18,6 +18,7 @@
 // Aligner results are cached per (read, representative) since they do not depend on the database.
 #include "ngsid_internal.h"
 #include "../../include/ngsid_tables.h"
+#include "../../include/ngsid_batch.h"
 #include <math.h>
 #include <algorithm>
 
@@ -441,6 +442,52 @@ __global__ void k_finalize(ClDev D, uint64_t n, const uint8_t* __restrict__ seed
     }
 }
 
+// ---- segmented call (ngsid_cluster_greedy_segmented): the segment number of a read goes into the free high bits of its minimizer codes, after minimizer selection.
+// The representatives' code lists and the sorted index are built from these codes, so the one binary search of k_count_hits / k_count_hits_reps / mapped_span
+// lands inside the read's own segment and never walks a posting of another one.  One 64-lane workgroup per read (the shape of the CSR gather).
+// The segment of read r is found in the uploaded offsets (the last s with seg_off[s] <= r: empty segments share an offset with their successor) and also written to segof[r].
+__global__ void k_tag_codes(uint64_t* __restrict__ mzcode, const uint64_t* __restrict__ mzoff, const uint64_t* __restrict__ seg_off, uint32_t n_seg, uint32_t* __restrict__ segof, uint64_t n, int shift)
+{
+    const uint64_t r = blockIdx.x; if (r >= n) return;
+    uint32_t lo = 0, hi = n_seg + 1;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (seg_off[mid] <= r) lo = mid + 1; else hi = mid; }
+    const uint32_t sg = lo - 1;                                      // seg_off[0] = 0 <= r < n = seg_off[n_seg]: 0 <= sg < n_seg
+    if (threadIdx.x == 0) segof[r] = sg;
+    if (n_seg < 2) return;
+    const uint64_t tag = (uint64_t)sg << shift, e = mzoff[r + 1];
+    for (uint64_t j = mzoff[r] + threadIdx.x; j < e; j += blockDim.x) mzcode[j] |= tag;
+}
+
+// the four counters of k_finalize per segment, from the finished per-read results (mapped, aligned, reads that reached the alignment stage, new representatives).
+// A wave whose reads are all of one segment - nearly every wave - adds once per counter, the others once per read.
+__global__ void k_seg_counters(const uint8_t* __restrict__ status, const uint8_t* __restrict__ alnflag, const uint32_t* __restrict__ segof, uint64_t n,
+                               unsigned long long* __restrict__ counters)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t sg = live ? segof[i] : 0xffffffffu;
+    const uint8_t st = live ? status[i] : (uint8_t)NGSID_ST_SHORT;
+    const bool m = live && st == NGSID_ST_MAPPED, a = live && st == NGSID_ST_ALIGNED, nr = live && st == NGSID_ST_NEWREP;
+    const bool al = live && st != NGSID_ST_SHORT && st != NGSID_ST_SEEDED && alnflag[i] != 0;
+    const uint32_t sg0 = (uint32_t)__shfl((int)sg, 0);
+    if (__ballot(live && sg != sg0) == 0ull) {
+        const unsigned long long c0 = __popcll(__ballot(m)), c1 = __popcll(__ballot(a)), c2 = __popcll(__ballot(al)), c3 = __popcll(__ballot(nr));
+        if ((threadIdx.x & 63) == 0 && live) {
+            unsigned long long* c = counters + 4ull * sg0;
+            if (c0) atomicAdd(&c[0], c0);
+            if (c1) atomicAdd(&c[1], c1);
+            if (c2) atomicAdd(&c[2], c2);
+            if (c3) atomicAdd(&c[3], c3);
+        }
+    } else if (live) {
+        unsigned long long* c = counters + 4ull * sg;
+        if (m) atomicAdd(&c[0], 1ull);
+        if (a) atomicAdd(&c[1], 1ull);
+        if (al) atomicAdd(&c[2], 1ull);
+        if (nr) atomicAdd(&c[3], 1ull);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host driver
 namespace {
 struct RepStore {
@@ -582,6 +629,8 @@ struct ClusterRun {
     DevBuf<uint64_t>& cnt; uint32_t stride = 0;      // (kept in the context: a block's matrix is up to a few GB, a fresh allocation of it costs 20+ ms)
     DevBuf<uint32_t> req_q, req_t, req_slot, d_scal; DevBuf<int32_t> req_open, req_mid, req_region;
     DevBuf<unsigned long long> d_mask; PinVec<unsigned long long> h_mask;
+    const uint64_t* seg_off = nullptr; uint64_t n_seg = 0; DevBuf<uint32_t> d_segof; DevBuf<uint64_t> d_segoff;      // segmented call: reads [seg_off[s], seg_off[s+1]) are sample s (null: the plain call)
+    uint64_t restart_rounds = 0;
     explicit ClusterRun(ngsid_ctx* c) : ctx(c), cnt(c->cl_cnt) {}
     void refresh() { D.rep_read = S.rep_read.p; D.pool = S.pool.p; D.pool_off = S.pool_off.p; }      // the three pointers of D that move when S grows
     // ---- per-read preprocessing (a1-a3), the max-gap table, the items to process and the per-read state
@@ -600,7 +649,8 @@ struct ClusterRun {
             rc = ngsid_minimizers_csr(ctx, RD, k, w, ngsid_ctx_mz(ctx), mzcnt.p, hlen.p, herr0.p, rawerr.p, v_mzcnt.data(), v_hlen.data(), &bad); if (rc) return rc;
             if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "read %lld: base outside ACGTN", bad);
         }
-        if (k <= 21 && N >= 1024) {       // key of the minimizer cache (the polisher's strand detection may be handed the same reads next); small sets are not worth the fingerprint
+        if (seg_off) { rc = tag_segments(); if (rc) return rc; }      // (the minimizer cache stays invalid: the codes in the context now carry segment numbers)
+        else if (k <= 21 && N >= 1024) {       // key of the minimizer cache (the polisher's strand detection may be handed the same reads next); small sets are not worth the fingerprint
             unsigned long long fp = 0; rc = ngsid_reads_fingerprint(ctx, RD, &fp); if (rc) return rc;
             ctx->mzc.n = N; ctx->mzc.total = RD.total; ctx->mzc.k = k; ctx->mzc.w = w; ctx->mzc.fp = fp; ctx->mzc.valid = true;
         }
@@ -619,6 +669,16 @@ struct ClusterRun {
         if (prev_batch) { int mn = prev_batch[0]; for (uint64_t i = 1; i < N; ++i) mn = std::min(mn, prev_batch[i]); lowest = std::max(1, mn); }
         static thread_local PinVec<uint32_t> v_items; v_items.clear(); v_items.reserve(N);
         if (prev_batch) { h_seeded.assign(N, 0); for (uint64_t i = 0; i < N; ++i) { if (prev_batch[i] == lowest) h_seeded[i] = 1; else v_items.push_back((uint32_t)i); } }
+        else if (seg_off && n_seg > 1 && ngsid_opt(ctx, "cluster_seg_order", 0) == 0) {
+            // interleaved: by rank within the segment, then by segment.  Greedy order only matters within a segment (no item shares a code with a representative of another
+            // one), so the early representatives of ALL samples are tentative together in a restart round, instead of each sample restarting the block in its turn.
+            std::vector<uint64_t> act; for (uint64_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] > seg_off[s]) act.push_back(s);
+            for (uint64_t j = 0; !act.empty(); ++j) {
+                size_t keep = 0;
+                for (size_t a = 0; a < act.size(); ++a) { const uint64_t s = act[a]; v_items.push_back((uint32_t)(seg_off[s] + j)); if (seg_off[s] + j + 1 < seg_off[s + 1]) act[keep++] = s; }
+                act.resize(keep);
+            }
+        }
         else for (uint64_t i = 0; i < N; ++i) v_items.push_back((uint32_t)i);
         NI = (uint32_t)v_items.size(); h_items = v_items.data();
         HIPCHK(ctx, d_items.alloc(NI)); if (NI) HIPCHK(ctx, hipMemcpyAsync(d_items.p, v_items.data(), 4ull * NI, hipMemcpyHostToDevice, ctx->stream));
@@ -633,6 +693,21 @@ struct ClusterRun {
         HIPCHK(ctx, hipMemsetAsync(alnflag.p, 0, N, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(kind.p, 0, N, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(top.p, 0, 4 * N, ctx->stream));            // (read by rep_can_matter for reads that never reached k_decide_map's top pass: short reads)
+        return NGSID_OK;
+    }
+    // ---- segmented call: segment of every read, and the segment number in the free high bits of the minimizer codes just computed
+    int32_t tag_segments()
+    {
+        // bits a code uses: 3 per letter (k <= 21); k >= 22: dense ranks below the call's minimizer count
+        int used = 3 * k;
+        if (k > 21) { const uint64_t total = ctx->h_mzoff[N]; used = 1; while (used < 64 && (total >> used) != 0) ++used; }
+        const int free_bits = 64 - used;
+        if (n_seg > 1 && (free_bits <= 0 || (free_bits < 64 && ((n_seg - 1) >> free_bits) != 0)))
+            NGSID_FAIL(ctx, NGSID_ERR_ARG, "%llu segments, but a minimizer code of k = %d leaves %d bits for the segment number", (unsigned long long)n_seg, k, free_bits < 0 ? 0 : free_bits);
+        HIPCHK(ctx, d_segof.alloc(N)); HIPCHK(ctx, d_segoff.alloc(n_seg + 1));
+        HIPCHK(ctx, hipMemcpyAsync(d_segoff.p, seg_off, 8 * (n_seg + 1), hipMemcpyHostToDevice, ctx->stream));      // (the caller's array: valid for the whole call, so nothing waits for this copy)
+        hipLaunchKernelGGL(k_tag_codes, dim3((unsigned)N), dim3(64), 0, ctx->stream, ctx->pol_mzcode.p, ctx->mz_off.p, d_segoff.p, (uint32_t)n_seg, d_segof.p, N, used);
+        HIPCHK(ctx, hipGetLastError());
         return NGSID_OK;
     }
     // ---- the empty representative store and, in a merge round, the seeded representatives
@@ -768,7 +843,7 @@ struct ClusterRun {
         return NGSID_OK;
     }
     // ---- results
-    int32_t finalize(HostTimer& ht, bool seeded, int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4])
+    int32_t finalize(HostTimer& ht, bool seeded, int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4], uint64_t* seg_counters = nullptr)
     {
         DevBuf<int32_t> d_rep; DevBuf<uint8_t> d_status; DevBuf<double> d_herr_out; DevBuf<unsigned long long> d_counters;
         HIPCHK(ctx, d_rep.alloc(N)); HIPCHK(ctx, d_status.alloc(N)); HIPCHK(ctx, d_herr_out.alloc(N)); HIPCHK(ctx, d_counters.alloc(4));
@@ -781,6 +856,13 @@ struct ClusterRun {
         HIPCHK(ctx, hipMemcpyAsync(h_status.data(), d_status.p, N, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(h_herr.data(), d_herr_out.p, 8 * N, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(h_cnt, d_counters.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+        DevBuf<unsigned long long> d_segcnt;
+        if (seg_counters && n_seg) {
+            HIPCHK(ctx, d_segcnt.alloc(4 * n_seg)); HIPCHK(ctx, hipMemsetAsync(d_segcnt.p, 0, 32 * n_seg, ctx->stream));
+            hipLaunchKernelGGL(k_seg_counters, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, d_status.p, alnflag.p, d_segof.p, N, d_segcnt.p);
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(seg_counters, d_segcnt.p, 32 * n_seg, hipMemcpyDeviceToHost, ctx->stream));
+        }
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         ht.mark("finalize + download");
         memcpy(rep_of_read, h_rep.data(), 4 * N);
@@ -792,21 +874,27 @@ struct ClusterRun {
 };
 }
 
-extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_cluster_params_t* prm,
-                                        const uint32_t* acc_rank, const int32_t* prev_batch, const double* known_err,
-                                        int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4])
+// The driver of both entry points.  seg_off != null: the segmented call (n_seg segments, per-segment counters in seg_counters, no prev_batch / known_err)
+static int32_t cluster_greedy_run(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_cluster_params_t* prm,
+                                  const uint32_t* acc_rank, const int32_t* prev_batch, const double* known_err,
+                                  const uint64_t* seg_off, uint64_t n_seg,
+                                  int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4], uint64_t* seg_counters)
 {
-    ApiClock api_clock_(ctx, "cluster_greedy");
-    if (!ctx) return NGSID_ERR_ARG;
-    if (!reads || !prm || !rep_of_read) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     const int k = prm->k, w = prm->w;
     if (k < 1 || k > NGSID_MAX_K || w < k) NGSID_FAIL(ctx, NGSID_ERR_ARG, "bad k/w (k=%d, w=%d; k <= %d)", k, w, NGSID_MAX_K);
+    if (seg_off) {      // everything that needs no device work is checked before any is done
+        if (seg_off[0] != 0 || seg_off[n_seg] != reads->n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "seg_off must start at 0 and end at the number of reads (%llu .. %llu, %llu reads)", (unsigned long long)seg_off[0], (unsigned long long)seg_off[n_seg], (unsigned long long)reads->n);
+        for (uint64_t s = 0; s < n_seg; ++s) if (seg_off[s + 1] < seg_off[s]) NGSID_FAIL(ctx, NGSID_ERR_ARG, "seg_off decreases at segment %llu", (unsigned long long)s);
+        if (k <= 21 && n_seg > 1 && ((n_seg - 1) >> (64 - 3 * k)) != 0) NGSID_FAIL(ctx, NGSID_ERR_ARG, "%llu segments, but a minimizer code of k = %d leaves %d bits for the segment number", (unsigned long long)n_seg, k, 64 - 3 * k);
+        if (seg_counters) memset(seg_counters, 0, 32 * n_seg);
+    }
     HostTimer ht(ctx->stream, "cluster");
     ClusterRun run(ctx);
     int32_t rc = ngsid_upload_reads(ctx, reads, &run.RD, true); if (rc) return rc;
     ht.mark("upload");
     run.N = run.RD.n; run.k = k;
     if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
+    run.seg_off = seg_off; run.n_seg = n_seg;
     if (run.N == 0) return NGSID_OK;
     if (run.N > 0x7fffffffull) NGSID_FAIL(ctx, NGSID_ERR_ARG, "too many reads");
     if (!g_cl_tables[ctx->device & 15]) { HIPCHK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(c_round2_t), NGSID_ROUND2_T, sizeof(double) * 15)); g_cl_tables[ctx->device & 15] = true; }
@@ -825,7 +913,7 @@ extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* rea
             rc = run.align_rounds(B); if (rc) return rc;
             rc = run.commit_speculative(policy, B); if (rc) return rc;
             if (B.lo >= B.b1) break;      // nothing left to decide again: not a restart
-            ++B.rounds;
+            ++B.rounds; ++run.restart_rounds;
             const uint32_t nb1 = policy.cut_restarting(B);
             if (nb1 < B.b1) {
                 hipLaunchKernelGGL(k_undecide, dim3((B.b1 - nb1 + 255) / 256), dim3(256), 0, ctx->stream, run.D, run.d_items.p, nb1, B.b1);
@@ -837,5 +925,27 @@ extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* rea
         b0 = B.b1;
     }
     ht.mark("blocks");
-    return run.finalize(ht, prev_batch != nullptr, rep_of_read, hpc_err_out, status_out, counters);
+    if (seg_off && ctx->prof) ctx->prof_acc["count_cluster_seg_restart_rounds"].second += run.restart_rounds;      // a work counter like poa_dp_rows / sg_dp_cells, not a kernel: "<name> <rounds> 0" in ngsid_profile_read
+    return run.finalize(ht, prev_batch != nullptr, rep_of_read, hpc_err_out, status_out, counters, seg_counters);
+}
+
+extern "C" int32_t ngsid_cluster_greedy(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_cluster_params_t* prm,
+                                        const uint32_t* acc_rank, const int32_t* prev_batch, const double* known_err,
+                                        int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t counters[4])
+{
+    ApiClock api_clock_(ctx, "cluster_greedy");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (!reads || !prm || !rep_of_read) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    return cluster_greedy_run(ctx, reads, prm, acc_rank, prev_batch, known_err, nullptr, 0, rep_of_read, hpc_err_out, status_out, counters, nullptr);
+}
+
+extern "C" int32_t ngsid_cluster_greedy_segmented(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_cluster_params_t* prm, const uint32_t* acc_rank,
+                                                  const uint64_t* seg_off, uint64_t n_segments,
+                                                  int32_t* rep_of_read, double* hpc_err_out, uint8_t* status_out, uint64_t* counters)
+{
+    ApiClock api_clock_(ctx, "cluster_greedy_segmented");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (!reads || !prm || !rep_of_read || !seg_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    if (n_segments > 0xffffffffull) NGSID_FAIL(ctx, NGSID_ERR_ARG, "too many segments");
+    return cluster_greedy_run(ctx, reads, prm, acc_rank, nullptr, nullptr, seg_off, n_segments, rep_of_read, hpc_err_out, status_out, nullptr, counters);
 }

@@ -254,8 +254,9 @@ def normalized_reads(sr: SortedReads):
     return sr.rs
 
 
-def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=None):
+def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=None, precomputed=None):
     """clusters the reads sel (indices into the sorted set, ascending = processing order).
+    precomputed (multi-sample mode, --t 1): this sample's (rep_of, herr, status, counters) slice of a segmented clustering call over cluster_inputs() - the library call is skipped.
     -> rep_of [n] (sorted index of the final representative, self for reads outside sel), herr [n], pos [n] (position in the cluster's read list),
        counters, acc_id [n] (dense rank of the accession 'name_score', -1 outside sel; None when all accessions are distinct)"""
     n = sr.n
@@ -268,7 +269,7 @@ def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=Non
         logging.warning("%d reads are longer than %d bases: they are not clustered and stay singletons (use --m / --s to filter by length)", int(too_long.sum()), MAX_READ_LEN)
         sel = sel[~too_long]
     whole = work_dev is not None and len(sel) == n and args.nr_cores <= 1       # every read in one call: the device-resident set as it is
-    work = work_dev if whole else subset_reads(work if work is not None else sr.rs, sel)
+    if precomputed is None: work = work_dev if whole else subset_reads(work if work is not None else sr.rs, sel)
     prm = cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
                          aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
                          symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=select_p_table(args.k, args.w))
@@ -330,7 +331,7 @@ def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=Non
         pos_l = trk["pos"]                     # (= parallelize.list_positions(len(sel), joins), kept up to date round by round)
     else:
         t1 = time()
-        rep_l, herr_l, st, cnt = api.cluster_greedy(work, prm, acc_rank=rank)
+        rep_l, herr_l, st, cnt = precomputed if precomputed is not None else api.cluster_greedy(work, prm, acc_rank=rank)
         T["cluster_library_call"] = time() - t1; t1 = time()
         counters[:] = cnt
         rep_l = rep_l.astype(np.int64)
@@ -348,6 +349,14 @@ def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=Non
     if len(rank) and int(rank.max()) + 1 < len(rank):                  # duplicate accessions exist (same name AND same score)
         acc_id = np.full(n, -1, dtype=np.int64); acc_id[sel] = rank
     return rep_of, herr, pos, counters, acc_id
+
+
+def cluster_inputs(sr: SortedReads, work, sel):
+    """what cluster() hands to its one library call at --t 1: (host read set of the clustered reads, their accession ranks)"""
+    sel = sel[sr.lens[sel] <= MAX_READ_LEN]
+    fut = getattr(sr, "rank_all", None)
+    rank = fut.result() if (fut is not None and len(sel) == sr.n) else _string_ranks(sr.names, sr.sfx, sel)
+    return subset_reads(work if work is not None else sr.rs, sel), rank
 
 
 def write_round_dump(args, sr, sel, it, reps, r, herr, pos_):
@@ -636,6 +645,78 @@ def main(args, api=None):
 
 
 def _main(args, api):
+    if getattr(args, "fastq_dir", None):
+        return _main_samples(args, api)
+    st = _ingest(args, api)
+    sr, work, work_dev, sel, T = st["sr"], st["work"], st["work_dev"], st["sel"], st["T"]
+    t0 = time()
+    logging.info(f"Starting Clustering: {len(sel)} reads")
+    try:
+        clustered = cluster(sr, work, sel, args, api, work_dev, T)
+    finally:                                        # sorted.fastq is written whatever the clustering call did (the reference has it on disk before it clusters)
+        deferred, args._deferred = getattr(args, "_deferred", []), []
+        for fn_, a_, kw_ in deferred: _write(args, fn_, *a_, **kw_)
+    return _finish(args, api, st, clustered, t0)
+
+
+def sample_files(folder):
+    """the samples of --fastq_dir: every *.fastq / *.fq directly under the folder, in sorted name order -> [(sample name = file name without extension, path)]"""
+    out = []
+    for f in sorted(os.listdir(folder)):
+        path = os.path.join(folder, f)
+        if os.path.isfile(path) and f.endswith((".fastq", ".fq")):
+            out.append((os.path.splitext(f)[0], path))
+    return out
+
+
+def _main_samples(args, api):
+    """--fastq_dir: every file of the folder is one sample with its own output folder, holding what a run of --fastq on that file writes.  The files are ingested and scored one
+    after the other in this context (score_and_sort; the per-sample selections --m / --s / --sample_size / --top_reads apply per sample, a random --sample_size draws in sample
+    order), the selected reads of ALL samples are clustered in one segmented call (include/ngsid_batch.h), then every sample runs the writers and the consensus stages of a
+    single run on its slice.  (The consensus stages still run per sample here: pipeline.run_hot_path_samples is the array form that batches them too.)"""
+    import copy
+    T = {}
+    subs = []
+    for name, path in sample_files(args.fastq_dir):
+        a = copy.copy(args)
+        a.fastq, a.fastq_dir, a.outfolder = path, None, os.path.join(args.outfolder, name)
+        os.makedirs(a.outfolder, exist_ok=True)
+        subs.append((a, _ingest(a, api)))
+    if not subs:
+        raise ValueError("--fastq_dir %s holds no *.fastq / *.fq file" % args.fastq_dir)
+    t0 = time()
+    try:
+        ins = [cluster_inputs(st["sr"], st["work"], st["sel"]) for _, st in subs]
+        rs = [x[0] for x in ins]
+        lens = np.concatenate([np.diff(x.off.astype(np.int64)) for x in rs])
+        off = np.zeros(len(lens) + 1, dtype=np.uint64); off[1:] = np.cumsum(lens)
+        seg = np.zeros(len(rs) + 1, dtype=np.uint64); seg[1:] = np.cumsum([x.n for x in rs])
+        allr = ReadSet(np.concatenate([x.seq for x in rs]), np.concatenate([x.qual for x in rs]), off)
+        prm = cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
+                             aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
+                             symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=select_p_table(args.k, args.w))
+        if np.isnan(select_p_table(args.k, args.w)).all():
+            raise KeyError("no rows in the shared-minimizer table for k=%d, w=%d (NGSpeciesID:72-77)" % (args.k, args.w))
+        logging.info("Starting Clustering: %d reads of %d samples" % (allr.n, len(subs)))
+        rep, herr, status, cnt = api.cluster_greedy_segmented(allr, prm, seg, acc_rank=np.concatenate([x[1] for x in ins]).astype(np.uint32)) if allr.n else (np.zeros(0, np.int32), np.zeros(0), np.zeros(0, np.uint8), np.zeros((len(rs), 4), np.uint64))
+    finally:
+        for a, _ in subs:
+            deferred, a._deferred = getattr(a, "_deferred", []), []
+            for fn_, a_, kw_ in deferred: _write(a, fn_, *a_, **kw_)
+    T["cluster"] = time() - t0
+    out = {}
+    for x, (a, st) in enumerate(subs):
+        lo, hi = int(seg[x]), int(seg[x + 1])
+        pre = (rep[lo:hi] - np.int32(lo), herr[lo:hi], status[lo:hi], cnt[x])
+        t1 = time()
+        clustered = cluster(st["sr"], st["work"], st["sel"], a, api, st["work_dev"], st["T"], precomputed=pre)
+        out[os.path.basename(a.outfolder)] = _finish(a, api, st, clustered, t1)
+    return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
+                clusters=sum(r["clusters"] for r in out.values()))
+
+
+def _ingest(args, api):
+    """score + sort + resident read set + the per-sample selection of the reads to cluster (NGSpeciesID:36-63)"""
     T = {}
     t0 = time()
     args.outfile = os.path.join(args.outfolder, "sorted.fastq")
@@ -659,13 +740,14 @@ def _main(args, api):
         sel = sel[:args.sample_size]
     elif 0 < args.sample_size < len(sel):
         sel = sel[np.asarray(sorted(random.sample(range(len(sel)), args.sample_size)), dtype=np.int64)]
+    return dict(sr=sr, work=work, work_dev=work_dev, sel=sel, T=T)
+
+
+def _finish(args, api, st, clustered, t0):
+    """everything behind the clustering call: cluster files, consensus, polishing (NGSpeciesID:99-152)"""
+    sr, work, work_dev, sel, T = st["sr"], st["work"], st["work_dev"], st["sel"], st["T"]
+    rep_of, herr, pos, counters, acc_id = clustered
     abundance_cutoff = int(args.abundance_ratio * len(sel))
-    logging.info(f"Starting Clustering: {len(sel)} reads")
-    try:
-        rep_of, herr, pos, counters, acc_id = cluster(sr, work, sel, args, api, work_dev, T)
-    finally:                                        # sorted.fastq is written whatever the clustering call did (the reference has it on disk before it clusters)
-        deferred, args._deferred = getattr(args, "_deferred", []), []
-        for fn_, a_, kw_ in deferred: _write(args, fn_, *a_, **kw_)
     T["cluster"] = time() - t0; t0 = time()
     logging.debug(f"Time elapsed clustering: {T['cluster']}")
     if getattr(args, "strand_aware", False) and len(sel) == sr.n:

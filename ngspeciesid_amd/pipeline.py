@@ -48,20 +48,20 @@ def select_centers(reps, counts, score, abundance_cutoff):
     return [int(i) for i in idx if counts[i] >= abundance_cutoff]
 
 
-def detect_reverse_complements(api: Api, centers, rc_identity_threshold):
-    """consensus.detect_reverse_complements (consensus.py:148-183): centers = [n_reads, c_id, seq, groups(list of cluster ids)].
-    Identity = matching columns / alignment columns of the semi-global alignment (open 3, ext 1, +2/-2), max over fw / rc."""
-    n = len(centers)
-    if n <= 1:
-        return [[c[0], c[1], c[2], list(c[3])] for c in centers]
-    seqs = [c[2] for c in centers]
-    rcs = [revcomp_str(s) for s in seqs]
-    q = ReadSet.from_strings(seqs); t = ReadSet.from_strings(seqs + rcs)
+def _rc_pairs(n, q0=0, t0=0, rc0=None):
+    """(query, target) index lists of detect_reverse_complements for n centres: every i < j against j forward and j reverse-complemented.  The centres are
+    q0 .. q0+n-1 of the query set, t0 .. of the target set, their reverse complements rc0 .. of the target set."""
+    rc0 = n if rc0 is None else rc0
     qi, ti = [], []
     for i in range(n):
         for j in range(i + 1, n):
-            qi += [i, i]; ti += [j, n + j]
-    score, ncols, nmatch, _ = api.sg_align_batch(q, t, qi, ti, 3, 1, 2, -2, 13, None)
+            qi += [q0 + i, q0 + i]; ti += [t0 + j, rc0 + j]
+    return qi, ti
+
+
+def _rc_decide(centers, ncols, nmatch, rc_identity_threshold):
+    """the decision loop of consensus.detect_reverse_complements (consensus.py:163-183) on the alignment results of _rc_pairs(len(centers))"""
+    n = len(centers)
     ident = {}
     p = 0
     for i in range(n):
@@ -79,6 +79,41 @@ def detect_reverse_complements(api: Api, centers, rc_identity_threshold):
                 if ident[(i, j)] >= rc_identity_threshold:          # NB the reference also re-merges already removed centres
                     merged_n += centers[j][0]; removed.add(centers[j][1]); allg += list(centers[j][3])
         out.append([merged_n, cid, seq, allg])
+    return out
+
+
+def detect_reverse_complements(api: Api, centers, rc_identity_threshold):
+    """consensus.detect_reverse_complements (consensus.py:148-183): centers = [n_reads, c_id, seq, groups(list of cluster ids)].
+    Identity = matching columns / alignment columns of the semi-global alignment (open 3, ext 1, +2/-2), max over fw / rc."""
+    n = len(centers)
+    if n <= 1:
+        return [[c[0], c[1], c[2], list(c[3])] for c in centers]
+    seqs = [c[2] for c in centers]
+    rcs = [revcomp_str(s) for s in seqs]
+    q = ReadSet.from_strings(seqs); t = ReadSet.from_strings(seqs + rcs)
+    qi, ti = _rc_pairs(n)
+    score, ncols, nmatch, _ = api.sg_align_batch(q, t, qi, ti, 3, 1, 2, -2, 13, None)
+    return _rc_decide(centers, ncols, nmatch, rc_identity_threshold)
+
+
+def detect_reverse_complements_samples(api: Api, centers_per_sample, rc_identity_threshold):
+    """detect_reverse_complements for several samples with ONE alignment call: pairs only within a sample, the decision loop per sample"""
+    seqs = [c[2] for cs in centers_per_sample for c in cs]
+    nall = len(seqs)
+    qi, ti, span = [], [], []
+    base = 0
+    for cs in centers_per_sample:
+        n = len(cs)
+        a, b = (_rc_pairs(n, base, base, nall + base) if n > 1 else ([], []))
+        span.append((len(qi), len(qi) + len(a))); qi += a; ti += b
+        base += n
+    ncols = nmatch = None
+    if qi:
+        q = ReadSet.from_strings(seqs); t = ReadSet.from_strings(seqs + [revcomp_str(s) for s in seqs])
+        _, ncols, nmatch, _ = api.sg_align_batch(q, t, qi, ti, 3, 1, 2, -2, 13, None)
+    out = []
+    for cs, (a, b) in zip(centers_per_sample, span):
+        out.append([[c[0], c[1], c[2], list(c[3])] for c in cs] if len(cs) <= 1 else _rc_decide(cs, ncols[a:b], nmatch[a:b], rc_identity_threshold))
     return out
 
 
@@ -165,3 +200,89 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
     res["centers"] = [(m[0], m[1], m[2], polished[i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged)]
     return res
+
+
+POA_BAND64_MAXLEN = 3000       # include/ngsid.h NGSID_POA_BAND64_MAXLEN: band <= 0 means 64 columns iff every read of the call has at most this many bases, else 128
+
+
+def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
+                         rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
+                         p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
+                         strand_aware=False, draft_trim=None, single_below=None):
+    """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
+    run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
+    call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
+    are grouped by the band they would get alone (a sample with a read above POA_BAND64_MAXLEN bases gets 128 columns, the others 64), so at most two consensus
+    and two polishing calls.  strand_aware is not supported here (ValueError)."""
+    if strand_aware:
+        raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
+    tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
+    single_below = SINGLE_BELOW if single_below is None else single_below
+    T = timings if timings is not None else {}
+    so = np.asarray(seg_off, dtype=np.int64); ns = len(so) - 1
+    t0 = time.perf_counter()
+    prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
+    rep_of, herr, status, counters = api.cluster_greedy_segmented(rs, prm, so.astype(np.uint64), acc_rank=acc_rank)
+    T["cluster"] = T.get("cluster", 0.0) + time.perf_counter() - t0
+    out = [dict(rep_of=rep_of[so[s]:so[s + 1]] - np.int32(so[s]), status=status[so[s]:so[s + 1]], counters=counters[s], hpc_err=herr[so[s]:so[s + 1]], centers=[]) for s in range(ns)]
+    if not do_consensus:
+        return out
+    # ---- per-sample cluster tables and selections (local indices), the samples grouped by band
+    t0 = time.perf_counter()
+    if rs.mem == 0:
+        lens = np.diff(rs.off.astype(np.int64))
+    else:
+        kp = rs.keep if isinstance(rs.keep, dict) else {}
+        lens = np.diff(kp["host"].off.astype(np.int64)) if kp.get("host") is not None else np.diff(kp["off"].cpu().numpy().astype(np.int64))
+    tab = [None] * ns
+    for s in range(ns):
+        a0, n = int(so[s]), int(so[s + 1] - so[s])
+        if n == 0:
+            continue
+        reps, order, grp_off, counts = clusters_from_rep(out[s]["rep_of"])
+        sel = select_centers(reps, counts, score[a0:a0 + n], int(abundance_ratio * n))      # NGSpeciesID:65, per sample
+        if sel:
+            bnd = band if band > 0 else (64 if int(lens[a0:a0 + n].max()) <= POA_BAND64_MAXLEN else 128)
+            tab[s] = (reps, order, grp_off, counts, sel, bnd)
+    T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
+    def cluster_reads(s, ci):                                                   # global read numbers of cluster ci of sample s, truncated like run_hot_path does
+        _, order, grp_off = tab[s][:3]
+        a, b = int(grp_off[ci]), int(grp_off[ci + 1])
+        if max_seqs_for_consensus >= 0:
+            b = min(b, a + max_seqs_for_consensus)                              # consensus.py:260
+        return order[a:b].astype(np.int64) + int(so[s])
+    live = [s for s in range(ns) if tab[s] is not None]
+    bands = sorted({tab[s][5] for s in live})
+    # ---- draft consensus: one call per band
+    t0 = time.perf_counter()
+    drafts = {}
+    for bnd in bands:
+        keys = [(s, ci) for s in live if tab[s][5] == bnd for ci in tab[s][4]]
+        parts = [cluster_reads(s, ci) for s, ci in keys]
+        sub_off = np.concatenate(([0], np.cumsum([len(x) for x in parts])))
+        res = api.poa_consensus(rs, sub_off, poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below),
+                                read_order=np.concatenate(parts).astype(np.uint32))
+        drafts.update(zip(keys, res))
+    T["consensus"] = T.get("consensus", 0.0) + time.perf_counter() - t0
+    # ---- reverse-complement detection: one alignment call, pairs within a sample only
+    t0 = time.perf_counter()
+    centers = [[[int(tab[s][3][ci]), int(tab[s][0][ci]), drafts[(s, ci)], [ci]] for ci in tab[s][4]] for s in live]
+    merged = dict(zip(live, detect_reverse_complements_samples(api, centers, rc_identity_threshold)))
+    T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
+    polished = {s: [m[2] for m in merged[s]] for s in live}
+    if do_polish and racon_iter > 0:
+        t0 = time.perf_counter()
+        for bnd in bands:
+            ss = [s for s in live if tab[s][5] == bnd]
+            lists = [l for s in ss for l in pooled_read_lists(merged[s], lambda ci, s=s: cluster_reads(s, ci))]
+            pprm = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
+            p_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
+            pol, _ = api.polish(ReadSet.from_strings([m[2] for s in ss for m in merged[s]]), rs, p_off, pprm, read_order=np.concatenate(lists).astype(np.uint32))
+            x = 0
+            for s in ss:
+                polished[s] = pol[x:x + len(merged[s])]; x += len(merged[s])
+        T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
+    for s in live:
+        reps = tab[s][0]
+        out[s]["centers"] = [(m[0], m[1], m[2], polished[s][i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged[s])]
+    return out
