@@ -45,6 +45,13 @@ class PolishParams(C.Structure):
                 ("aln_match", C.c_int32), ("aln_mismatch", C.c_int32), ("aln_open", C.c_int32), ("aln_ext", C.c_int32), ("trim", C.c_int32), ("aln_mode", C.c_int32), ("stop_when_stable", C.c_int32), ("single_below", C.c_int32)]
 
 
+class SupportParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("clip", C.c_int32)]          # include/ngsid_support.h ngsid_support_params_t
+
+
+SUPPORT_COLUMNS = ("depth", "agree", "A", "C", "G", "T", "del", "ins_after")       # the eight counters per base of Api.consensus_support
+
+
 def cluster_params(k=13, w=20, min_shared=5, min_fraction=0.8, mapped_threshold=0.7, aligned_threshold=0.4,
                    min_prob_no_hits=0.1, symmetric=False, p_shared=None):
     p = ClusterParams()
@@ -578,4 +585,23 @@ class Api:
         seqs = [[out[int(ooff[it * ng + g]):int(ooff[it * ng + g + 1])].tobytes().decode() for g in range(ng)] for it in range(iters)]
         u = used[:n].reshape(iters, ng) if n else used[:0].reshape(0, ng)
         return (seqs, u, rec) if aln else (seqs, u)
+
+    # ---- include/ngsid_support.h
+    def consensus_support(self, centres: ReadSet, rs: ReadSet, grp_off, read_order=None, k=13, w=20, clip=False):
+        """ngsid_consensus_support: per base of every centre how many of its group's reads agree, disagree (and with what), delete or insert ->
+        (counts [total, 8] uint32 in SUPPORT_COLUMNS order, cen_off [n_groups + 1], n_used [n_groups], strand [n_listed] int8: 0, 1, -1 = no shared minimizer).
+        Rows cen_off[g] .. cen_off[g + 1] of counts are centre g.  Grouping as in polish(); clip=True counts a read between its first and last run of 15 equal
+        columns only (the polisher's aln_mode 3).  There is no CPU implementation: a library without the entry point is an error."""
+        if centres.mem != MEM_HOST: raise ValueError("consensus_support takes the centres as a host read set")
+        if not hasattr(self.lib, self.prefix + "consensus_support"):
+            raise NgsidError(-2, "the bound library does not export %sconsensus_support (include/ngsid_support.h): rebuild it from this tree" % self.prefix)
+        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
+        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
+        ng = len(grp_off) - 1
+        cen_off = centres.off.copy(); total = int(cen_off[-1]) if len(cen_off) else 0
+        counts = np.zeros((total, 8), dtype=np.uint32); used = np.zeros(max(ng, 1), dtype=np.uint64); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
+        prm = SupportParams(int(k), int(w), 1 if clip else 0)
+        rc = self._call("consensus_support", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(counts), _p(used), _p(strand))
+        if rc: self._err(rc)
+        return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
 

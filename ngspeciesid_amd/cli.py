@@ -80,6 +80,7 @@ def build_parser():
     p.add_argument('--polish_all_iterations', action='store_true', help='extension: run every --racon_iter iteration even when an iteration returned its input unchanged (the default stops polishing such a cluster: same result, less time)')
     p.add_argument('--poa_single_below', type=int, default=None, help='extension: clusters / polishing windows with fewer sequences than this are aligned as ONE graph in read order (spoa\'s and racon\'s own order) instead of being depth-tiled; 0 = tile everything; default: the library\'s measured threshold (pipeline.SINGLE_BELOW)')
     p.add_argument('--racon_subgraph_layers', action='store_true', help='extension: a polishing layer that does not span its window is aligned globally to the sub-graph between its first and last backbone positions, as racon does, instead of end-free to the whole window graph (default off: the shipped polisher)')
+    p.add_argument('--consensus_support', action='store_true', help='extension: per-base read support of every consensus. Writes racon_cl_id_*/consensus.fastq (header and sequence of consensus.fasta, qualities from the support as Phred+33) and racon_cl_id_*/consensus_support.tsv (pos base depth agree A C G T del ins_after); without --racon, consensus_reference_{id}.fastq and consensus_reference_{id}.support.tsv')
     p.add_argument('--skip_paf', action='store_true', help='extension: do not write racon_cl_id_*/read_alignments_it_{i}.paf (the reference leaves minimap2\'s PAF of every polishing iteration there; default: written)')
     p.set_defaults(which='main')
     sub = p.add_subparsers(help='sub-command help')

@@ -83,6 +83,37 @@ def write_racon_iteration_files(outfolder, name, seqs, used):
         shutil.copyfile(last, os.path.join(outfolder, "consensus.fasta"))
 
 
+def support_phred(counts):
+    """Phred quality per base from the counters of Api.consensus_support ([len, 8]: depth, agree, ...) - the one place the formula lives:
+    Q = min(60, floor(-10 log10((depth - agree + 1) / (depth + 2)))), float64; depth 0 -> 0.  (Add-one smoothing of the disagreeing fraction: a base every one of n
+    reads carries gets -10 log10(1 / (n + 2)), so Q grows with the depth and 60 needs a million agreeing reads.)"""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1, 8)
+    depth, agree = c[:, 0], c[:, 1]
+    q = np.minimum(60.0, np.floor(-10.0 * np.log10((depth - agree + 1.0) / (depth + 2.0))))
+    q[depth == 0] = 0.0
+    return q.astype(np.uint8)
+
+
+def write_support_files(fastq_path, tsv_path, header, seq, counts):
+    """--consensus_support: the consensus as FASTQ (header = the FASTA's without '>', qualities support_phred as Phred+33) and its counters as a table, one line per base
+    (pos is 1-based)."""
+    counts = np.asarray(counts).reshape(-1, 8)
+    if len(counts) != len(seq): raise ValueError("support table of %d rows for a sequence of %d bases" % (len(counts), len(seq)))
+    with open(fastq_path, "w") as f:
+        f.write("@{0}\n{1}\n+\n{2}\n".format(header, seq, (support_phred(counts) + 33).astype(np.uint8).tobytes().decode()))
+    with open(tsv_path, "w") as f:
+        f.write("pos\tbase\tdepth\tagree\tA\tC\tG\tT\tdel\tins_after\n")
+        for i, (b, row) in enumerate(zip(seq, counts.tolist())):
+            f.write("{0}\t{1}\t{2}\n".format(i + 1, b, "\t".join(str(v) for v in row)))
+
+
+def write_support_for_fasta(fasta_path, fastq_path, tsv_path, counts):
+    """write_support_files for the (one) record of a FASTA file that is on disk: same header, same sequence line"""
+    with open(fasta_path) as f:
+        lines = f.read().split("\n")
+    write_support_files(fastq_path, tsv_path, lines[0][1:], lines[1], counts)
+
+
 def highest_aln_identity(seq, seq2, api=None):
     """max identity over forward / reverse-complement semi-global alignments (consensus.py:129-145)."""
     api = api or runtime.get_api()

@@ -21,11 +21,14 @@ typedef unsigned long long u64;
 // (span and window break points), as the oracle does (ongsid_polish, clip_span): what minimap2's chain ends do before racon's edlib call.  One instance only (unbanded,
 // 16-block groups): the mode serves the primer-trimming flow of the CLI, a handful of centres.
 #define CLIP_RUN 15
-template <int BMAX, bool WIN, bool CLIP = false>
+// REC (ngsid_consensus_support): the traceback also RECORDS its path - one nibble per target position into the pair's row of `rec` (layout and codes: ngsid_internal.h), packed in a
+// register and stored as a dword per 8 positions.  The instances without REC are unchanged; only ngsid_launch_ed_align_rec launches the ones with it.
+template <int BMAX, bool WIN, bool CLIP = false, bool REC = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
 void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-byte units */, uint32_t mstride, uint32_t* __restrict__ work_ctr, int32_t* __restrict__ dist_out,
                 int8_t* __restrict__ hcar /* per wave mstride x 64: horizontal delta below the last block of a block group */,
-                int bandK /* > 0: Ukkonen band for distances <= bandK (single block group only) */, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ fail_count)
+                int bandK /* > 0: Ukkonen band for distances <= bandK (single block group only) */, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ fail_count,
+                uint32_t* __restrict__ rec /* REC only */, uint32_t rec_stride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -183,6 +186,9 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
         const int W = J.window > 0 ? J.window : 0x7fffffff;
         int cw = -1, w_qf = 0, w_ql = 0, w_tf = 0, w_tl = 0;
         int c_run = 0, c_x0q = -1, c_x0t = -1; bool c_started = false;       // CLIP state (unused otherwise)
+        uint32_t r_acc = 0; int r_w = -1;                                    // REC state (unused otherwise): the dword being packed and its index in the row
+        uint32_t* myrec = (REC && have) ? rec + p * (u64)rec_stride : nullptr;
+        auto rec_put = [&](int ti, uint32_t nib) { const int w_ = ti >> 3; if (w_ != r_w) { if (r_w >= 0) myrec[r_w] = r_acc; r_acc = 0; r_w = w_; } r_acc |= nib << ((ti & 7) * 4); };
         int wsn = j > 0 ? (j - 1) / W : 0, ws = wsn * W;       // window of the current target position, tracked without divisions
         // The lanes walk their paths IN LOCKSTEP OVER THE TARGET COLUMNS (round 3): in round jj every lane whose path stands in column jj handles that column (any
         // number of vertical moves, then one diagonal or horizontal move), so the 64 loads of a round go to the same column - one or two coalesced KB instead of
@@ -212,6 +218,7 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
             }
             if (on) {
                 { const int nb = tb_blk(i, jj - 1); if (nb != wb) { w = tb_load(nb, jj - 1); wb = nb; } }
+                uint32_t r_ins = 0;                                                            // REC: the path made vertical moves in this column (query-only columns behind target position jj - 1)
                 for (;;) {
                     const int bit = (i - 1) & 63;
                     const u64 dv = ((u64)w.y << 32) | w.x, uv = ((u64)w.w << 32) | w.z;
@@ -243,17 +250,23 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
                                 if (c_run >= CLIP_RUN) { c_x0q = qi0; c_x0t = ti0; }        // inside a long run: the earliest such column so far
                             }
                         } else record(qi0, ti0);
+                        if constexpr (REC) {
+                            const int cq = ngsid_bcode(q[qi0]), ct = ngsid_bcode(t[ti0]);
+                            rec_put(ti0, (cq < 4 ? (cq == ct ? (uint32_t)NGSID_REC_EQ : (uint32_t)NGSID_REC_SUB + cq) : (uint32_t)NGSID_REC_OTHER) | r_ins);
+                        }
                         --i; --j; break;
                     }
                     if constexpr (CLIP) c_run = 0;                                              // a gap column ends a run
-                    if (!up) { --j; break; }
+                    if (!up) { if constexpr (REC) rec_put(j - 1, (uint32_t)NGSID_REC_DEL | r_ins); --j; break; }
                     --i;
+                    if constexpr (REC) r_ins = NGSID_REC_INS;
                     if (i == 0) break;
                     { const int nb = tb_blk(i, jj - 1); if (nb != wb) { w = tb_load(nb, jj - 1); wb = nb; } }
                 }
             }
         }
         i = 0;
+        if constexpr (REC) { if (r_w >= 0) myrec[r_w] = r_acc; }
         if (bpp && ok && cw >= 0 && cw < J.bp_windows) { bpp[cw * 4 + 0] = w_qf; bpp[cw * 4 + 1] = w_ql; bpp[cw * 4 + 2] = w_tf; bpp[cw * 4 + 3] = w_tl; }
         if constexpr (CLIP) {
             if (have && ok && c_started) {      // head side: everything in front of the first run of CLIP_RUN equal columns goes
@@ -284,8 +297,9 @@ static int32_t ed_reserve(ngsid_ctx* ctx, u64& want, u64 per_wave)
     }
 }
 
-template <int BMAX, bool WIN = false, bool CLIP = false>
-static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, uint32_t ctr_slot = 14, int bandK = 0, uint32_t fail_slot = 15, uint32_t* fail_list = nullptr)
+struct EdRec { uint32_t* p = nullptr; uint32_t stride = 0; };       // REC instances: the path matrix
+template <int BMAX, bool WIN = false, bool CLIP = false, bool REC = false>
+static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, uint32_t ctr_slot = 14, int bandK = 0, uint32_t fail_slot = 15, uint32_t* fail_list = nullptr, EdRec rec = EdRec())
 {
     const u64 nbundles = (job.npairs + 63) / 64;
     const uint32_t mstride = (max_tlen + 63u) & ~63u;                     // rounded so that backbones growing by a few bases between iterations reuse the scratch
@@ -293,7 +307,7 @@ static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen,
     const u64 per_wave = nblocks * mstride * 64;                           // 16-byte units
     const size_t lds = (size_t)BMAX * 3 * 64 * 8 + (size_t)ngsid_opt(ctx, "ed_lds_pad_kb", 0) * 1024;      // (dev option: extra LDS per wave = fewer resident waves, for occupancy measurements)
     int occ = 0;
-    HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_ed_align<BMAX, WIN, CLIP>, 64, lds));
+    HIPCHK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_ed_align<BMAX, WIN, CLIP, REC>, 64, lds));
     if (occ < 1) occ = 1;
     u64 want = std::min<u64>(nbundles, (u64)occ * ctx->n_cu);
     const u64 by_mem = std::max<u64>(1, std::min<size_t>((size_t)24 << 30, ctx->scratch_budget) / (per_wave * 16));
@@ -302,8 +316,8 @@ static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen,
     if (ctx->ed_h.n < want * (u64)mstride * 64) HIPCHK(ctx, ctx->ed_h.reserve(want * (u64)mstride * 64));
     if (ctx->aln_ctr.n < 16) HIPCHK(ctx, ctx->aln_ctr.alloc(16));
     HIPCHK(ctx, hipMemsetAsync(ctx->aln_ctr.p + ctr_slot, 0, sizeof(uint32_t), ctx->stream));
-    { ProfScope ps_(ctx, "k_ed_align"); hipLaunchKernelGGL((k_ed_align<BMAX, WIN, CLIP>), dim3((unsigned)want), dim3(64), lds, ctx->stream, job, ctx->ed_tb.p, per_wave, mstride, ctx->aln_ctr.p + ctr_slot, dist_out, ctx->ed_h.p,
-                                                            bandK, fail_list ? fail_list : ctx->ed_fail.p, ctx->aln_ctr.p + fail_slot); }
+    { ProfScope ps_(ctx, REC ? "k_ed_align_rec" : "k_ed_align"); hipLaunchKernelGGL((k_ed_align<BMAX, WIN, CLIP, REC>), dim3((unsigned)want), dim3(64), lds, ctx->stream, job, ctx->ed_tb.p, per_wave, mstride, ctx->aln_ctr.p + ctr_slot, dist_out, ctx->ed_h.p,
+                                                            bandK, fail_list ? fail_list : ctx->ed_fail.p, ctx->aln_ctr.p + fail_slot, rec.p, rec.stride); }
     HIPCHK(ctx, hipGetLastError());
     return NGSID_OK;
 }
@@ -311,23 +325,26 @@ static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen,
 // pairs whose distance exceeded the band of the first launch (list ctx->ed_fail, count aln_ctr[15]): unbanded.  With retryK > 0 (class launches with a band of at most
 // 150) they first run in the sliding-window instance with that wider band - half the blocks per column of the unbanded instance, and a handful of pairs costs the
 // latency of ONE pair - and only what exceeds it too (list ctx->ed_fail2, count aln_ctr[7]) runs unbanded.
-static int32_t launch_ed_fallback(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, int retryK = 0)
+template <bool REC>
+static int32_t launch_ed_fallback(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, int retryK, EdRec rec)
 {
     AlignJob j = job; j.pair_list = ctx->ed_fail.p; j.npairs_dev = ctx->aln_ctr.p + 15; j.pair_list2 = nullptr; j.npairs_dev2 = nullptr;
     if (retryK > 0) {
         HIPCHK(ctx, ctx->ed_fail2.reserve(job.npairs));
-        int32_t rc = launch_ed<8, true>(ctx, j, max_qlen, max_tlen, dist_out, 6, retryK, 7, ctx->ed_fail2.p);
+        int32_t rc = launch_ed<8, true, false, REC>(ctx, j, max_qlen, max_tlen, dist_out, 6, retryK, 7, ctx->ed_fail2.p, rec);
         if (rc) return rc;
         j.pair_list = ctx->ed_fail2.p; j.npairs_dev = ctx->aln_ctr.p + 7;
     }
-    return launch_ed<16>(ctx, j, max_qlen, max_tlen, dist_out, 13, 0);
+    return launch_ed<16, false, false, REC>(ctx, j, max_qlen, max_tlen, dist_out, 13, 0, 15, nullptr, rec);
 }
 
-int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out)
+// the routing of a batch to the instances, shared by the plain (REC = false) and the path-recording call
+template <bool REC>
+static int32_t ed_align_route(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, EdRec rec)
 {
     if (job.npairs == 0) return NGSID_OK;
     if (max_qlen > NGSID_MAX_CONSENSUS_LEN || max_tlen > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "sequence longer than %d in the edit-distance aligner", NGSID_MAX_CONSENSUS_LEN);
-    if (job.clip) return launch_ed<16, false, true>(ctx, job, max_qlen, max_tlen, dist_out, 14, 0);      // overlap-span clipping (aln_mode 3): the one CLIP instance, unbanded
+    if (job.clip) return launch_ed<16, false, true, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, 0, 15, nullptr, rec);      // overlap-span clipping (aln_mode 3): the one CLIP instance, unbanded
     // band: wide enough for the usual read-to-draft distance, pairs beyond it take the unbanded launch (the result does not depend on it)
     int bandK = 64 + (int)(max_qlen / 32);
     const bool band_set = ngsid_opt(ctx, "ed_band", -1) >= 0;
@@ -352,8 +369,8 @@ int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
             u64 w2 = want; { int32_t rr = ed_reserve(ctx, w2, per_wave); if (rr) return rr; }
             if (ctx->ed_h.n < w2 * (u64)mstride * 64) HIPCHK(ctx, ctx->ed_h.reserve(w2 * (u64)mstride * 64));
         }
-        if ((rc = launch_ed<4>(ctx, cls(0, 256), std::min<uint32_t>(max_qlen, 256), max_tlen, dist_out, 1, bandK))) return rc;
-        if (max_qlen > 256 && (rc = launch_ed<8>(ctx, cls(1, 512), std::min<uint32_t>(max_qlen, 512), max_tlen, dist_out, 2, bandK))) return rc;
+        if ((rc = launch_ed<4, false, false, REC>(ctx, cls(0, 256), std::min<uint32_t>(max_qlen, 256), max_tlen, dist_out, 1, bandK, 15, nullptr, rec))) return rc;
+        if (max_qlen > 256 && (rc = launch_ed<8, false, false, REC>(ctx, cls(1, 512), std::min<uint32_t>(max_qlen, 512), max_tlen, dist_out, 2, bandK, 15, nullptr, rec))) return rc;
         // 513-768 bases: the 8-block window instance as well (12 KB of LDS per wave instead of 18 KB: three waves per SIMD instead of two, -8 %);
         // NGSID_ED_WIN_ALL=0 selects the 12-block instance with all blocks resident
         const bool win_all = ngsid_opt(ctx, "ed_win_all", 1) != 0;
@@ -366,22 +383,34 @@ int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
             // a band of up to ~100 fits a window of SIX blocks (9 KB of LDS and 12 state registers less per wave: four waves per SIMD instead of three); a bundle
             // whose length spread needs more (span check in the kernel) goes to the retry launch
             const bool win6 = win2 && bandK <= 100 && ngsid_opt(ctx, "ed_win6", 1) != 0;
-            if ((rc = win6 ? launch_ed<6, true>(ctx, j2, std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 3, bandK)
-                    : win2 ? launch_ed<8, true>(ctx, j2, std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 3, bandK)
-                           : launch_ed<12>(ctx, j2, std::min<uint32_t>(max_qlen, 768), max_tlen, dist_out, 3, bandK))) return rc;
+            if ((rc = win6 ? launch_ed<6, true, false, REC>(ctx, j2, std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 3, bandK, 15, nullptr, rec)
+                    : win2 ? launch_ed<8, true, false, REC>(ctx, j2, std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 3, bandK, 15, nullptr, rec)
+                           : launch_ed<12, false, false, REC>(ctx, j2, std::min<uint32_t>(max_qlen, 768), max_tlen, dist_out, 3, bandK, 15, nullptr, rec))) return rc;
         }
-        if (max_qlen > 768 && !win2 && (rc = launch_ed<16>(ctx, cls(3, 896), std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 4, bandK))) return rc;
-        if (max_qlen > 896 && (rc = win16 ? launch_ed<16, true>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK) : win ? launch_ed<8, true>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK) : launch_ed<16>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK))) return rc;
-        return bandK > 0 ? launch_ed_fallback(ctx, job, max_qlen, max_tlen, dist_out, win2 ? 180 : 0) : NGSID_OK;
+        if (max_qlen > 768 && !win2 && (rc = launch_ed<16, false, false, REC>(ctx, cls(3, 896), std::min<uint32_t>(max_qlen, 896), max_tlen, dist_out, 4, bandK, 15, nullptr, rec))) return rc;
+        if (max_qlen > 896 && (rc = win16 ? launch_ed<16, true, false, REC>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK, 15, nullptr, rec) : win ? launch_ed<8, true, false, REC>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK, 15, nullptr, rec) : launch_ed<16, false, false, REC>(ctx, cls(4, 0), max_qlen, max_tlen, dist_out, 5, bandK, 15, nullptr, rec))) return rc;
+        return bandK > 0 ? launch_ed_fallback<REC>(ctx, job, max_qlen, max_tlen, dist_out, win2 ? 180 : 0, rec) : NGSID_OK;
     }
     if (bandK > 0) HIPCHK(ctx, hipMemsetAsync(ctx->aln_ctr.p + 15, 0, sizeof(uint32_t), ctx->stream));
     int32_t rc;
-    if (max_qlen <= 256) rc = launch_ed<4>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);
-    else if (max_qlen <= 512) rc = launch_ed<8>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);
-    else if (max_qlen <= 768) rc = launch_ed<12>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);
-    else if (win16) rc = launch_ed<16, true>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);
-    else if (win) rc = launch_ed<8, true>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);
-    else rc = launch_ed<16>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK);          // longer queries: groups of 16 blocks, horizontal deltas carried through HBM
+    if (max_qlen <= 256) rc = launch_ed<4, false, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);
+    else if (max_qlen <= 512) rc = launch_ed<8, false, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);
+    else if (max_qlen <= 768) rc = launch_ed<12, false, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);
+    else if (win16) rc = launch_ed<16, true, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);
+    else if (win) rc = launch_ed<8, true, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);
+    else rc = launch_ed<16, false, false, REC>(ctx, job, max_qlen, max_tlen, dist_out, 14, bandK, 15, nullptr, rec);          // longer queries: groups of 16 blocks, horizontal deltas carried through HBM
     if (rc || bandK <= 0) return rc;
-    return launch_ed_fallback(ctx, job, max_qlen, max_tlen, dist_out);
+    return launch_ed_fallback<REC>(ctx, job, max_qlen, max_tlen, dist_out, 0, rec);
+}
+
+int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out)
+{
+    return ed_align_route<false>(ctx, job, max_qlen, max_tlen, dist_out, EdRec());
+}
+
+int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride)
+{
+    if (!rec || !job.span || (uint64_t)stride * 8 < max_tlen) NGSID_FAIL(ctx, NGSID_ERR_ARG, "internal: path matrix of the edit-distance aligner missing or too narrow");
+    EdRec r; r.p = rec; r.stride = stride;
+    return ed_align_route<true>(ctx, job, max_qlen, max_tlen, nullptr, r);
 }

@@ -1,0 +1,153 @@
+// k_support.hip - ngsid_consensus_support (include/ngsid_support.h): per base of every centre, how many reads agree, disagree (and with what), delete or insert.
+//
+// Two passes.  STORE: the polisher's edit-distance aligner with the path recorded (k_ed_align<.., REC>, k_ed_align.hip) writes one nibble per (read, centre position) into
+// a [read][centre position] matrix - 0.5 B per cell, a dword store per lane and 8 columns.  SUM (k_support_sum, below): lanes over centre positions (8 lanes share a dword,
+// 256 lanes read 128 consecutive bytes of a row), a workgroup takes a slice of ONE group's reads, keeps the eight counters of its position in registers and adds them once
+// per (workgroup, position) with atomicAdd on uint32.  The traceback itself never touches the counters: its 64 lanes walk 64 reads of the same centre in near lockstep, so
+// every step would be 64 atomics on one address.  Integer adds commute: the result does not depend on the schedule.
+#include "ngsid_internal.h"
+#include "../../include/ngsid_support.h"
+#include <algorithm>
+
+typedef unsigned long long u64;
+
+#define SUPPORT_TILE 256        // centre positions per workgroup (= threads)
+#define SUPPORT_SLICE 1024      // reads per workgroup
+
+__global__ __launch_bounds__(SUPPORT_TILE)
+void k_support_sum(const uint32_t* __restrict__ rec, uint32_t stride, const int32_t* __restrict__ span /* per pair {q_begin, q_end, t_begin, t_end}, -1 = no counted column */,
+                   const uint32_t* __restrict__ items /* [n][3]: group, first pair, end pair (pairs of this chunk) */, const uint64_t* __restrict__ cen_off,
+                   uint32_t* __restrict__ counts, u64* __restrict__ n_used)
+{
+    const uint32_t g = items[blockIdx.x * 3], p0 = items[blockIdx.x * 3 + 1], p1 = items[blockIdx.x * 3 + 2];
+    if (blockIdx.y == 0) {              // reads of the slice that counted at least one column
+        unsigned used = 0;
+        for (uint32_t p = p0 + threadIdx.x; p < p1; p += SUPPORT_TILE) used += span[(u64)p * 4 + 2] >= 0;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) used += __shfl_xor(used, d);
+        if ((threadIdx.x & 63) == 0 && used) atomicAdd(n_used + g, (u64)used);
+    }
+    const int m = (int)(cen_off[g + 1] - cen_off[g]);
+    const int b = (int)(blockIdx.y * SUPPORT_TILE + threadIdx.x);
+    if (b >= m) return;
+    const uint32_t* col = rec + (b >> 3); const int sh = (b & 7) * 4;
+    uint32_t depth = 0, agree = 0, sa = 0, sc = 0, sg = 0, st = 0, del = 0, ins = 0;
+#pragma unroll 4
+    for (uint32_t p = p0; p < p1; ++p) {
+        const int tb = span[(u64)p * 4 + 2], te = span[(u64)p * 4 + 3];          // (uniform: one scalar load per read)
+        if (b < tb || b > te) continue;                                            // outside the counted columns of this read (tb = te = -1: none)
+        const uint32_t nib = (col[(u64)p * stride] >> sh) & 15u, code = nib & 7u;
+        depth += code != 0; agree += code == NGSID_REC_EQ;
+        sa += code == NGSID_REC_SUB; sc += code == NGSID_REC_SUB + 1; sg += code == NGSID_REC_SUB + 2; st += code == NGSID_REC_SUB + 3;
+        del += code == NGSID_REC_DEL;
+        ins += (nib >> 3) & (uint32_t)(b < te);                                    // a run behind the LAST counted column is not counted
+    }
+    uint32_t* out = counts + (cen_off[g] + (u64)b) * NGSID_SUPPORT_NCOUNT;
+    if (depth) atomicAdd(out + NGSID_SUPPORT_DEPTH, depth);
+    if (agree) atomicAdd(out + NGSID_SUPPORT_AGREE, agree);
+    if (sa) atomicAdd(out + NGSID_SUPPORT_SUB_A, sa);
+    if (sc) atomicAdd(out + NGSID_SUPPORT_SUB_A + 1, sc);
+    if (sg) atomicAdd(out + NGSID_SUPPORT_SUB_A + 2, sg);
+    if (st) atomicAdd(out + NGSID_SUPPORT_SUB_A + 3, st);
+    if (del) atomicAdd(out + NGSID_SUPPORT_DEL, del);
+    if (ins) atomicAdd(out + NGSID_SUPPORT_INS, ins);
+}
+
+extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order,
+                                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_support_params_t* prm,
+                                           uint32_t* counts, uint64_t* n_used, int8_t* strand)
+{
+    ApiClock api_clock_(ctx, "consensus_support");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (!centres || !reads || !grp_off || !prm) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    if (centres->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one centre per group expected");
+    if (prm->clip != 0 && prm->clip != 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_support_params_t.clip must be 0 or 1");
+    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
+    const uint64_t N = RD.n, NL = grp_off[n_groups]; const uint32_t G = (uint32_t)n_groups;
+    if (!read_order && NL > N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
+    if (read_order) for (uint64_t x = 0; x < NL; ++x) if (read_order[x] >= N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
+    // centres to host strings (the strand detection takes them like the polisher's backbones)
+    std::vector<std::string> B(G); std::vector<uint64_t> boff(G + 1, 0); std::vector<uint8_t> bseq;
+    if (G) {
+        if (centres->mem == NGSID_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpy(boff.data(), centres->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
+            if (boff[G]) HIPCHK(ctx, hipMemcpy(bseq.data(), centres->seq, boff[G], hipMemcpyDeviceToHost));
+        } else { memcpy(boff.data(), centres->off, 8 * (G + 1)); bseq.assign(centres->seq, centres->seq + boff[G]); bseq.push_back(0); }
+    }
+    const uint64_t total = boff[G]; uint32_t maxb = 0;
+    for (uint32_t g = 0; g < G; ++g) { B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g])); maxb = std::max<uint32_t>(maxb, (uint32_t)B[g].size()); }
+    if (total && !counts) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null counts");
+    if (counts) memset(counts, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total);
+    if (n_used) for (uint32_t g = 0; g < G; ++g) n_used[g] = 0;
+    if (strand) for (uint64_t x = 0; x < NL; ++x) strand[x] = -1;
+    if (maxb > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "centre longer than %d", NGSID_MAX_CONSENSUS_LEN);
+    // ---- read -> group map
+    std::vector<uint32_t> h_rgroup(N, 0xffffffffu);
+    for (uint32_t g = 0; g < G; ++g) for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
+        const uint64_t r = read_order ? read_order[x] : x;
+        if (h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): list every read under one centre", (unsigned long long)r, h_rgroup[r], g);
+        h_rgroup[r] = g;
+    }
+    if (N == 0 || G == 0 || NL == 0) return NGSID_OK;
+    // ---- strand + oriented reads: the polisher's first stage
+    OrientBufs ob; static thread_local PinVec<uint8_t> h_orient;
+    rc = ngsid_polish_orient(ctx, RD, B, h_rgroup, prm->k, prm->w, ob, h_orient); if (rc) return rc;
+    // ---- pairs in list order (group by group); pairs [gbeg[g], gbeg[g+1]) are group g's
+    static thread_local PinVec<uint32_t> pair_read, pair_group; pair_read.clear(); pair_group.clear();
+    std::vector<uint64_t> gbeg(G + 1, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
+            const uint64_t r = read_order ? read_order[x] : x;
+            if (h_orient[r] == 255) continue;
+            pair_read.push_back((uint32_t)r); pair_group.push_back(g); if (strand) strand[x] = (int8_t)h_orient[r];
+        }
+        gbeg[g + 1] = pair_read.size();
+    }
+    const uint64_t NP = pair_read.size();
+    if (NP == 0 || total == 0) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return NGSID_OK; }
+    DevBuf<uint32_t> d_pair_read, d_pair_group, d_counts, d_items, d_rec; DevBuf<int32_t> d_span; DevBuf<u64> d_used;
+    HIPCHK(ctx, d_pair_read.alloc(NP)); HIPCHK(ctx, d_pair_group.alloc(NP)); HIPCHK(ctx, d_counts.alloc(total * NGSID_SUPPORT_NCOUNT)); HIPCHK(ctx, d_used.alloc(G));
+    HIPCHK(ctx, hipMemcpyAsync(d_pair_read.p, pair_read.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_pair_group.p, pair_group.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_counts.p, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(d_used.p, 0, sizeof(u64) * G, ctx->stream));
+    ngsid_reads_t br{bseq.data(), nullptr, boff.data(), G, NGSID_MEM_HOST, 0};
+    DevReads BB; rc = ngsid_upload_reads(ctx, &br, &BB, false); if (rc) return rc;
+    // ---- chunks of pairs under the byte budget of the path matrix (the share of the free device memory the POA batches take; option "support_budget_mb")
+    const uint32_t stride = ((maxb + 63u) & ~63u) / 8;                    // dwords per row
+    size_t budget = 0;
+    { const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
+      if (mb > 0) budget = (size_t)mb << 20;
+      else { size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)16 << 30;
+             budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (3 * (size_t)ngsid_pool_contexts()), (size_t)256 << 20), (size_t)16 << 30); } }
+    const uint64_t rows = std::min<uint64_t>(NP, std::max<uint64_t>(64, budget / ((size_t)stride * 4)));
+    HIPCHK(ctx, d_rec.alloc(rows * stride)); HIPCHK(ctx, d_span.alloc(rows * 4));
+    std::vector<uint32_t> items;
+    for (uint64_t c0 = 0; c0 < NP; c0 += rows) {
+        const uint64_t c1 = std::min(NP, c0 + rows);
+        AlignJob J{};
+        J.qseq = ctx->pol_oseq.p; J.qoff = RD.off; J.tseq = BB.seq; J.toff = BB.off; J.qidx = d_pair_read.p + c0; J.tidx = d_pair_group.p + c0; J.npairs = c1 - c0;
+        J.span = d_span.p; J.clip = prm->clip;
+        rc = ngsid_launch_ed_align_rec(ctx, J, RD.maxlen, maxb, d_rec.p, stride); if (rc) return rc;
+        items.clear();
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint64_t a = std::max(gbeg[g], c0), e = std::min(gbeg[g + 1], c1);
+            if (B[g].empty()) continue;
+            for (uint64_t s = a; s < e; s += SUPPORT_SLICE) { items.push_back(g); items.push_back((uint32_t)(s - c0)); items.push_back((uint32_t)(std::min(e, s + SUPPORT_SLICE) - c0)); }
+        }
+        if (items.empty()) continue;
+        HIPCHK(ctx, d_items.reserve(items.size()));
+        HIPCHK(ctx, hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, ctx->stream));
+        { ProfScope ps_(ctx, "k_support_sum");
+          hipLaunchKernelGGL(k_support_sum, dim3((unsigned)(items.size() / 3), (maxb + SUPPORT_TILE - 1) / SUPPORT_TILE), dim3(SUPPORT_TILE), 0, ctx->stream,
+                             d_rec.p, stride, d_span.p, d_items.p, BB.off, d_counts.p, d_used.p); }
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `items` is pageable and refilled by the next chunk
+    }
+    std::vector<u64> h_used(G);
+    HIPCHK(ctx, hipMemcpyAsync(counts, d_counts.p, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(h_used.data(), d_used.p, sizeof(u64) * G, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_used) for (uint32_t g = 0; g < G; ++g) n_used[g] = h_used[g];
+    return NGSID_OK;
+}

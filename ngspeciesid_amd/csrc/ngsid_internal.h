@@ -206,6 +206,14 @@ bool ngsid_align16_applicable(const AlignJob& job, uint32_t max_qlen, uint32_t m
 int32_t ngsid_partition_pairs(ngsid_ctx* ctx, const AlignJob& job, uint32_t long_len = 0);      // query-length classes {<=256, <=512, <=768, <=896, rest}: lists in ctx->aln_cls, counts in ctx->aln_ctr[8..12]
 int32_t ngsid_side_streams(ngsid_ctx* ctx);          // creates ctx->side / events on first use
 int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out);   // k_ed_align.hip (uses qseq..npairs, bp, bp_windows, window, span)
+// The same alignments with the PATH of every pair recorded (ngsid_consensus_support, k_support.hip): row p of rec ([npairs][stride] dwords, stride >= ceil(max_tlen / 8)) receives one nibble
+// per target position the path of pair p passes, position t in bits 4 * (t & 7) of dword t >> 3: bits 0-2 = the column that consumes t (NGSID_REC_*), bit 3 = query-only columns follow it
+// directly.  Positions the path does not pass are left unwritten: read a row only inside the pair's span (job.span is required).
+int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride);
+enum { NGSID_REC_EQ = 1, NGSID_REC_SUB = 2 /* + code of the read's letter (A C G T) */, NGSID_REC_OTHER = 6 /* mismatch, read letter outside ACGT */, NGSID_REC_DEL = 7, NGSID_REC_INS = 8 };
+// poa_host.hip: first stage of ngsid_polish (strand by shared HPC minimizers + oriented copies of the reads in ctx->pol_oseq / pol_oqual); S keeps its device temporaries alive for the caller
+struct OrientBufs { DevBuf<uint32_t> d_rgroup; DevBuf<double> herr, rawerr; DevBuf<uint8_t> d_orient; };
+int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vector<std::string>& B, const std::vector<uint32_t>& h_rgroup, int k, int w, OrientBufs& S, PinVec<uint8_t>& h_orient);
 
 typedef unsigned int ngsid_v4u __attribute__((ext_vector_type(4)));
 // 16-byte load served by L2 (nt): for scratch that this wave rewrites between uses, where an L1 line could be stale

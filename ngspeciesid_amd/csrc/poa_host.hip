@@ -819,55 +819,17 @@ extern "C" int32_t ngsid_polish_trace_aln(ngsid_ctx* ctx, const ngsid_reads_t* b
     return polish_trace_impl(ctx, backbones, reads, read_order, grp_off, n_groups, prm, it_off, it_out, it_cap, needed, it_used, it_aln);
 }
 
-static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                           uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used, PolishTrace* trace)
+// First stage of ngsid_polish, shared with ngsid_consensus_support (k_support.hip): the strand of every read against the backbone B[g] of its group h_rgroup[r] (h_orient: 0 forward,
+// 1 reverse complement, 255 = in no group or no shared minimizer) and the oriented copies of the reads in ctx->pol_oseq / pol_oqual (k_orient, in flight on the stream at return).
+int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vector<std::string>& B, const std::vector<uint32_t>& h_rgroup, int k, int w, OrientBufs& S, PinVec<uint8_t>& h_orient)
 {
-    if (!ctx) return NGSID_ERR_ARG;
-    if (!backbones || !reads || !grp_off || !prm || !out_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    if (backbones->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one backbone per group expected");
-    HostTimer ht(ctx->stream, "polish");
-    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
-    if (!read_order && grp_off[n_groups] > RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
-    if (read_order) for (uint64_t x = 0; x < grp_off[n_groups]; ++x) if (read_order[x] >= RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
-    const uint64_t N = RD.n; const uint32_t G = (uint32_t)n_groups;
-    const int W = prm->window > 0 ? prm->window : 500;
-    ht.mark("upload + checks");
-    // backbones to host strings (they are tiny and are rebuilt on the host after every iteration)
-    std::vector<std::string> B(G);
-    {
-        std::vector<uint64_t> boff(G + 1); std::vector<uint8_t> bseq;
-        if (backbones->mem == NGSID_MEM_DEVICE) {
-            HIPCHK(ctx, hipMemcpy(boff.data(), backbones->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
-            if (boff[G]) HIPCHK(ctx, hipMemcpy(bseq.data(), backbones->seq, boff[G], hipMemcpyDeviceToHost));
-        } else { memcpy(boff.data(), backbones->off, 8 * (G + 1)); bseq.assign(backbones->seq, backbones->seq + boff[G]); bseq.push_back(0); }
-        for (uint32_t g = 0; g < G; ++g) B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g]));
-    }
-    if (N == 0 || G == 0) {
-        uint64_t total = 0; out_off[0] = 0; bool ovf = false;
-        for (uint32_t g = 0; g < G; ++g) { if (trace) {} else if (total + B[g].size() <= out_cap && out) memcpy(out + total, B[g].data(), B[g].size()); else if (B[g].size()) ovf = true; total += B[g].size(); out_off[g + 1] = total; if (n_used) n_used[g] = 0; }
-        if (trace) for (int it = 0; it < prm->iters; ++it) for (uint32_t g = 0; g < G; ++g) { trace->seq.push_back(B[g]); trace->used.push_back(0); }
-        if (trace && trace->aln) for (uint64_t x = 0; x < (uint64_t)prm->iters * grp_off[n_groups] * 6; ++x) trace->aln[x] = -1;
-        if (needed) *needed = total; if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "output buffer too small"); return NGSID_OK;
-    }
-    // ---- read -> group map, mean read length per group (TGS/NGS window type)
-    std::vector<uint32_t> h_rgroup(N, 0xffffffffu); std::vector<uint8_t> tgs(G, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        double tot = 0; const uint64_t ns = grp_off[g + 1] - grp_off[g];
-        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-            const uint64_t r = read_order ? read_order[x] : x;
-            if (h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): strand and layers are kept per read, list every read under one backbone", (unsigned long long)r, h_rgroup[r], g);
-            h_rgroup[r] = g; tot += (double)(RD.h_off[r + 1] - RD.h_off[r]);
-        }
-        tgs[g] = ns > 0 && (tot / (double)ns) > 1000.0;
-    }
-    ht.mark("group map");
+    const uint64_t N = RD.n; const uint32_t G = (uint32_t)B.size(); int32_t rc;
     // ---- strand detection (replaces minimap2's strand call): shared HPC minimizers with the initial backbone, fw vs rc
-    DevBuf<uint64_t>& mzcode = ctx->pol_mzcode; DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen; DevBuf<uint32_t> d_rgroup; DevBuf<double> herr, rawerr; DevBuf<uint8_t> d_orient; DevBuf<int> flag;
-    HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N)); HIPCHK(ctx, flag.alloc(1));
+    DevBuf<uint64_t>& mzcode = ctx->pol_mzcode; DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen; DevBuf<uint32_t>& d_rgroup = S.d_rgroup; DevBuf<double>& herr = S.herr; DevBuf<double>& rawerr = S.rawerr; DevBuf<uint8_t>& d_orient = S.d_orient;
+    HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N));
     HIPCHK(ctx, d_rgroup.alloc(N)); HIPCHK(ctx, d_orient.alloc(N));
     HIPCHK(ctx, hipMemcpyAsync(d_rgroup.p, h_rgroup.data(), 4 * N, hipMemcpyHostToDevice, ctx->stream));
-    const int sk = std::min(prm->k, 21), sw = std::max(prm->w, sk);       // strand detection only needs SOME minimizer scheme: one-word codes, comparable between the two launches
+    const int sk = std::min(k, 21), sw = std::max(w, sk);       // strand detection only needs SOME minimizer scheme: one-word codes, comparable between the two launches
     {   // the clustering call that preceded this one left the minimizers of the same reads in the context (same bases, offsets, k, w): reuse them
         bool hit = false;
         if (ctx->mzc.valid && ctx->mzc.n == N && ctx->mzc.total == RD.total && ctx->mzc.k == sk && ctx->mzc.w == sw) {
@@ -911,13 +873,62 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    static thread_local PinVec<uint8_t> h_orient; h_orient.resize(N);
+    h_orient.resize(N);
     HIPCHK(ctx, hipMemcpyAsync(h_orient.data(), d_orient.p, N, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ht.mark("minimizers + strand");
     // ---- oriented copies of the reads
     DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual; HIPCHK(ctx, oseq.reserve(RD.total + 16)); if (RD.qual) HIPCHK(ctx, oqual.reserve(RD.total + 16));
     { ProfScope ps_(ctx, "k_orient"); hipLaunchKernelGGL(k_orient, dim3((unsigned)N), dim3(128), 0, ctx->stream, RD.seq, RD.qual, RD.off, N, d_orient.p, oseq.p, RD.qual ? oqual.p : nullptr); }
     HIPCHK(ctx, hipGetLastError());
+    return NGSID_OK;
+}
+
+static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
+                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
+                           uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used, PolishTrace* trace)
+{
+    if (!ctx) return NGSID_ERR_ARG;
+    if (!backbones || !reads || !grp_off || !prm || !out_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    if (backbones->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one backbone per group expected");
+    HostTimer ht(ctx->stream, "polish");
+    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
+    if (!read_order && grp_off[n_groups] > RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
+    if (read_order) for (uint64_t x = 0; x < grp_off[n_groups]; ++x) if (read_order[x] >= RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
+    const uint64_t N = RD.n; const uint32_t G = (uint32_t)n_groups;
+    const int W = prm->window > 0 ? prm->window : 500;
+    ht.mark("upload + checks");
+    // backbones to host strings (they are tiny and are rebuilt on the host after every iteration)
+    std::vector<std::string> B(G);
+    {
+        std::vector<uint64_t> boff(G + 1); std::vector<uint8_t> bseq;
+        if (backbones->mem == NGSID_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpy(boff.data(), backbones->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
+            if (boff[G]) HIPCHK(ctx, hipMemcpy(bseq.data(), backbones->seq, boff[G], hipMemcpyDeviceToHost));
+        } else { memcpy(boff.data(), backbones->off, 8 * (G + 1)); bseq.assign(backbones->seq, backbones->seq + boff[G]); bseq.push_back(0); }
+        for (uint32_t g = 0; g < G; ++g) B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g]));
+    }
+    if (N == 0 || G == 0) {
+        uint64_t total = 0; out_off[0] = 0; bool ovf = false;
+        for (uint32_t g = 0; g < G; ++g) { if (trace) {} else if (total + B[g].size() <= out_cap && out) memcpy(out + total, B[g].data(), B[g].size()); else if (B[g].size()) ovf = true; total += B[g].size(); out_off[g + 1] = total; if (n_used) n_used[g] = 0; }
+        if (trace) for (int it = 0; it < prm->iters; ++it) for (uint32_t g = 0; g < G; ++g) { trace->seq.push_back(B[g]); trace->used.push_back(0); }
+        if (trace && trace->aln) for (uint64_t x = 0; x < (uint64_t)prm->iters * grp_off[n_groups] * 6; ++x) trace->aln[x] = -1;
+        if (needed) *needed = total; if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "output buffer too small"); return NGSID_OK;
+    }
+    // ---- read -> group map, mean read length per group (TGS/NGS window type)
+    std::vector<uint32_t> h_rgroup(N, 0xffffffffu); std::vector<uint8_t> tgs(G, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        double tot = 0; const uint64_t ns = grp_off[g + 1] - grp_off[g];
+        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
+            const uint64_t r = read_order ? read_order[x] : x;
+            if (h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): strand and layers are kept per read, list every read under one backbone", (unsigned long long)r, h_rgroup[r], g);
+            h_rgroup[r] = g; tot += (double)(RD.h_off[r + 1] - RD.h_off[r]);
+        }
+        tgs[g] = ns > 0 && (tot / (double)ns) > 1000.0;
+    }
+    ht.mark("group map");
+    OrientBufs ob; DevBuf<int> flag; HIPCHK(ctx, flag.alloc(1)); static thread_local PinVec<uint8_t> h_orient;
+    rc = ngsid_polish_orient(ctx, RD, B, h_rgroup, prm->k, prm->w, ob, h_orient); if (rc) return rc;
+    DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual;
+    ht.mark("minimizers + strand + orient");
     // ---- pairs (usable reads of reads that belong to a group), fixed over the iterations
     static thread_local PinVec<uint32_t> pair_read, pair_group; pair_read.clear(); pair_group.clear();
     const bool want_aln = trace && trace->aln; const uint64_t NL = grp_off[n_groups];

@@ -594,6 +594,21 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
             merged[x][2] = polished[x]
             if used_out is not None: used_out[c_id] = int(used[x])
         T["polish"] = T.get("polish", 0.0) + time() - t0
+    if getattr(args, "consensus_support", False) and merged:
+        # --consensus_support: the read support of every base of the sequences just written, over the reads the polisher takes; clip as in the polisher (primer-trimmed flows)
+        t0 = time()
+        racon = getattr(args, "racon", False) and args.racon_iter >= 0
+        s_off = np.concatenate(([0], np.cumsum([len(x) for x in polish_lists]))).astype(np.uint64)
+        counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings([m[2] for m in merged]), work, s_off, read_order=np.concatenate(polish_lists).astype(np.uint32), k=args.k, w=args.w, clip=clip)
+        for x, (nr, c_id, center, cs) in enumerate(merged):
+            tab = counts[int(cen_off[x]):int(cen_off[x + 1])]
+            if racon:
+                folder = os.path.join(args.outfolder, "racon_cl_id_{0}".format(c_id))
+                consensus_mod.write_support_for_fasta(os.path.join(folder, "consensus.fasta"), os.path.join(folder, "consensus.fastq"), os.path.join(folder, "consensus_support.tsv"), tab)
+            else:
+                ref = os.path.join(args.outfolder, "consensus_reference_{0}".format(c_id))
+                consensus_mod.write_support_for_fasta(ref + ".fasta", ref + ".fastq", ref + ".support.tsv", tab)
+        T["support"] = T.get("support", 0.0) + time() - t0
     return merged
 
 

@@ -138,9 +138,11 @@ def pooled_read_lists(merged, group_reads):
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                 strand_aware=False, draft_trim=None, single_below=None):
+                 strand_aware=False, draft_trim=None, single_below=None, support=False):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
-    default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership."""
+    default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
+    support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
+    polisher takes (Api.consensus_support); every other key is what support=False returns."""
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
     single_below = SINGLE_BELOW if single_below is None else single_below
     T = timings if timings is not None else {}
@@ -186,7 +188,8 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     merged = detect_reverse_complements(api, centers, rc_identity_threshold)
     T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
     polished = [m[2] for m in merged]
-    if do_polish and racon_iter > 0:
+    polishing = do_polish and racon_iter > 0
+    if polishing or support:
         t0 = time.perf_counter()
         def group_reads(ci):                                                    # pooled reads of the merged clusters (consensus.py:208-215)
             a, b = int(grp_off[ci]), int(grp_off[ci + 1])
@@ -194,12 +197,26 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
                 b = min(b, a + max_seqs_for_consensus)                          # the pooled file is built from the truncated reads_c_id files
             return order[a:b]
         lists = pooled_read_lists(merged, group_reads)
+    if polishing:
         pprm = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=band, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
         p_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
         polished, used = api.polish(ReadSet.from_strings([m[2] for m in merged]), rs, p_off, pprm, read_order=np.concatenate(lists))      # (dealt to two contexts when it pays: _capi.Api lanes)
         T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
     res["centers"] = [(m[0], m[1], m[2], polished[i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged)]
+    if support:
+        t0 = time.perf_counter()
+        res["support"] = _support_of(api, rs, list(polished), lists, k, w)
+        T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
     return res
+
+
+def _support_of(api, rs, seqs, lists, k, w):
+    """Api.consensus_support of the sequences seqs over their read lists, ONE call -> one [len, 8] array per sequence"""
+    if not seqs:
+        return []
+    s_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
+    counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings(seqs), rs, s_off, read_order=np.concatenate(lists).astype(np.uint32), k=k, w=w)
+    return [counts[int(cen_off[i]):int(cen_off[i + 1])] for i in range(len(seqs))]
 
 
 POA_BAND64_MAXLEN = 3000       # include/ngsid.h NGSID_POA_BAND64_MAXLEN: band <= 0 means 64 columns iff every read of the call has at most this many bases, else 128
@@ -208,12 +225,13 @@ POA_BAND64_MAXLEN = 3000       # include/ngsid.h NGSID_POA_BAND64_MAXLEN: band <
 def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                         strand_aware=False, draft_trim=None, single_below=None):
+                         strand_aware=False, draft_trim=None, single_below=None, support=False):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
     are grouped by the band they would get alone (a sample with a read above POA_BAND64_MAXLEN bases gets 128 columns, the others 64), so at most two consensus
-    and two polishing calls.  strand_aware is not supported here (ValueError)."""
+    and two polishing calls.  support=True: the support key of run_hot_path per sample, from one consensus_support call for all samples.  strand_aware is not
+    supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
@@ -270,11 +288,14 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     merged = dict(zip(live, detect_reverse_complements_samples(api, centers, rc_identity_threshold)))
     T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
     polished = {s: [m[2] for m in merged[s]] for s in live}
-    if do_polish and racon_iter > 0:
+    polishing = do_polish and racon_iter > 0
+    if polishing or support:
+        pooled = {s: pooled_read_lists(merged[s], lambda ci, s=s: cluster_reads(s, ci)) for s in live}
+    if polishing:
         t0 = time.perf_counter()
         for bnd in bands:
             ss = [s for s in live if tab[s][5] == bnd]
-            lists = [l for s in ss for l in pooled_read_lists(merged[s], lambda ci, s=s: cluster_reads(s, ci))]
+            lists = [l for s in ss for l in pooled[s]]
             pprm = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
             p_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
             pol, _ = api.polish(ReadSet.from_strings([m[2] for s in ss for m in merged[s]]), rs, p_off, pprm, read_order=np.concatenate(lists).astype(np.uint32))
@@ -285,4 +306,11 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     for s in live:
         reps = tab[s][0]
         out[s]["centers"] = [(m[0], m[1], m[2], polished[s][i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged[s])]
+    if support:
+        t0 = time.perf_counter()
+        sup = _support_of(api, rs, [q for s in live for q in polished[s]], [l for s in live for l in pooled[s]], k, w)
+        x = 0
+        for s in live:
+            out[s]["support"] = sup[x:x + len(merged[s])]; x += len(merged[s])
+        T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
     return out
