@@ -49,6 +49,14 @@ class SupportParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("w", C.c_int32), ("clip", C.c_int32)]          # include/ngsid_support.h ngsid_support_params_t
 
 
+class DemuxParams(C.Structure):
+    _fields_ = [("window", C.c_int32), ("max_ed", C.c_int32), ("iupac", C.c_int32)]  # include/ngsid_demux.h ngsid_demux_params_t
+
+
+DEMUX_FIELDS = ("tag", "ed", "start", "end", "ed2")                                # the five integers per (read, side) of Api.demux_locate
+DEMUX_MAX_TAG_LEN, DEMUX_MAX_WINDOW = 64, 256
+
+
 SUPPORT_COLUMNS = ("depth", "agree", "A", "C", "G", "T", "del", "ins_after")       # the eight counters per base of Api.consensus_support
 
 
@@ -605,3 +613,21 @@ class Api:
         if rc: self._err(rc)
         return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
 
+
+    # ---- include/ngsid_demux.h
+    def demux_locate(self, rs: ReadSet, tags, window=150, max_ed=3, iupac=True, matrices=False):
+        """ngsid_demux_locate: every tag located in both end windows of every read -> hits [n, 2, 5] int32 in DEMUX_FIELDS order (side 1 in reverse-complement
+        coordinates); matrices=True: (hits, ed_all [n, 2, T] int16, end_all [n, 2, T] int16), ed and end of every tag.  tags: a list of strings or a host ReadSet.
+        There is no CPU implementation: a library without the entry point is an error."""
+        if not hasattr(self.lib, self.prefix + "demux_locate"):
+            raise NgsidError(-2, "the bound library does not export %sdemux_locate (include/ngsid_demux.h): rebuild it from this tree" % self.prefix)
+        tg = tags if isinstance(tags, ReadSet) else ReadSet.from_strings(list(tags))
+        if tg.mem != MEM_HOST: raise ValueError("demux_locate takes the tags as a host read set")
+        n, T = rs.n, tg.n
+        hits = np.full((n, 2, 5), -1, dtype=np.int32)
+        ed_all = np.full((n, 2, T), -1, dtype=np.int16) if matrices else None
+        end_all = np.full((n, 2, T), -1, dtype=np.int16) if matrices else None
+        prm = DemuxParams(int(window), int(max_ed), 1 if iupac else 0)
+        rc = self._call("demux_locate", C.byref(rs.c), C.byref(tg.c), C.byref(prm), _p(hits), _p(ed_all), _p(end_all))
+        if rc: self._err(rc)
+        return (hits, ed_all, end_all) if matrices else hits

@@ -42,6 +42,9 @@ def write_fastq(args):
 FASTQ_DIR_NEEDS_T1 = ("--fastq_dir requires --t 1: with --t N the cluster membership depends on the batch schedule of every sample, and merge rounds are not "
                       "batched across samples. Run with --t 1, or run the samples one by one with --fastq.")
 
+DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are handed to the --fastq_dir path, where with --t N the cluster membership depends on the "
+                  "batch schedule of every sample, and merge rounds are not batched across samples. Run with --t 1.")
+
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
@@ -81,6 +84,12 @@ def build_parser():
     p.add_argument('--poa_single_below', type=int, default=None, help='extension: clusters / polishing windows with fewer sequences than this are aligned as ONE graph in read order (spoa\'s and racon\'s own order) instead of being depth-tiled; 0 = tile everything; default: the library\'s measured threshold (pipeline.SINGLE_BELOW)')
     p.add_argument('--racon_subgraph_layers', action='store_true', help='extension: a polishing layer that does not span its window is aligned globally to the sub-graph between its first and last backbone positions, as racon does, instead of end-free to the whole window graph (default off: the shipped polisher)')
     p.add_argument('--consensus_support', action='store_true', help='extension: per-base read support of every consensus. Writes racon_cl_id_*/consensus.fastq (header and sequence of consensus.fasta, qualities from the support as Phred+33) and racon_cl_id_*/consensus_support.tsv (pos base depth agree A C G T del ins_after); without --racon, consensus_reference_{id}.fastq and consensus_reference_{id}.support.tsv')
+    p.add_argument('--demux_sheet', type=str, default=None, help='extension: --fastq is a pooled run; FILE is a TSV with one row per sample, sample<TAB>forward tag[<TAB>reverse tag] (tags of up to 64 bases, IUPAC codes allowed, primer included if wanted). Every read end is searched for every tag on the GPU; the reads are written to <outfolder>/demux/<sample>.fastq (+ <outfolder>/demux_unassigned.fastq, <outfolder>/demux_summary.tsv) and the samples then run like --fastq_dir <outfolder>/demux (needs --fastq, --outfolder and --t 1)')
+    p.add_argument('--demux_max_ed', type=int, default=3, help='extension: largest edit distance at which a tag counts as found in a read end')
+    p.add_argument('--demux_window', type=int, default=150, help='extension: bases of each read end that are searched for the tags (1..256)')
+    p.add_argument('--demux_min_margin', type=int, default=2, help='extension: an end is ambiguous when its second-best tag is closer than this many edits to its best')
+    p.add_argument('--demux_keep_tags', action='store_true', help='extension: leave the tags on the demultiplexed reads (default: cut each end behind its tag)')
+    p.add_argument('--demux_only', action='store_true', help='extension: stop after the demultiplexing outputs')
     p.add_argument('--skip_paf', action='store_true', help='extension: do not write racon_cl_id_*/read_alignments_it_{i}.paf (the reference leaves minimap2\'s PAF of every polishing iteration there; default: written)')
     p.set_defaults(which='main')
     sub = p.add_subparsers(help='sub-command help')
@@ -114,6 +123,17 @@ def cli(argv=None):
             logging.error("--fastq_dir needs --outfolder (one sub-folder per sample is written there)."); sys.exit(1)
         if not os.path.isdir(args.fastq_dir):
             logging.error("--fastq_dir %s is not a folder." % args.fastq_dir); sys.exit(1)
+    if getattr(args, "demux_sheet", None):
+        if getattr(args, "fastq_dir", None) or args.use_old_sorted_file or not args.fastq:
+            logging.error("--demux_sheet splits ONE pooled file: give it with --fastq, not with --fastq_dir or --use_old_sorted_file."); sys.exit(1)
+        if args.nr_cores != 1:
+            logging.error(DEMUX_NEEDS_T1); sys.exit(1)
+        if not args.outfolder:
+            logging.error("--demux_sheet needs --outfolder (the sample files and one sub-folder per sample are written there)."); sys.exit(1)
+        if not os.path.isfile(args.demux_sheet):
+            logging.error("--demux_sheet %s is not a file." % args.demux_sheet); sys.exit(1)
+        if not 1 <= args.demux_window <= 256 or args.demux_max_ed < 0 or args.demux_min_margin < 0:
+            logging.error("--demux_window must be 1..256, --demux_max_ed and --demux_min_margin must not be negative."); sys.exit(1)
     if args.medaka:
         logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
     if args.k > 32 or args.k < 1:

@@ -540,6 +540,8 @@ void myers_last_row(const uint8_t* q, int qlen, const uint8_t* t, int tlen, int 
 }
 }  // namespace
 
+bool ngsid_iupac_eq(uint8_t a, uint8_t b, int iupac) { return iupac_eq(a, b, iupac); }      // the same rule for the match masks of ngsid_demux_locate (k_demux.hip)
+
 extern "C" int32_t ngsid_host_infix_locate(const uint8_t* query, int32_t qlen, const uint8_t* target, int32_t tlen, int32_t max_ed, int32_t iupac,
                                            int32_t* ed, int32_t* start, int32_t* end)
 {

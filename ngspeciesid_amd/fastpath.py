@@ -660,6 +660,8 @@ def main(args, api=None):
 
 
 def _main(args, api):
+    if getattr(args, "demux_sheet", None):
+        return _main_demux(args, api)
     if getattr(args, "fastq_dir", None):
         return _main_samples(args, api)
     st = _ingest(args, api)
@@ -728,6 +730,22 @@ def _main_samples(args, api):
         out[os.path.basename(a.outfolder)] = _finish(a, api, st, clustered, t1)
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
+
+
+def _main_demux(args, api):
+    """--demux_sheet: the pooled file is split by sample tag (demux.py over ngsid_demux_locate; the pooled reads are neither scored nor sorted), then the sample files
+    run through the --fastq_dir path as they are: <outfolder>/<sample>/ per sample.  --demux_only stops after the demultiplexer's own outputs."""
+    import copy
+    from . import demux
+    os.makedirs(args.outfolder, exist_ok=True)
+    folder, info = demux.run(args, api)
+    if getattr(args, "demux_only", False):
+        return dict(demux=info, samples={}, timings=dict(info["timings"]), n_sorted=0, n_clustered=0, clusters=0)
+    a = copy.copy(args)
+    a.fastq, a.demux_sheet, a.fastq_dir = None, None, folder
+    res = _main_samples(a, api)
+    res["demux"] = info; res["timings"].update(info["timings"])
+    return res
 
 
 def _ingest(args, api):
