@@ -1,8 +1,9 @@
-"""CPU: the oracle's edit-distance polisher aligner (ongsid_ed_align_batch) against hand-made answers and an independent
-brute-force infix edit distance."""
+"""CPU: the oracle's edit-distance polisher aligner (ongsid_ed_align_batch) against hand-made answers, an independent
+brute-force infix edit distance and the plain reference of the contract (ed_reference.py: span and break points, exactly)."""
 import numpy as np
 import pytest
 from ngspeciesid_amd._capi import ReadSet
+import ed_reference
 
 
 def infix_distance(q, t):
@@ -46,8 +47,10 @@ def test_distance_is_the_infix_edit_distance(oracle):
             elif u < 0.22: q[k] = "N"
         qs.append("".join(q)); ts.append(T)
     Q = ReadSet.from_strings(qs); T = ReadSet.from_strings(ts); idx = np.arange(len(qs), dtype=np.uint32)
-    d, span, _ = oracle.ed_align_batch(Q, T, idx, idx)
+    d, span, bp = oracle.ed_align_batch(Q, T, idx, idx, window=7, bp_windows=13)
+    rd, rspan, rbp = ed_reference.ed_align_batch(qs, ts, idx, idx, window=7, bp_windows=13)
     for i, (q, t) in enumerate(zip(qs, ts)):
         assert d[i] == infix_distance(q, t), (q, t)
         if span[i][0] >= 0:
             assert 0 <= span[i][0] <= span[i][1] < len(q) and 0 <= span[i][2] <= span[i][3] < len(t)
+        assert d[i] == rd[i] and span[i].tolist() == rspan[i].tolist() and bp[i].tolist() == rbp[i].tolist(), (q, t)

@@ -1,8 +1,10 @@
 """dev tool / stress parity of the edit-distance polisher aligner (HIP bit-parallel kernel vs the oracle's plain DP).
 
-    python tools/stress_ed.py [n_pairs] [max_qlen] [seed] [error_scale]
+    python tools/stress_ed.py [n_pairs] [max_qlen] [seed] [error_scale] [full|-] [edges]
 (error_scale multiplies the 8 % substitution / 8 % indel rates of the related queries: small values give long queries with a small distance,
 the case the banded sliding-window instance of the kernel is for)
+A sixth argument `edges` appends the pairs of family b of tests/ed_cases.py (distances K - 1, K, K + 1 and ~2K around the bands 12 ... 180),
+so that the volume run also crosses the band limit on purpose.
 Exit code 1 on any difference in distance, span or window break points.
 """
 import sys, os, time
@@ -18,6 +20,7 @@ maxq = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 escale = float(sys.argv[4]) if len(sys.argv) > 4 else 1.0
 full = len(sys.argv) > 5 and sys.argv[5] == "full"      # full-length queries against targets of similar length (what the polisher sees): whole waves stay inside the band
+edges = len(sys.argv) > 6 and sys.argv[6] == "edges"
 rng = np.random.default_rng(seed)
 api = runtime.get_api(0); orc = load_oracle()
 A = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -55,6 +58,12 @@ for T in targets:
     T = T.copy()
     if rng.random() < 0.3 and len(T): T[rng.integers(0, len(T), max(1, len(T) // 60))] = ord("N")
     tstr.append(T.tobytes().decode())
+if edges:
+    import ed_cases
+    for case in ed_cases.cases("b"):
+        for a, b in sorted(set(zip(case.q_idx.tolist(), case.t_idx.tolist()))):       # every distinct pair once (the oracle runs a full DP per pair)
+            qs.append(case.queries[a]); ti.append(len(tstr)); tstr.append(case.targets[b])
+    n = len(qs)
 Q = ReadSet.from_strings(qs); T = ReadSet.from_strings(tstr)
 qi = np.arange(n, dtype=np.uint32); ti = np.array(ti, dtype=np.uint32)
 W = 100; nw = (max(len(t) for t in tstr) + W - 1) // W
