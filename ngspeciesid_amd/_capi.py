@@ -53,6 +53,17 @@ class DemuxParams(C.Structure):
     _fields_ = [("window", C.c_int32), ("max_ed", C.c_int32), ("iupac", C.c_int32)]  # include/ngsid_demux.h ngsid_demux_params_t
 
 
+class RefDbParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("w", C.c_int32)]                                  # include/ngsid_classify.h ngsid_refdb_params_t
+
+
+class ClassifyParams(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("min_shared", C.c_int32)]                     # include/ngsid_classify.h ngsid_classify_params_t
+
+
+CLASSIFY_MAX_TOPK, CLASSIFY_MAX_K = 64, 21
+
+
 DEMUX_FIELDS = ("tag", "ed", "start", "end", "ed2")                                # the five integers per (read, side) of Api.demux_locate
 DEMUX_MAX_TAG_LEN, DEMUX_MAX_WINDOW = 64, 256
 
@@ -631,3 +642,63 @@ class Api:
         rc = self._call("demux_locate", C.byref(rs.c), C.byref(tg.c), C.byref(prm), _p(hits), _p(ed_all), _p(end_all))
         if rc: self._err(rc)
         return (hits, ed_all, end_all) if matrices else hits
+
+    # ---- include/ngsid_classify.h
+    def _need_classify(self):
+        if not hasattr(self.lib, self.prefix + "classify_search") or not hasattr(self.lib, self.prefix + "refdb_build"):
+            raise NgsidError(-2, "the bound library does not export %srefdb_build / %sclassify_search (include/ngsid_classify.h): rebuild it from this tree" % (self.prefix, self.prefix))
+
+    def refdb_build(self, refs, k=13, w=20) -> "RefDb":
+        """ngsid_refdb_build: the minimizer index of a reference library (a list of strings or a host ReadSet) on the device -> RefDb handle (.info(), .release(),
+        context manager).  There is no CPU implementation: a library without the entry point is an error."""
+        self._need_classify()
+        rs = refs if isinstance(refs, ReadSet) else ReadSet.from_strings(list(refs))
+        if rs.mem != MEM_HOST: raise ValueError("refdb_build takes the references as a host read set")
+        prm = RefDbParams(int(k), int(w)); h = C.c_void_p()
+        rc = self._call("refdb_build", C.byref(rs.c), C.byref(prm), C.byref(h))
+        if rc: self._err(rc)
+        return RefDb(self, h, int(k), int(w), rs)
+
+    def classify_search(self, refdb: "RefDb", queries: ReadSet, top_k=8, min_shared=3, n_codes=False):
+        """ngsid_classify_search -> (cand_ref [n, top_k] int32, cand_shared [n, top_k] int32, cand_strand [n, top_k] int8), -1 where a query has fewer candidates;
+        n_codes=True: + n_codes [n, 2] int32, the distinct minimizer codes of each query strand."""
+        self._need_classify()
+        if refdb.api is not self or refdb.handle is None: raise NgsidError(-2, "the reference library was released or belongs to another context")
+        n = queries.n; K = max(int(top_k), 0)
+        ref = np.full((n, K), -1, dtype=np.int32); sh = np.full((n, K), -1, dtype=np.int32); st = np.full((n, K), -1, dtype=np.int8)
+        nc = np.zeros((n, 2), dtype=np.int32) if n_codes else None
+        prm = ClassifyParams(int(top_k), int(min_shared))
+        rc = self._call("classify_search", refdb.handle, C.byref(queries.c), C.byref(prm), _p(ref), _p(sh), _p(st), _p(nc))
+        if rc: self._err(rc)
+        return (ref, sh, st, nc) if n_codes else (ref, sh, st)
+
+
+class RefDb:
+    """handle of a reference library built by Api.refdb_build; owned by that context (released with it at the latest)"""
+
+    def __init__(self, api, handle, k, w, refs=None):
+        self.api, self.handle, self.k, self.w = api, handle, k, w
+        self.refs = refs          # the host read set it was built from: classify.verify aligns against it
+
+    def info(self):
+        """-> dict(n_refs, n_postings, n_codes, device_bytes)"""
+        if self.handle is None: raise NgsidError(-2, "the reference library was released")
+        v = [C.c_uint64(0) for _ in range(4)]
+        f = self.api._fn("refdb_info")
+        rc = f(self.handle, *[C.byref(x) for x in v])
+        if rc: self.api._err(rc)
+        return dict(zip(("n_refs", "n_postings", "n_codes", "device_bytes"), (int(x.value) for x in v)))
+
+    def release(self):
+        """idempotent"""
+        h, self.handle = self.handle, None
+        if h is not None and self.api.ctx is not None:
+            rc = self.api._call("refdb_release", h)
+            if rc: self.api._err(rc)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False

@@ -48,6 +48,7 @@ DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are h
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
+                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--version', action='version', version='%(prog)s 0.3.1-mi355x')
     p.add_argument('--debug', action='store_true')
@@ -90,6 +91,9 @@ def build_parser():
     p.add_argument('--demux_min_margin', type=int, default=2, help='extension: an end is ambiguous when its second-best tag is closer than this many edits to its best')
     p.add_argument('--demux_keep_tags', action='store_true', help='extension: leave the tags on the demultiplexed reads (default: cut each end behind its tag)')
     p.add_argument('--demux_only', action='store_true', help='extension: stop after the demultiplexing outputs')
+    p.add_argument('--reference_db', type=str, default=None, help='extension: FASTA of reference barcodes (BOLD, UNITE, SILVA, ...). Every final consensus (the polished one with --racon, else the draft) is searched in it on the GPU by shared minimizers, both strands, and its best candidates are verified by alignment; writes <outfolder>/classification.tsv (consensus_id n_reads rank reference strand shared identity aln_cols n_match q_cov r_cov called header; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/classification_all.tsv). Needs --consensus')
+    from . import classify as _classify
+    _classify.add_flags(p)
     p.add_argument('--skip_paf', action='store_true', help='extension: do not write racon_cl_id_*/read_alignments_it_{i}.paf (the reference leaves minimap2\'s PAF of every polishing iteration there; default: written)')
     p.set_defaults(which='main')
     sub = p.add_subparsers(help='sub-command help')
@@ -103,12 +107,43 @@ def build_parser():
     return p
 
 
+def _classify_subparser(cf):
+    """the `classify` sub-command.  It is parsed by a parser of its own (cli() below), not as a sub-parser of the main command like write_fastq: the main command requires one
+    of --fastq / --use_old_sorted_file / --fastq_dir, which a sub-parser cannot lift, and `classify --fasta X --reference_db DB --outfile T` needs none of them."""
+    from . import classify as _classify
+    cf.add_argument('--fasta', type=str, required=True, help='sequences to classify')
+    cf.add_argument('--reference_db', type=str, required=True, help='FASTA of reference barcodes')
+    cf.add_argument('--outfile', type=str, required=True, help='the table (columns of classification.tsv)')
+    _classify.add_flags(cf)
+    cf.set_defaults(which='classify')
+    return cf
+
+
+def _check_classify(args):
+    from . import classify as _classify
+    err = _classify.check_args(args)
+    if err:
+        logging.error(err); sys.exit(1)
+    if not os.path.isfile(args.reference_db):
+        logging.error("--reference_db %s is not a file." % args.reference_db); sys.exit(1)
+
+
 def cli(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO, format='%(message)s')
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == 'classify':              # `classify --fasta X --reference_db DB --outfile T` needs none of the main command's inputs
+        args = _classify_subparser(argparse.ArgumentParser(prog='classify', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    else:
+        args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.DEBUG if getattr(args, 'debug', False) else logging.INFO, format='%(message)s')
     if getattr(args, "which", "main") == 'write_fastq':          # NGSpeciesID:255-258
         write_fastq(args)
         logging.info("Wrote clusters to separate fastq files.")
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'classify':
+        _check_classify(args)
+        from . import classify as _classify
+        rows = _classify.classify_fasta(args)
+        logging.info("Wrote %d rows to %s." % (len(rows), args.outfile))
         sys.exit(0)
     if args.ont and args.isoseq:
         logging.error("Arguments mutually exclusive, specify either --isoseq or --ont. "); sys.exit()
@@ -134,6 +169,10 @@ def cli(argv=None):
             logging.error("--demux_sheet %s is not a file." % args.demux_sheet); sys.exit(1)
         if not 1 <= args.demux_window <= 256 or args.demux_max_ed < 0 or args.demux_min_margin < 0:
             logging.error("--demux_window must be 1..256, --demux_max_ed and --demux_min_margin must not be negative."); sys.exit(1)
+    if getattr(args, "reference_db", None):
+        if not args.consensus:
+            logging.error("--reference_db classifies consensus sequences: it needs --consensus."); sys.exit(1)
+        _check_classify(args)
     if args.medaka:
         logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
     if args.k > 32 or args.k < 1:

@@ -119,7 +119,10 @@ struct ngsid_ctx {
     DevBuf<unsigned long long> stat;     // work counters while profiling is on (bench.py): [0] DP rows of k_poa_tile, [1] DP cells of the clustering aligner
     bool prof = false; std::vector<ProfEntry> prof_events; std::map<std::string, std::pair<double, uint64_t>> prof_acc;
     DevBuf<int32_t> poa_h; DevBuf<uint8_t> poa_d; DevBuf<uint8_t> poa_g; DevBuf<uint32_t> poa_cov;   // POA tile scratch (grow-only)
+    DevBuf<uint32_t> cls_cnt;                                  // count rows [query][strand][reference] of ngsid_classify_search's current chunk (grow-only; k_classify.hip)
+    std::vector<struct ngsid_refdb*> refdbs;                   // reference libraries built in this context (ngsid_refdb_build) and not released yet: they go with the context
 };
+void ngsid_refdb_release_all(ngsid_ctx* ctx);                  // k_classify.hip: ngsid_destroy releases the libraries the caller left
 
 // Scheduling options of a context (ngsid_ctx_option): block sizes, kernel instance choice, band of the first attempt.  Set explicitly through the
 // C-ABI by tests and tools - the library reads NO environment variable for them; results never depend on them (the tests run both ways).

@@ -673,7 +673,20 @@ def _main(args, api):
     finally:                                        # sorted.fastq is written whatever the clustering call did (the reference has it on disk before it clusters)
         deferred, args._deferred = getattr(args, "_deferred", []), []
         for fn_, a_, kw_ in deferred: _write(args, fn_, *a_, **kw_)
-    return _finish(args, api, st, clustered, t0)
+    res = _finish(args, api, st, clustered, t0)
+    if getattr(args, "reference_db", None) and args.consensus:
+        _classify_step(args, api, [(None, args.outfolder, res["centers"])], res["timings"])
+    return res
+
+
+def _classify_step(args, api, groups, T):
+    """--reference_db: the final consensuses (the polished sequences with --racon, else the drafts) of every (sample, folder, centres) group against the reference
+    library, all in one search and one verification call (classify.run) -> classification.tsv per folder (+ classification_all.tsv with samples)"""
+    from . import classify
+    t0 = time()
+    named = [(sample, folder, [("consensus_cl_id_{0}_total_supporting_reads_{1}".format(c_id, nr), nr, seq) for nr, c_id, seq, _ in centers]) for sample, folder, centers in groups]
+    classify.run(args, api, named)
+    T["classify"] = time() - t0
 
 
 def sample_files(folder):
@@ -728,6 +741,8 @@ def _main_samples(args, api):
         t1 = time()
         clustered = cluster(st["sr"], st["work"], st["sel"], a, api, st["work_dev"], st["T"], precomputed=pre)
         out[os.path.basename(a.outfolder)] = _finish(a, api, st, clustered, t1)
+    if getattr(args, "reference_db", None) and args.consensus:
+        _classify_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 

@@ -138,11 +138,13 @@ def pooled_read_lists(merged, group_reads):
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                 strand_aware=False, draft_trim=None, single_below=None, support=False):
+                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
-    polisher takes (Api.consensus_support); every other key is what support=False returns."""
+    polisher takes (Api.consensus_support); every other key is what support=False returns.
+    classify=RefDb (extension; Api.refdb_build): also classify = one list of ranked hits per centre (classify.identify: its final sequence searched in the reference
+    library and verified by alignment; classify_kwargs: top_k, min_shared, min_identity, min_query_cov); every other key is what classify=None returns."""
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
     single_below = SINGLE_BELOW if single_below is None else single_below
     T = timings if timings is not None else {}
@@ -161,6 +163,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         res.update(rep_of=rep_of, flip=flip, strand_info=sinfo)
         T["strand_merge"] = T.get("strand_merge", 0.0) + time.perf_counter() - t0
     if not do_consensus:
+        if classify is not None: res["classify"] = []
         return res
     t0 = time.perf_counter()
     reps, order, grp_off, counts = clusters_from_rep(rep_of)
@@ -171,6 +174,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     sel = select_centers(reps, counts, score, cutoff)
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     if not sel:
+        if classify is not None: res["classify"] = []                           # no centre: nothing to name
         return res
     t0 = time.perf_counter()
     sub_order, sub_off = [], [0]
@@ -207,6 +211,11 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         t0 = time.perf_counter()
         res["support"] = _support_of(api, rs, list(polished), lists, k, w)
         T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
+    if classify is not None:
+        from . import classify as classify_mod
+        t0 = time.perf_counter()
+        res["classify"] = classify_mod.identify(api, classify, list(polished), **(classify_kwargs or {}))
+        T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
     return res
 
 
@@ -225,13 +234,13 @@ POA_BAND64_MAXLEN = 3000       # include/ngsid.h NGSID_POA_BAND64_MAXLEN: band <
 def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                         strand_aware=False, draft_trim=None, single_below=None, support=False):
+                         strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
     are grouped by the band they would get alone (a sample with a read above POA_BAND64_MAXLEN bases gets 128 columns, the others 64), so at most two consensus
-    and two polishing calls.  support=True: the support key of run_hot_path per sample, from one consensus_support call for all samples.  strand_aware is not
-    supported here (ValueError)."""
+    and two polishing calls.  support=True: the support key of run_hot_path per sample, from one consensus_support call for all samples.  classify=RefDb: the classify
+    key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
@@ -244,6 +253,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     T["cluster"] = T.get("cluster", 0.0) + time.perf_counter() - t0
     out = [dict(rep_of=rep_of[so[s]:so[s + 1]] - np.int32(so[s]), status=status[so[s]:so[s + 1]], counters=counters[s], hpc_err=herr[so[s]:so[s + 1]], centers=[]) for s in range(ns)]
     if not do_consensus:
+        if classify is not None:
+            for o in out: o["classify"] = []
         return out
     # ---- per-sample cluster tables and selections (local indices), the samples grouped by band
     t0 = time.perf_counter()
@@ -313,4 +324,13 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
         for s in live:
             out[s]["support"] = sup[x:x + len(merged[s])]; x += len(merged[s])
         T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
+    if classify is not None:
+        from . import classify as classify_mod
+        t0 = time.perf_counter()
+        hits = classify_mod.identify(api, classify, [q for s in live for q in polished[s]], **(classify_kwargs or {}))
+        for o in out: o["classify"] = []                                        # samples without a centre
+        x = 0
+        for s in live:
+            out[s]["classify"] = hits[x:x + len(merged[s])]; x += len(merged[s])
+        T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
     return out
