@@ -71,6 +71,18 @@ DEMUX_MAX_TAG_LEN, DEMUX_MAX_WINDOW = 64, 256
 SUPPORT_COLUMNS = ("depth", "agree", "A", "C", "G", "T", "del", "ins_after")       # the eight counters per base of Api.consensus_support
 
 
+PHASE_MAX_SITES, PHASE_MAX_HAPS = 64, 16                                          # include/ngsid_phase.h
+GENO_DEL, GENO_OTHER, GENO_NONE, HAP_ANY = 4, 5, 7, 255
+
+
+def phase_offsets(grp_off, site_off):
+    """-> (geno_off, tab_off) [n_groups + 1] uint64: where group g's [R_g, S_g] genotype block and its [S_g, S_g, 5, 5] pair tables start (include/ngsid_phase.h)"""
+    r = np.diff(np.asarray(grp_off).astype(np.int64)); s = np.diff(np.asarray(site_off).astype(np.int64))
+    geno_off = np.zeros(len(r) + 1, dtype=np.uint64); tab_off = np.zeros(len(r) + 1, dtype=np.uint64)
+    geno_off[1:] = np.cumsum(r * s); tab_off[1:] = np.cumsum(25 * s * s)
+    return geno_off, tab_off
+
+
 def cluster_params(k=13, w=20, min_shared=5, min_fraction=0.8, mapped_threshold=0.7, aligned_threshold=0.4,
                    min_prob_no_hits=0.1, symmetric=False, p_shared=None):
     p = ClusterParams()
@@ -623,6 +635,61 @@ class Api:
         rc = self._call("consensus_support", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(counts), _p(used), _p(strand))
         if rc: self._err(rc)
         return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
+
+    # ---- include/ngsid_phase.h
+    def _need_phase(self):
+        if not all(hasattr(self.lib, self.prefix + n) for n in ("phase_genotypes", "phase_pair_tables", "phase_assign")):
+            raise NgsidError(-2, "the bound library does not export %sphase_genotypes / _pair_tables / _assign (include/ngsid_phase.h): rebuild it from this tree" % self.prefix)
+
+    def phase_genotypes(self, centres: ReadSet, rs: ReadSet, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):
+        """ngsid_phase_genotypes: the allele of every listed read at the sites site_pos[site_off[g]:site_off[g + 1]] (ascending centre positions, at most PHASE_MAX_SITES) of
+        its group -> (geno uint8, geno_off [n_groups + 1], strand [n_listed] int8).  geno[geno_off[g]:geno_off[g + 1]].reshape(R_g, S_g) is group g, [listed read][site]:
+        0-3 = A C G T, GENO_DEL, GENO_OTHER (mismatch with a read base outside ACGT), GENO_NONE (not counted).  Grouping, strands and counted columns as in consensus_support().
+        There is no CPU implementation: a library without the entry point is an error."""
+        if centres.mem != MEM_HOST: raise ValueError("phase_genotypes takes the centres as a host read set")
+        self._need_phase()
+        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
+        site_pos = np.ascontiguousarray(site_pos, dtype=np.uint32)
+        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
+        ng = len(grp_off) - 1
+        if len(site_off) != ng + 1 or len(site_pos) != int(site_off[-1]): raise ValueError("phase_genotypes: site_off has one entry per group + 1 and site_pos site_off[-1] entries")
+        geno_off, _ = phase_offsets(grp_off, site_off)
+        geno = np.full(max(int(geno_off[-1]), 1), GENO_NONE, dtype=np.uint8); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
+        sp = site_pos if len(site_pos) else np.zeros(1, dtype=np.uint32)
+        prm = SupportParams(int(k), int(w), 1 if clip else 0)
+        rc = self._call("phase_genotypes", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(site_off), _p(sp), _p(geno), _p(strand))
+        if rc: self._err(rc)
+        return geno[:int(geno_off[-1])], geno_off, strand[:int(grp_off[-1])]
+
+    def phase_pair_tables(self, geno, grp_off, site_off):
+        """ngsid_phase_pair_tables -> (tables uint32, tab_off [n_groups + 1]): tables[tab_off[g]:tab_off[g + 1]].reshape(S_g, S_g, 5, 5)[s, t, a, b], s < t, = listed reads of
+        group g with code a at site s and code b at site t (both <= GENO_DEL); zero for s >= t."""
+        self._need_phase()
+        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
+        geno_off, tab_off = phase_offsets(grp_off, site_off)
+        geno = np.ascontiguousarray(geno, dtype=np.uint8)
+        if len(geno) != int(geno_off[-1]): raise ValueError("phase_pair_tables: geno has %d entries, the offsets ask for %d" % (len(geno), int(geno_off[-1])))
+        tables = np.zeros(max(int(tab_off[-1]), 1), dtype=np.uint32)
+        rc = self._call("phase_pair_tables", _p(geno if len(geno) else np.zeros(1, np.uint8)), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(tables))
+        if rc: self._err(rc)
+        return tables[:int(tab_off[-1])], tab_off
+
+    def phase_assign(self, geno, grp_off, site_off, hap_off, hap_alleles):
+        """ngsid_phase_assign: haplotypes hap_off[g]:hap_off[g + 1] (at most PHASE_MAX_HAPS) belong to group g, hap_alleles holds their [haplotype][site] blocks group after
+        group (0 - GENO_DEL, or HAP_ANY) -> (best int8, dist uint8, dist2 uint8) per listed read: the nearest haplotype within the group (the lowest on ties), its distance
+        over the sites both cover, and the smallest distance over the other haplotypes (255: none).  -1 / 255 / 255 for a read without a covered site or a group without haplotypes."""
+        self._need_phase()
+        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64); hap_off = np.ascontiguousarray(hap_off, dtype=np.uint64)
+        geno_off, _ = phase_offsets(grp_off, site_off)
+        geno = np.ascontiguousarray(geno, dtype=np.uint8); hal = np.ascontiguousarray(hap_alleles, dtype=np.uint8).ravel()
+        need = int((np.diff(hap_off.astype(np.int64)) * np.diff(site_off.astype(np.int64))).sum())
+        if len(geno) != int(geno_off[-1]) or len(hal) != need or len(hap_off) != len(grp_off): raise ValueError("phase_assign: geno / hap_alleles do not match the offsets")
+        nl = int(grp_off[-1])
+        best = np.full(max(nl, 1), -1, dtype=np.int8); dist = np.full(max(nl, 1), 255, dtype=np.uint8); dist2 = np.full(max(nl, 1), 255, dtype=np.uint8)
+        rc = self._call("phase_assign", _p(geno if len(geno) else np.zeros(1, np.uint8)), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(hap_off), _p(hal if len(hal) else np.zeros(1, np.uint8)),
+                        _p(best), _p(dist), _p(dist2))
+        if rc: self._err(rc)
+        return best[:nl], dist[:nl], dist2[:nl]
 
 
     # ---- include/ngsid_demux.h

@@ -94,6 +94,12 @@ def build_parser():
     p.add_argument('--reference_db', type=str, default=None, help='extension: FASTA of reference barcodes (BOLD, UNITE, SILVA, ...). Every final consensus (the polished one with --racon, else the draft) is searched in it on the GPU by shared minimizers, both strands, and its best candidates are verified by alignment; writes <outfolder>/classification.tsv (consensus_id n_reads rank reference strand shared identity aln_cols n_match q_cov r_cov called header; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/classification_all.tsv). Needs --consensus')
     from . import classify as _classify
     _classify.add_flags(p)
+    from . import phase as _phase
+    p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
+    p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
+    p.add_argument('--hap_min_reads', type=int, default=_phase.DEFAULTS["min_hap_reads"], help='extension: an allele string is a haplotype when at least this many reads carry it')
+    p.add_argument('--hap_min_phi', type=float, default=_phase.DEFAULTS["min_phi"], help='extension: two sites are linked at this phi coefficient of their allele table or above')
+    p.add_argument('--hap_max', type=int, default=_phase.DEFAULTS["max_haps"], help='extension: most haplotypes per cluster (2..16)')
     p.add_argument('--skip_paf', action='store_true', help='extension: do not write racon_cl_id_*/read_alignments_it_{i}.paf (the reference leaves minimap2\'s PAF of every polishing iteration there; default: written)')
     p.set_defaults(which='main')
     sub = p.add_subparsers(help='sub-command help')
@@ -151,6 +157,15 @@ def cli(argv=None):
         args.k, args.w = 15, 50
     elif args.ont:
         args.k, args.w = 13, 20
+    if getattr(args, "split_haplotypes", False):
+        if getattr(args, "fastq_dir", None) or getattr(args, "demux_sheet", None):
+            logging.error("--split_haplotypes works on one sample: it cannot be combined with --fastq_dir or --demux_sheet (run the samples one by one)."); sys.exit(1)
+        if not args.consensus:
+            logging.error("--split_haplotypes splits the reads of consensus sequences: it needs --consensus."); sys.exit(1)
+        from . import phase as _phase
+        err = _phase.check_args(args)
+        if err:
+            logging.error(err); sys.exit(1)
     if getattr(args, "fastq_dir", None):
         if args.nr_cores != 1:
             logging.error(FASTQ_DIR_NEEDS_T1); sys.exit(1)

@@ -5,8 +5,7 @@
 // 256 lanes read 128 consecutive bytes of a row), a workgroup takes a slice of ONE group's reads, keeps the eight counters of its position in registers and adds them once
 // per (workgroup, position) with atomicAdd on uint32.  The traceback itself never touches the counters: its 64 lanes walk 64 reads of the same centre in near lockstep, so
 // every step would be 64 atomics on one address.  Integer adds commute: the result does not depend on the schedule.
-#include "ngsid_internal.h"
-#include "../../include/ngsid_support.h"
+#include "k_support.h"
 #include <algorithm>
 
 typedef unsigned long long u64;
@@ -53,12 +52,13 @@ void k_support_sum(const uint32_t* __restrict__ rec, uint32_t stride, const int3
     if (ins) atomicAdd(out + NGSID_SUPPORT_INS, ins);
 }
 
-extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order,
-                                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_support_params_t* prm,
-                                           uint32_t* counts, uint64_t* n_used, int8_t* strand)
+// The store pass and its bookkeeping, shared with ngsid_phase_genotypes (k_phase.hip): argument checks, strands, pairs in list order, the path matrix chunk by chunk.
+// `init` runs once the centres are on the host (P.G, P.total, P.maxb, P.boff: validate and clear the caller's outputs); `start` once before the first chunk, when there is
+// at least one pair (everything else of P is set: device allocations of the consumer); `chunk` after the store pass of every chunk, followed by a stream synchronisation.
+int32_t ngsid_rec_walk(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups,
+                       const ngsid_support_params_t* prm, int8_t* strand, const std::function<int32_t(const RecPlan&)>& init,
+                       const std::function<int32_t(const RecPlan&)>& start, const std::function<int32_t(const RecPlan&, const RecChunk&)>& chunk)
 {
-    ApiClock api_clock_(ctx, "consensus_support");
-    if (!ctx) return NGSID_ERR_ARG;
     if (!centres || !reads || !grp_off || !prm) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     if (centres->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one centre per group expected");
     if (prm->clip != 0 && prm->clip != 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_support_params_t.clip must be 0 or 1");
@@ -67,7 +67,8 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
     if (!read_order && NL > N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
     if (read_order) for (uint64_t x = 0; x < NL; ++x) if (read_order[x] >= N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
     // centres to host strings (the strand detection takes them like the polisher's backbones)
-    std::vector<std::string> B(G); std::vector<uint64_t> boff(G + 1, 0); std::vector<uint8_t> bseq;
+    RecPlan P; P.G = G; P.boff.assign(G + 1, 0);
+    std::vector<std::string> B(G); std::vector<uint64_t>& boff = P.boff; std::vector<uint8_t> bseq;
     if (G) {
         if (centres->mem == NGSID_MEM_DEVICE) {
             HIPCHK(ctx, hipMemcpy(boff.data(), centres->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
@@ -76,9 +77,8 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
     }
     const uint64_t total = boff[G]; uint32_t maxb = 0;
     for (uint32_t g = 0; g < G; ++g) { B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g])); maxb = std::max<uint32_t>(maxb, (uint32_t)B[g].size()); }
-    if (total && !counts) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null counts");
-    if (counts) memset(counts, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total);
-    if (n_used) for (uint32_t g = 0; g < G; ++g) n_used[g] = 0;
+    P.total = total; P.maxb = maxb;
+    rc = init(P); if (rc) return rc;
     if (strand) for (uint64_t x = 0; x < NL; ++x) strand[x] = -1;
     if (maxb > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "centre longer than %d", NGSID_MAX_CONSENSUS_LEN);
     // ---- read -> group map
@@ -93,28 +93,28 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
     OrientBufs ob; static thread_local PinVec<uint8_t> h_orient;
     rc = ngsid_polish_orient(ctx, RD, B, h_rgroup, prm->k, prm->w, ob, h_orient); if (rc) return rc;
     // ---- pairs in list order (group by group); pairs [gbeg[g], gbeg[g+1]) are group g's
-    static thread_local PinVec<uint32_t> pair_read, pair_group; pair_read.clear(); pair_group.clear();
-    std::vector<uint64_t> gbeg(G + 1, 0);
+    static thread_local PinVec<uint32_t> pair_read, pair_group, pair_x; pair_read.clear(); pair_group.clear(); pair_x.clear();
+    std::vector<uint64_t>& gbeg = P.gbeg; gbeg.assign(G + 1, 0);
     for (uint32_t g = 0; g < G; ++g) {
         for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
             const uint64_t r = read_order ? read_order[x] : x;
             if (h_orient[r] == 255) continue;
-            pair_read.push_back((uint32_t)r); pair_group.push_back(g); if (strand) strand[x] = (int8_t)h_orient[r];
+            pair_read.push_back((uint32_t)r); pair_group.push_back(g); pair_x.push_back((uint32_t)(x - grp_off[g])); if (strand) strand[x] = (int8_t)h_orient[r];
         }
         gbeg[g + 1] = pair_read.size();
     }
-    const uint64_t NP = pair_read.size();
+    const uint64_t NP = pair_read.size(); P.NP = NP; P.pair_x = pair_x.data();
     if (NP == 0 || total == 0) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return NGSID_OK; }
-    DevBuf<uint32_t> d_pair_read, d_pair_group, d_counts, d_items, d_rec; DevBuf<int32_t> d_span; DevBuf<u64> d_used;
-    HIPCHK(ctx, d_pair_read.alloc(NP)); HIPCHK(ctx, d_pair_group.alloc(NP)); HIPCHK(ctx, d_counts.alloc(total * NGSID_SUPPORT_NCOUNT)); HIPCHK(ctx, d_used.alloc(G));
+    DevBuf<uint32_t> d_pair_read, d_pair_group, d_rec; DevBuf<int32_t> d_span;
+    HIPCHK(ctx, d_pair_read.alloc(NP)); HIPCHK(ctx, d_pair_group.alloc(NP));
     HIPCHK(ctx, hipMemcpyAsync(d_pair_read.p, pair_read.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(d_pair_group.p, pair_group.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_counts.p, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(d_used.p, 0, sizeof(u64) * G, ctx->stream));
     ngsid_reads_t br{bseq.data(), nullptr, boff.data(), G, NGSID_MEM_HOST, 0};
     DevReads BB; rc = ngsid_upload_reads(ctx, &br, &BB, false); if (rc) return rc;
     // ---- chunks of pairs under the byte budget of the path matrix (the share of the free device memory the POA batches take; option "support_budget_mb")
     const uint32_t stride = ((maxb + 63u) & ~63u) / 8;                    // dwords per row
+    P.stride = stride; P.d_cen_seq = BB.seq; P.d_cen_off = BB.off; P.d_pair_group = d_pair_group.p;
+    rc = start(P); if (rc) return rc;
     size_t budget = 0;
     { const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
       if (mb > 0) budget = (size_t)mb << 20;
@@ -122,28 +122,56 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
              budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (3 * (size_t)ngsid_pool_contexts()), (size_t)256 << 20), (size_t)16 << 30); } }
     const uint64_t rows = std::min<uint64_t>(NP, std::max<uint64_t>(64, budget / ((size_t)stride * 4)));
     HIPCHK(ctx, d_rec.alloc(rows * stride)); HIPCHK(ctx, d_span.alloc(rows * 4));
-    std::vector<uint32_t> items;
     for (uint64_t c0 = 0; c0 < NP; c0 += rows) {
         const uint64_t c1 = std::min(NP, c0 + rows);
         AlignJob J{};
         J.qseq = ctx->pol_oseq.p; J.qoff = RD.off; J.tseq = BB.seq; J.toff = BB.off; J.qidx = d_pair_read.p + c0; J.tidx = d_pair_group.p + c0; J.npairs = c1 - c0;
         J.span = d_span.p; J.clip = prm->clip;
         rc = ngsid_launch_ed_align_rec(ctx, J, RD.maxlen, maxb, d_rec.p, stride); if (rc) return rc;
+        rc = chunk(P, RecChunk{d_rec.p, d_span.p, c0, c1}); if (rc) return rc;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // the consumer's host lists are pageable and refilled by the next chunk
+    }
+    return NGSID_OK;
+}
+
+extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order,
+                                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_support_params_t* prm,
+                                           uint32_t* counts, uint64_t* n_used, int8_t* strand)
+{
+    ApiClock api_clock_(ctx, "consensus_support");
+    if (!ctx) return NGSID_ERR_ARG;
+    DevBuf<uint32_t> d_counts, d_items; DevBuf<u64> d_used; std::vector<uint32_t> items; bool started = false;
+    auto init = [&](const RecPlan& P) -> int32_t {
+        if (P.total && !counts) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null counts");
+        if (counts) memset(counts, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * P.total);
+        if (n_used) for (uint32_t g = 0; g < P.G; ++g) n_used[g] = 0;
+        return NGSID_OK;
+    };
+    auto start = [&](const RecPlan& P) -> int32_t {
+        HIPCHK(ctx, d_counts.alloc(P.total * NGSID_SUPPORT_NCOUNT)); HIPCHK(ctx, d_used.alloc(P.G));
+        HIPCHK(ctx, hipMemsetAsync(d_counts.p, 0, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * P.total, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_used.p, 0, sizeof(u64) * P.G, ctx->stream));
+        started = true; return NGSID_OK;
+    };
+    auto chunk = [&](const RecPlan& P, const RecChunk& C) -> int32_t {
         items.clear();
-        for (uint32_t g = 0; g < G; ++g) {
-            const uint64_t a = std::max(gbeg[g], c0), e = std::min(gbeg[g + 1], c1);
-            if (B[g].empty()) continue;
-            for (uint64_t s = a; s < e; s += SUPPORT_SLICE) { items.push_back(g); items.push_back((uint32_t)(s - c0)); items.push_back((uint32_t)(std::min(e, s + SUPPORT_SLICE) - c0)); }
+        for (uint32_t g = 0; g < P.G; ++g) {
+            const uint64_t a = std::max(P.gbeg[g], C.c0), e = std::min(P.gbeg[g + 1], C.c1);
+            if (P.boff[g + 1] == P.boff[g]) continue;
+            for (uint64_t s = a; s < e; s += SUPPORT_SLICE) { items.push_back(g); items.push_back((uint32_t)(s - C.c0)); items.push_back((uint32_t)(std::min(e, s + SUPPORT_SLICE) - C.c0)); }
         }
-        if (items.empty()) continue;
+        if (items.empty()) return NGSID_OK;
         HIPCHK(ctx, d_items.reserve(items.size()));
         HIPCHK(ctx, hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, ctx->stream));
         { ProfScope ps_(ctx, "k_support_sum");
-          hipLaunchKernelGGL(k_support_sum, dim3((unsigned)(items.size() / 3), (maxb + SUPPORT_TILE - 1) / SUPPORT_TILE), dim3(SUPPORT_TILE), 0, ctx->stream,
-                             d_rec.p, stride, d_span.p, d_items.p, BB.off, d_counts.p, d_used.p); }
+          hipLaunchKernelGGL(k_support_sum, dim3((unsigned)(items.size() / 3), (P.maxb + SUPPORT_TILE - 1) / SUPPORT_TILE), dim3(SUPPORT_TILE), 0, ctx->stream,
+                             C.rec, P.stride, C.span, d_items.p, P.d_cen_off, d_counts.p, d_used.p); }
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `items` is pageable and refilled by the next chunk
-    }
+        return NGSID_OK;
+    };
+    int32_t rc = ngsid_rec_walk(ctx, centres, reads, read_order, grp_off, n_groups, prm, strand, init, start, chunk); if (rc) return rc;
+    if (!started) return NGSID_OK;
+    const uint32_t G = (uint32_t)n_groups; const uint64_t total = d_counts.n / NGSID_SUPPORT_NCOUNT;
     std::vector<u64> h_used(G);
     HIPCHK(ctx, hipMemcpyAsync(counts, d_counts.p, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(h_used.data(), d_used.p, sizeof(u64) * G, hipMemcpyDeviceToHost, ctx->stream));

@@ -107,6 +107,11 @@ def _single_below(args):
     return pipeline.SINGLE_BELOW if v is None else int(v)
 
 
+def _draft_prm(args, node_cap):
+    """the draft consensus' parameters of a CLI run"""
+    return poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=getattr(args, "poa_tile_depth", pipeline.TILE_DEPTH), band=getattr(args, "poa_band", 0), node_cap=node_cap, trim=pipeline.DRAFT_TRIM, single_below=_single_below(args))
+
+
 def _polish_prm(args, node_cap, clip):
     """the polisher's parameters of a CLI run; clip: the backbones are primer-trimmed (include/ngsid.h: aln_mode 3, trim 3).  --racon_subgraph_layers sets
     NGSID_ALN_SUBGRAPH in both flows."""
@@ -480,8 +485,7 @@ def consensus_and_polish(args, sr, work, reps, sizes, goff, list_order, abundanc
             args._pooled_early[int(reps[c])] = (c,)
     long_reads = gmax > 1000
     node_cap = 22 if long_reads else 0
-    drafts = api.poa_consensus(work, sub_off, poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=getattr(args, "poa_tile_depth", pipeline.TILE_DEPTH), band=getattr(args, "poa_band", 0), node_cap=node_cap, trim=pipeline.DRAFT_TRIM, single_below=_single_below(args)),
-                               read_order=read_order32)
+    drafts = api.poa_consensus(work, sub_off, _draft_prm(args, node_cap), read_order=read_order32)
     T["draft_consensus"] = time() - t0
     centers = [[int(sizes[c]), int(reps[c]), drafts[c], [c]] for c in range(nsel)]
     barcodes = None
@@ -600,6 +604,7 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
         racon = getattr(args, "racon", False) and args.racon_iter >= 0
         s_off = np.concatenate(([0], np.cumsum([len(x) for x in polish_lists]))).astype(np.uint64)
         counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings([m[2] for m in merged]), work, s_off, read_order=np.concatenate(polish_lists).astype(np.uint32), k=args.k, w=args.w, clip=clip)
+        counts_of = [counts[int(cen_off[x]):int(cen_off[x + 1])] for x in range(len(merged))]
         for x, (nr, c_id, center, cs) in enumerate(merged):
             tab = counts[int(cen_off[x]):int(cen_off[x + 1])]
             if racon:
@@ -609,7 +614,39 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
                 ref = os.path.join(args.outfolder, "consensus_reference_{0}".format(c_id))
                 consensus_mod.write_support_for_fasta(ref + ".fasta", ref + ".fastq", ref + ".support.tsv", tab)
         T["support"] = T.get("support", 0.0) + time() - t0
+    if getattr(args, "split_haplotypes", False):
+        _split_haplotypes(args, api, sr, work, merged, polish_lists, node_cap, clip, counts_of if getattr(args, "consensus_support", False) and merged else None, T)
     return merged
+
+
+def _split_haplotypes(args, api, sr, work, merged, polish_lists, node_cap, clip, supports, T):
+    """--split_haplotypes: the pooled reads of every final consensus split by linked variant sites (phase.build: sites from the support, genotypes, pair tables and assignment
+    on the device, ONE draft and ONE polishing call for the haplotypes of all clusters that split) -> haplotypes.tsv, one FASTA per haplotype next to the cluster's own
+    consensus file (racon_cl_id_{id}/consensus_h{j}.fasta, without --racon consensus_reference_{id}_h{j}.fasta; the cluster's header with _h{j} behind the id and the
+    haplotype's read count).  A later pass of _merge_and_polish has removed the files of the pass before."""
+    from . import phase
+    t0 = time()
+    racon = getattr(args, "racon", False) and args.racon_iter >= 0
+    host = work if work.mem == 0 else ((work.keep if isinstance(work.keep, dict) else {}).get("host") or sr.rs)          # (a set gathered in HBM has no host twin of its own: the sorted reads are it)
+    entries = phase.build(api, work, [m[2] for m in merged], polish_lists, _draft_prm(args, node_cap), _polish_prm(args, node_cap, clip) if racon else None,
+                          supports=supports, k=args.k, w=args.w, clip=clip, host_rs=host, **phase.policy_from_args(args)) if merged else []
+    ids = [m[1] for m in merged]
+    phase.write_table(os.path.join(args.outfolder, "haplotypes.tsv"), phase.table_rows(ids, entries))
+    named = []
+    for c_id, e in zip(ids, entries):
+        if e is None: continue
+        for j, seq in enumerate(e["polished"]):
+            n = int(e["n_reads"][j]); name = "consensus_cl_id_{0}_h{1}_total_supporting_reads_{2}".format(c_id, j, n)
+            if racon:
+                path = os.path.join(args.outfolder, "racon_cl_id_{0}".format(c_id), "consensus_h{0}.fasta".format(j))
+                head = "{0} LN:i:{1} RC:i:{2} XC:f:1.000000".format(name, len(seq), int(e["used"][j]))
+            else:
+                path = os.path.join(args.outfolder, "consensus_reference_{0}_h{1}.fasta".format(c_id, j)); head = name
+            with open(path, "w") as f:
+                f.write(">{0}\n{1}\n".format(head, seq))
+            named.append((name, n, seq))
+    args._hap_entries, args._hap_named = entries, named
+    T["haplotypes"] = T.get("haplotypes", 0.0) + time() - t0
 
 
 def _write_pooled(path, ids, sr, jobs=None):
@@ -674,17 +711,21 @@ def _main(args, api):
         deferred, args._deferred = getattr(args, "_deferred", []), []
         for fn_, a_, kw_ in deferred: _write(args, fn_, *a_, **kw_)
     res = _finish(args, api, st, clustered, t0)
+    if getattr(args, "split_haplotypes", False) and args.consensus:
+        res["haplotypes"] = getattr(args, "_hap_entries", [])
     if getattr(args, "reference_db", None) and args.consensus:
-        _classify_step(args, api, [(None, args.outfolder, res["centers"])], res["timings"])
+        _classify_step(args, api, [(None, args.outfolder, res["centers"])], res["timings"], extra=getattr(args, "_hap_named", None) if getattr(args, "split_haplotypes", False) else None)
     return res
 
 
-def _classify_step(args, api, groups, T):
+def _classify_step(args, api, groups, T, extra=None):
     """--reference_db: the final consensuses (the polished sequences with --racon, else the drafts) of every (sample, folder, centres) group against the reference
     library, all in one search and one verification call (classify.run) -> classification.tsv per folder (+ classification_all.tsv with samples)"""
     from . import classify
     t0 = time()
     named = [(sample, folder, [("consensus_cl_id_{0}_total_supporting_reads_{1}".format(c_id, nr), nr, seq) for nr, c_id, seq, _ in centers]) for sample, folder, centers in groups]
+    if extra:                                   # --split_haplotypes (one folder): the haplotype sequences behind the clusters' own, under their ids
+        named[0] = (named[0][0], named[0][1], named[0][2] + list(extra))
     classify.run(args, api, named)
     T["classify"] = time() - t0
 

@@ -138,13 +138,17 @@ def pooled_read_lists(merged, group_reads):
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None):
+                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
     polisher takes (Api.consensus_support); every other key is what support=False returns.
     classify=RefDb (extension; Api.refdb_build): also classify = one list of ranked hits per centre (classify.identify: its final sequence searched in the reference
-    library and verified by alignment; classify_kwargs: top_k, min_shared, min_identity, min_query_cov); every other key is what classify=None returns."""
+    library and verified by alignment; classify_kwargs: top_k, min_shared, min_identity, min_query_cov); every other key is what classify=None returns.
+    split_haplotypes=True (extension; phase.py, include/ngsid_phase.h): also haplotypes = one entry per centre, None or dict(sites, alleles [H, S], n_reads [H], assign
+    [per pooled read] int8, draft [H], polished [H], used [H] and, with classify, classify [H]): the centre's pooled reads split by linked variant sites of its final sequence, every
+    haplotype drafted and polished with the parameters of the cluster's own draft and polish (haplotype_kwargs: the policy arguments of phase.split_many); every other key
+    is what split_haplotypes=False returns."""
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
     single_below = SINGLE_BELOW if single_below is None else single_below
     T = timings if timings is not None else {}
@@ -164,6 +168,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         T["strand_merge"] = T.get("strand_merge", 0.0) + time.perf_counter() - t0
     if not do_consensus:
         if classify is not None: res["classify"] = []
+        if split_haplotypes: res["haplotypes"] = []
         return res
     t0 = time.perf_counter()
     reps, order, grp_off, counts = clusters_from_rep(rep_of)
@@ -175,6 +180,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     if not sel:
         if classify is not None: res["classify"] = []                           # no centre: nothing to name
+        if split_haplotypes: res["haplotypes"] = []
         return res
     t0 = time.perf_counter()
     sub_order, sub_off = [], [0]
@@ -184,8 +190,8 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
             b = min(b, a + max_seqs_for_consensus)                              # consensus.py:260
         sub_order.append(order[a:b]); sub_off.append(sub_off[-1] + (b - a))
     sub_order = np.concatenate(sub_order) if sub_order else np.zeros(0, np.uint32)
-    drafts = api.poa_consensus(rs, sub_off, poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=band, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below),
-                               read_order=sub_order)
+    draft_prm = poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=band, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below)
+    drafts = api.poa_consensus(rs, sub_off, draft_prm, read_order=sub_order)
     T["consensus"] = T.get("consensus", 0.0) + time.perf_counter() - t0
     t0 = time.perf_counter()
     centers = [[int(counts[ci]), int(reps[ci]), drafts[x], [ci]] for x, ci in enumerate(sel)]
@@ -193,7 +199,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
     polished = [m[2] for m in merged]
     polishing = do_polish and racon_iter > 0
-    if polishing or support:
+    if polishing or support or split_haplotypes:
         t0 = time.perf_counter()
         def group_reads(ci):                                                    # pooled reads of the merged clusters (consensus.py:208-215)
             a, b = int(grp_off[ci]), int(grp_off[ci + 1])
@@ -216,6 +222,18 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         t0 = time.perf_counter()
         res["classify"] = classify_mod.identify(api, classify, list(polished), **(classify_kwargs or {}))
         T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
+    if split_haplotypes:
+        from . import phase
+        t0 = time.perf_counter()
+        haps = phase.build(api, rs, list(polished), lists, draft_prm, pprm if polishing else None, supports=res.get("support"), k=k, w=w, **(haplotype_kwargs or {}))
+        if classify is not None:
+            seqs = [q for e in haps if e is not None for q in e["polished"]]
+            hits = classify_mod.identify(api, classify, seqs, **(classify_kwargs or {})) if seqs else []
+            x = 0
+            for e in haps:
+                if e is not None: e["classify"] = hits[x:x + len(e["polished"])]; x += len(e["polished"])
+        res["haplotypes"] = haps
+        T["haplotypes"] = T.get("haplotypes", 0.0) + time.perf_counter() - t0
     return res
 
 
