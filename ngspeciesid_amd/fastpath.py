@@ -107,6 +107,24 @@ def _single_below(args):
     return pipeline.SINGLE_BELOW if v is None else int(v)
 
 
+def _cluster_prm(args):
+    """the clustering parameters of a CLI run; a (k, w) without rows in the shared-minimizer table is the reference's KeyError (NGSpeciesID:72-77)"""
+    p_shared = select_p_table(args.k, args.w)
+    if np.isnan(p_shared).all():
+        raise KeyError("no rows in the shared-minimizer table for k=%d, w=%d (NGSpeciesID:72-77)" % (args.k, args.w))
+    return cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
+                          aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
+                          symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=p_shared)
+
+
+def _remove_consensus_files(args):
+    """what polish_sequences removes before it writes (consensus.py:195-200): the racon folders and the consensus_reference_* files of an earlier pass or run"""
+    for folder in glob.glob(os.path.join(args.outfolder, "racon_cl_id_*")):
+        shutil.rmtree(folder)
+    for file in glob.glob(os.path.join(args.outfolder, "consensus_reference_*")):
+        os.remove(file)
+
+
 def _draft_prm(args, node_cap):
     """the draft consensus' parameters of a CLI run"""
     return poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=getattr(args, "poa_tile_depth", pipeline.TILE_DEPTH), band=getattr(args, "poa_band", 0), node_cap=node_cap, trim=pipeline.DRAFT_TRIM, single_below=_single_below(args))
@@ -275,11 +293,7 @@ def cluster(sr: SortedReads, work: ReadSet, sel, args, api, work_dev=None, T=Non
         sel = sel[~too_long]
     whole = work_dev is not None and len(sel) == n and args.nr_cores <= 1       # every read in one call: the device-resident set as it is
     if precomputed is None: work = work_dev if whole else subset_reads(work if work is not None else sr.rs, sel)
-    prm = cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
-                         aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
-                         symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=select_p_table(args.k, args.w))
-    if np.isnan(select_p_table(args.k, args.w)).all():
-        raise KeyError("no rows in the shared-minimizer table for k=%d, w=%d (NGSpeciesID:72-77)" % (args.k, args.w))
+    prm = _cluster_prm(args)
     T = T if T is not None else {}
     t1 = time()
     fut = getattr(sr, "rank_all", None)
@@ -438,10 +452,7 @@ def consensus_and_polish(args, sr, work, reps, sizes, goff, list_order, abundanc
     logging.debug(f"{singles} singletons were discarded")
     logging.debug(f"{len(disc)} clusters were discarded due to not passing the abundance_cutoff: a total of {int(disc.sum())} reads were discarded. "
                   f"Highest abundance among them: {int(disc.max()) if len(disc) else 0} reads.")
-    for folder in glob.glob(os.path.join(args.outfolder, "racon_cl_id_*")):
-        shutil.rmtree(folder)
-    for file in glob.glob(os.path.join(args.outfolder, "consensus_reference_*")):
-        os.remove(file)
+    _remove_consensus_files(args)
     if nsel == 0:
         return []
     T = T if T is not None else {}
@@ -474,7 +485,7 @@ def consensus_and_polish(args, sr, work, reps, sizes, goff, list_order, abundanc
         logging.warning("%d read(s) longer than %d bases (up to %d) are left out of the consensus and polishing of their clusters (they stay in final_clusters.tsv and in the pooled read files)", ndrop, MAX_CONSENSUS_LEN, gmax)
         args._overlong = True
         gmax = int(max(sr.lens[cg].max() for cg in cgroups))
-    sub_off = np.concatenate(([0], np.cumsum([len(g) for g in cgroups]))).astype(np.uint64)
+    sub_off = pipeline.group_offsets(cgroups).astype(np.uint64)
     read_order = np.concatenate(cgroups); read_order32 = read_order.astype(np.uint32)
     args._merge_passes = 0                                                 # (a reused args namespace must not look like a later pass)
     args._pooled_early = {}
@@ -511,10 +522,7 @@ def consensus_and_polish(args, sr, work, reps, sizes, goff, list_order, abundanc
 def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T, polish_backbones=None, used_out=None, clip=False):
     """detect_reverse_complements + polish_sequences (consensus.py:148-183,186-246): centers = [n_reads, c_id, sequence, cluster indices]"""
     t0 = time()
-    for folder in glob.glob(os.path.join(args.outfolder, "racon_cl_id_*")):
-        shutil.rmtree(folder)
-    for file in glob.glob(os.path.join(args.outfolder, "consensus_reference_*")):
-        os.remove(file)
+    _remove_consensus_files(args)
     T["rc_merge_cleanup"] = T.get("rc_merge_cleanup", 0.0) + time() - t0; t1 = time()
     merged = pipeline.detect_reverse_complements(api, centers, args.rc_identity_threshold)
     T["rc_merge_detect"] = T.get("rc_merge_detect", 0.0) + time() - t1
@@ -567,7 +575,7 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
             if early: early[int(c_id)] = tuple(cs)
     T["rc_merge_write_pooled_reads"] = T.get("rc_merge_write_pooled_reads", 0.0) + time() - t0; t0 = time()
     if getattr(args, "racon", False) and args.racon_iter >= 0:
-        p_off = np.concatenate(([0], np.cumsum([len(x) for x in polish_lists]))).astype(np.uint64)
+        p_off = pipeline.group_offsets(polish_lists).astype(np.uint64)
         bb = ReadSet.from_strings([(polish_backbones or {}).get(m[1], m[2]) for m in merged])
         prm = _polish_prm(args, node_cap, clip)
         ro = np.concatenate(polish_lists).astype(np.uint32)
@@ -602,7 +610,7 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
         # --consensus_support: the read support of every base of the sequences just written, over the reads the polisher takes; clip as in the polisher (primer-trimmed flows)
         t0 = time()
         racon = getattr(args, "racon", False) and args.racon_iter >= 0
-        s_off = np.concatenate(([0], np.cumsum([len(x) for x in polish_lists]))).astype(np.uint64)
+        s_off = pipeline.group_offsets(polish_lists).astype(np.uint64)
         counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings([m[2] for m in merged]), work, s_off, read_order=np.concatenate(polish_lists).astype(np.uint32), k=args.k, w=args.w, clip=clip)
         counts_of = [counts[int(cen_off[x]):int(cen_off[x + 1])] for x in range(len(merged))]
         for x, (nr, c_id, center, cs) in enumerate(merged):
@@ -744,7 +752,7 @@ def _main_samples(args, api):
     """--fastq_dir: every file of the folder is one sample with its own output folder, holding what a run of --fastq on that file writes.  The files are ingested and scored one
     after the other in this context (score_and_sort; the per-sample selections --m / --s / --sample_size / --top_reads apply per sample, a random --sample_size draws in sample
     order), the selected reads of ALL samples are clustered in one segmented call (include/ngsid_batch.h), then every sample runs the writers and the consensus stages of a
-    single run on its slice.  (The consensus stages still run per sample here: pipeline.run_hot_path_samples is the array form that batches them too.)"""
+    single run on its slice.  (The consensus stages run per sample here, through the command line's own flow (consensus_and_polish); pipeline.run_hot_path_samples, the array form, batches them across the samples.)"""
     import copy
     T = {}
     subs = []
@@ -763,11 +771,7 @@ def _main_samples(args, api):
         off = np.zeros(len(lens) + 1, dtype=np.uint64); off[1:] = np.cumsum(lens)
         seg = np.zeros(len(rs) + 1, dtype=np.uint64); seg[1:] = np.cumsum([x.n for x in rs])
         allr = ReadSet(np.concatenate([x.seq for x in rs]), np.concatenate([x.qual for x in rs]), off)
-        prm = cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
-                             aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
-                             symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=select_p_table(args.k, args.w))
-        if np.isnan(select_p_table(args.k, args.w)).all():
-            raise KeyError("no rows in the shared-minimizer table for k=%d, w=%d (NGSpeciesID:72-77)" % (args.k, args.w))
+        prm = _cluster_prm(args)
         logging.info("Starting Clustering: %d reads of %d samples" % (allr.n, len(subs)))
         rep, herr, status, cnt = api.cluster_greedy_segmented(allr, prm, seg, acc_rank=np.concatenate([x[1] for x in ins]).astype(np.uint32)) if allr.n else (np.zeros(0, np.int32), np.zeros(0), np.zeros(0, np.uint8), np.zeros((len(rs), 4), np.uint64))
     finally:
@@ -842,9 +846,7 @@ def _finish(args, api, st, clustered, t0):
     if getattr(args, "strand_aware", False) and len(sel) == sr.n:
         # extension (strand.py): reverse-complement clusters are joined here, before the cluster files are written and before any consensus work
         from . import strand
-        prm = cluster_params(k=args.k, w=args.w, min_shared=args.min_shared, min_fraction=args.min_fraction, mapped_threshold=args.mapped_threshold,
-                             aligned_threshold=args.aligned_threshold, min_prob_no_hits=args.min_prob_no_hits,
-                             symmetric=bool(getattr(args, "symmetric_map_align_thresholds", False)), p_shared=select_p_table(args.k, args.w))
+        prm = _cluster_prm(args)
         if work is None: work = sr.rs
         rep_of, flip, pos, sinfo = strand.strand_merge(api, work, rep_of, sr.score, prm, min_size=max(2, abundance_cutoff // 2), pos=pos)
         logging.debug("strand-aware merge: %d of %d candidate clusters joined their reverse complement" % (sinfo["merged"], sinfo["candidates"]))

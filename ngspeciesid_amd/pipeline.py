@@ -85,15 +85,7 @@ def _rc_decide(centers, ncols, nmatch, rc_identity_threshold):
 def detect_reverse_complements(api: Api, centers, rc_identity_threshold):
     """consensus.detect_reverse_complements (consensus.py:148-183): centers = [n_reads, c_id, seq, groups(list of cluster ids)].
     Identity = matching columns / alignment columns of the semi-global alignment (open 3, ext 1, +2/-2), max over fw / rc."""
-    n = len(centers)
-    if n <= 1:
-        return [[c[0], c[1], c[2], list(c[3])] for c in centers]
-    seqs = [c[2] for c in centers]
-    rcs = [revcomp_str(s) for s in seqs]
-    q = ReadSet.from_strings(seqs); t = ReadSet.from_strings(seqs + rcs)
-    qi, ti = _rc_pairs(n)
-    score, ncols, nmatch, _ = api.sg_align_batch(q, t, qi, ti, 3, 1, 2, -2, 13, None)
-    return _rc_decide(centers, ncols, nmatch, rc_identity_threshold)
+    return detect_reverse_complements_samples(api, [centers], rc_identity_threshold)[0]
 
 
 def detect_reverse_complements_samples(api: Api, centers_per_sample, rc_identity_threshold):
@@ -135,6 +127,105 @@ def pooled_read_lists(merged, group_reads):
     return out
 
 
+def group_offsets(lists):
+    """group offsets of the concatenation of lists: [0, len(lists[0]), len(lists[0]) + len(lists[1]), ...]"""
+    return np.concatenate(([0], np.cumsum([len(x) for x in lists])))
+
+
+def _deal(flat, sizes):
+    """a flat list of results cut back into consecutive runs of sizes[0], sizes[1], ... entries"""
+    out, x = [], 0
+    for n in sizes:
+        out.append(flat[x:x + n]); x += n
+    return out
+
+
+def _support_of(api, rs, seqs, lists, k, w):
+    """Api.consensus_support of the sequences seqs over their read lists, ONE call -> one [len, 8] array per sequence"""
+    if not seqs:
+        return []
+    counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings(seqs), rs, group_offsets(lists), read_order=np.concatenate(lists), k=k, w=w)
+    return [counts[int(cen_off[i]):int(cen_off[i + 1])] for i in range(len(seqs))]
+
+
+def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs):
+    """Everything behind the clustering call, once for a list of samples: reads [seg_off[s], seg_off[s+1]) of rs are sample s, out[s] is its result dict (rep_of in read
+    indices local to the sample) and bands[s] the band of its draft and polishing calls.  Per sample the cluster table and the selection with the sample's own cut-off, the
+    reverse-complement bookkeeping and the pooled read lists; for all samples ONE alignment call, one consensus_support call and one search, and per distinct band one draft
+    and one polishing call.  Fills centers (and support / classify, when asked for) into the dicts of the samples that have a centre above their cut-off and leaves the other
+    dicts as they are.  -> None when no sample has one, else (polished, pooled, prms): polished[s] the final sequences and pooled[s] the polisher's read lists (read numbers
+    of rs) of every centre of sample s, prms[band] the (draft, polish or None) parameter structs of that band's calls."""
+    tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
+    single_below = SINGLE_BELOW if single_below is None else single_below
+    # ---- per-sample cluster tables and selections
+    t0 = time.perf_counter()
+    tab = {}                                                                    # the samples with a centre: s -> (reps, order, grp_off, counts, sel), order in read numbers of rs
+    for s, o in enumerate(out):
+        a0, n = int(seg_off[s]), int(seg_off[s + 1]) - int(seg_off[s])
+        if n == 0:
+            continue
+        reps, order, grp_off, counts = clusters_from_rep(o["rep_of"])
+        sel = select_centers(reps, counts, score[a0:a0 + n], int(abundance_ratio * n))      # NGSpeciesID:65, per sample
+        if sel:
+            tab[s] = (reps, (order + np.uint32(a0)) if a0 else order, grp_off, counts, sel)  # (a sample that starts at read 0 is not copied: a million indices per step in bench.py)
+    if _TOUCH and hasattr(api, "ctx"):
+        import ctypes as _C
+        api.lib.ngsid_ctx_option(api.ctx, b"touch", _C.c_int64(1))
+    T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
+    if not tab:
+        return None
+    def cluster_reads(s, ci):                                                   # the reads of cluster ci of sample s that the consensus stages see
+        _, order, grp_off = tab[s][:3]
+        a, b = int(grp_off[ci]), int(grp_off[ci + 1])
+        if max_seqs_for_consensus >= 0:
+            b = min(b, a + max_seqs_for_consensus)                              # consensus.py:260; the pooled file is built from the truncated reads_c_id files too
+        return order[a:b]
+    by_band = {bnd: [s for s in tab if bands[s] == bnd] for bnd in sorted({bands[s] for s in tab})}      # the samples that share their draft and polishing calls
+    # ---- draft consensus: one call per band
+    t0 = time.perf_counter()
+    drafts, prms = {}, {}
+    for bnd, ss in by_band.items():
+        keys = [(s, ci) for s in ss for ci in tab[s][4]]
+        parts = [cluster_reads(s, ci) for s, ci in keys]
+        prms[bnd] = [poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below), None]
+        drafts.update(zip(keys, api.poa_consensus(rs, group_offsets(parts), prms[bnd][0], read_order=np.concatenate(parts))))
+    T["consensus"] = T.get("consensus", 0.0) + time.perf_counter() - t0
+    # ---- reverse-complement detection: one alignment call, pairs within a sample only
+    t0 = time.perf_counter()
+    centers = [[[int(tab[s][3][ci]), int(tab[s][0][ci]), drafts[(s, ci)], [ci]] for ci in tab[s][4]] for s in tab]
+    merged = dict(zip(tab, detect_reverse_complements_samples(api, centers, rc_identity_threshold)))
+    T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
+    # ---- pooled read lists (consensus.py:208-215) and polishing: one call per band
+    t0 = time.perf_counter()
+    pooled = {s: pooled_read_lists(merged[s], lambda ci, s=s: cluster_reads(s, ci)) for s in tab}
+    polished = {s: [m[2] for m in merged[s]] for s in tab}
+    if do_polish and racon_iter > 0:
+        for bnd, ss in by_band.items():
+            lists = [l for s in ss for l in pooled[s]]
+            prms[bnd][1] = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
+            pol, _ = api.polish(ReadSet.from_strings([m[2] for s in ss for m in merged[s]]), rs, group_offsets(lists), prms[bnd][1], read_order=np.concatenate(lists))      # (dealt to two contexts when it pays: _capi.Api lanes)
+            polished.update(zip(ss, _deal(pol, [len(merged[s]) for s in ss])))
+        T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
+    for s in tab:
+        reps = tab[s][0]
+        out[s]["centers"] = [(m[0], m[1], m[2], polished[s][i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged[s])]
+    # ---- read support and classification of the final sequences: one call each
+    flat = [q for s in tab for q in polished[s]]; sizes = [len(merged[s]) for s in tab]
+    if support:
+        t0 = time.perf_counter()
+        for s, part in zip(tab, _deal(_support_of(api, rs, flat, [l for s in tab for l in pooled[s]], k, w), sizes)):
+            out[s]["support"] = part
+        T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
+    if classify is not None:
+        from . import classify as classify_mod
+        t0 = time.perf_counter()
+        for s, part in zip(tab, _deal(classify_mod.identify(api, classify, flat, **(classify_kwargs or {})), sizes)):
+            out[s]["classify"] = part
+        T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
+    return polished, pooled, prms
+
+
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
@@ -149,8 +240,6 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     [per pooled read] int8, draft [H], polished [H], used [H] and, with classify, classify [H]): the centre's pooled reads split by linked variant sites of its final sequence, every
     haplotype drafted and polished with the parameters of the cluster's own draft and polish (haplotype_kwargs: the policy arguments of phase.split_many); every other key
     is what split_haplotypes=False returns."""
-    tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
-    single_below = SINGLE_BELOW if single_below is None else single_below
     T = timings if timings is not None else {}
     t0 = time.perf_counter()
     prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
@@ -166,87 +255,43 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
             rs = strand.orient_reads(rs, flip)                                   # the consensus stages see every cluster in one orientation
         res.update(rep_of=rep_of, flip=flip, strand_info=sinfo)
         T["strand_merge"] = T.get("strand_merge", 0.0) + time.perf_counter() - t0
+    if classify is not None: res["classify"] = []                               # what stays without a centre: nothing to name, nothing to split
+    if split_haplotypes: res["haplotypes"] = []
     if not do_consensus:
-        if classify is not None: res["classify"] = []
-        if split_haplotypes: res["haplotypes"] = []
         return res
-    t0 = time.perf_counter()
-    reps, order, grp_off, counts = clusters_from_rep(rep_of)
-    if _TOUCH and hasattr(api, "ctx"):
-        import ctypes as _C
-        api.lib.ngsid_ctx_option(api.ctx, b"touch", _C.c_int64(1))
-    cutoff = int(abundance_ratio * n)                                           # NGSpeciesID:65
-    sel = select_centers(reps, counts, score, cutoff)
-    T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
-    if not sel:
-        if classify is not None: res["classify"] = []                           # no centre: nothing to name
-        if split_haplotypes: res["haplotypes"] = []
-        return res
-    t0 = time.perf_counter()
-    sub_order, sub_off = [], [0]
-    for ci in sel:
-        a, b = int(grp_off[ci]), int(grp_off[ci + 1])
-        if max_seqs_for_consensus >= 0:
-            b = min(b, a + max_seqs_for_consensus)                              # consensus.py:260
-        sub_order.append(order[a:b]); sub_off.append(sub_off[-1] + (b - a))
-    sub_order = np.concatenate(sub_order) if sub_order else np.zeros(0, np.uint32)
-    draft_prm = poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=band, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below)
-    drafts = api.poa_consensus(rs, sub_off, draft_prm, read_order=sub_order)
-    T["consensus"] = T.get("consensus", 0.0) + time.perf_counter() - t0
-    t0 = time.perf_counter()
-    centers = [[int(counts[ci]), int(reps[ci]), drafts[x], [ci]] for x, ci in enumerate(sel)]
-    merged = detect_reverse_complements(api, centers, rc_identity_threshold)
-    T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
-    polished = [m[2] for m in merged]
-    polishing = do_polish and racon_iter > 0
-    if polishing or support or split_haplotypes:
-        t0 = time.perf_counter()
-        def group_reads(ci):                                                    # pooled reads of the merged clusters (consensus.py:208-215)
-            a, b = int(grp_off[ci]), int(grp_off[ci + 1])
-            if max_seqs_for_consensus >= 0:
-                b = min(b, a + max_seqs_for_consensus)                          # the pooled file is built from the truncated reads_c_id files
-            return order[a:b]
-        lists = pooled_read_lists(merged, group_reads)
-    if polishing:
-        pprm = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=band, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
-        p_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
-        polished, used = api.polish(ReadSet.from_strings([m[2] for m in merged]), rs, p_off, pprm, read_order=np.concatenate(lists))      # (dealt to two contexts when it pays: _capi.Api lanes)
-        T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
-    res["centers"] = [(m[0], m[1], m[2], polished[i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged)]
-    if support:
-        t0 = time.perf_counter()
-        res["support"] = _support_of(api, rs, list(polished), lists, k, w)
-        T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
-    if classify is not None:
-        from . import classify as classify_mod
-        t0 = time.perf_counter()
-        res["classify"] = classify_mod.identify(api, classify, list(polished), **(classify_kwargs or {}))
-        T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
-    if split_haplotypes:
+    # one sample, reads [0, n); band goes through as it is: for band <= 0 the library applies the POA_BAND64_MAXLEN rule to the reads of the call, which here are the sample's
+    # (reading the lengths of a device-resident set here would cost a copy of its offsets to the host in every step)
+    stages = _consensus_stages(api, rs, score, [0, n], [res], [band], T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
+                               do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs)
+    if split_haplotypes and stages is not None:
         from . import phase
         t0 = time.perf_counter()
-        haps = phase.build(api, rs, list(polished), lists, draft_prm, pprm if polishing else None, supports=res.get("support"), k=k, w=w, **(haplotype_kwargs or {}))
+        polished, pooled, prms = stages
+        haps = phase.build(api, rs, list(polished[0]), pooled[0], *prms[band], supports=res.get("support"), k=k, w=w, **(haplotype_kwargs or {}))
         if classify is not None:
+            from . import classify as classify_mod
             seqs = [q for e in haps if e is not None for q in e["polished"]]
             hits = classify_mod.identify(api, classify, seqs, **(classify_kwargs or {})) if seqs else []
-            x = 0
-            for e in haps:
-                if e is not None: e["classify"] = hits[x:x + len(e["polished"])]; x += len(e["polished"])
+            for e, part in zip(haps, _deal(hits, [0 if e is None else len(e["polished"]) for e in haps])):
+                if e is not None: e["classify"] = part
         res["haplotypes"] = haps
         T["haplotypes"] = T.get("haplotypes", 0.0) + time.perf_counter() - t0
     return res
 
 
-def _support_of(api, rs, seqs, lists, k, w):
-    """Api.consensus_support of the sequences seqs over their read lists, ONE call -> one [len, 8] array per sequence"""
-    if not seqs:
-        return []
-    s_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
-    counts, cen_off, _, _ = api.consensus_support(ReadSet.from_strings(seqs), rs, s_off, read_order=np.concatenate(lists).astype(np.uint32), k=k, w=w)
-    return [counts[int(cen_off[i]):int(cen_off[i + 1])] for i in range(len(seqs))]
-
-
 POA_BAND64_MAXLEN = 3000       # include/ngsid.h NGSID_POA_BAND64_MAXLEN: band <= 0 means 64 columns iff every read of the call has at most this many bases, else 128
+
+
+def _bands_alone(rs, so, band):
+    """the band every sample [so[s], so[s+1]) of rs gets when it is run alone: band when it is given, else the library's rule for band <= 0 on the sample's own reads"""
+    if band > 0:
+        return [band] * (len(so) - 1)
+    if rs.mem == 0:
+        lens = np.diff(rs.off.astype(np.int64))
+    else:
+        kp = rs.keep if isinstance(rs.keep, dict) else {}
+        lens = np.diff(kp["host"].off.astype(np.int64)) if kp.get("host") is not None else np.diff(kp["off"].cpu().numpy().astype(np.int64))
+    return [64 if a == b or int(lens[a:b].max()) <= POA_BAND64_MAXLEN else 128 for a, b in zip(so[:-1], so[1:])]
 
 
 def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
@@ -261,8 +306,6 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
-    tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
-    single_below = SINGLE_BELOW if single_below is None else single_below
     T = timings if timings is not None else {}
     so = np.asarray(seg_off, dtype=np.int64); ns = len(so) - 1
     t0 = time.perf_counter()
@@ -270,85 +313,13 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     rep_of, herr, status, counters = api.cluster_greedy_segmented(rs, prm, so.astype(np.uint64), acc_rank=acc_rank)
     T["cluster"] = T.get("cluster", 0.0) + time.perf_counter() - t0
     out = [dict(rep_of=rep_of[so[s]:so[s + 1]] - np.int32(so[s]), status=status[so[s]:so[s + 1]], counters=counters[s], hpc_err=herr[so[s]:so[s + 1]], centers=[]) for s in range(ns)]
-    if not do_consensus:
-        if classify is not None:
-            for o in out: o["classify"] = []
-        return out
-    # ---- per-sample cluster tables and selections (local indices), the samples grouped by band
-    t0 = time.perf_counter()
-    if rs.mem == 0:
-        lens = np.diff(rs.off.astype(np.int64))
-    else:
-        kp = rs.keep if isinstance(rs.keep, dict) else {}
-        lens = np.diff(kp["host"].off.astype(np.int64)) if kp.get("host") is not None else np.diff(kp["off"].cpu().numpy().astype(np.int64))
-    tab = [None] * ns
-    for s in range(ns):
-        a0, n = int(so[s]), int(so[s + 1] - so[s])
-        if n == 0:
-            continue
-        reps, order, grp_off, counts = clusters_from_rep(out[s]["rep_of"])
-        sel = select_centers(reps, counts, score[a0:a0 + n], int(abundance_ratio * n))      # NGSpeciesID:65, per sample
-        if sel:
-            bnd = band if band > 0 else (64 if int(lens[a0:a0 + n].max()) <= POA_BAND64_MAXLEN else 128)
-            tab[s] = (reps, order, grp_off, counts, sel, bnd)
-    T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
-    def cluster_reads(s, ci):                                                   # global read numbers of cluster ci of sample s, truncated like run_hot_path does
-        _, order, grp_off = tab[s][:3]
-        a, b = int(grp_off[ci]), int(grp_off[ci + 1])
-        if max_seqs_for_consensus >= 0:
-            b = min(b, a + max_seqs_for_consensus)                              # consensus.py:260
-        return order[a:b].astype(np.int64) + int(so[s])
-    live = [s for s in range(ns) if tab[s] is not None]
-    bands = sorted({tab[s][5] for s in live})
-    # ---- draft consensus: one call per band
-    t0 = time.perf_counter()
-    drafts = {}
-    for bnd in bands:
-        keys = [(s, ci) for s in live if tab[s][5] == bnd for ci in tab[s][4]]
-        parts = [cluster_reads(s, ci) for s, ci in keys]
-        sub_off = np.concatenate(([0], np.cumsum([len(x) for x in parts])))
-        res = api.poa_consensus(rs, sub_off, poa_params(mode=POA_LOCAL, match=5, mismatch=-4, gap=-2, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=DRAFT_TRIM if draft_trim is None else draft_trim, single_below=single_below),
-                                read_order=np.concatenate(parts).astype(np.uint32))
-        drafts.update(zip(keys, res))
-    T["consensus"] = T.get("consensus", 0.0) + time.perf_counter() - t0
-    # ---- reverse-complement detection: one alignment call, pairs within a sample only
-    t0 = time.perf_counter()
-    centers = [[[int(tab[s][3][ci]), int(tab[s][0][ci]), drafts[(s, ci)], [ci]] for ci in tab[s][4]] for s in live]
-    merged = dict(zip(live, detect_reverse_complements_samples(api, centers, rc_identity_threshold)))
-    T["rc_merge"] = T.get("rc_merge", 0.0) + time.perf_counter() - t0
-    polished = {s: [m[2] for m in merged[s]] for s in live}
-    polishing = do_polish and racon_iter > 0
-    if polishing or support:
-        pooled = {s: pooled_read_lists(merged[s], lambda ci, s=s: cluster_reads(s, ci)) for s in live}
-    if polishing:
-        t0 = time.perf_counter()
-        for bnd in bands:
-            ss = [s for s in live if tab[s][5] == bnd]
-            lists = [l for s in ss for l in pooled[s]]
-            pprm = polish_params(iters=racon_iter, k=k, w=w, tile_depth=tile_depth, band=bnd, node_cap=node_cap, trim=polish_trim, aln_mode=polish_aln_mode, stop_when_stable=polish_stop_when_stable, single_below=single_below)
-            p_off = np.concatenate(([0], np.cumsum([len(x) for x in lists])))
-            pol, _ = api.polish(ReadSet.from_strings([m[2] for s in ss for m in merged[s]]), rs, p_off, pprm, read_order=np.concatenate(lists).astype(np.uint32))
-            x = 0
-            for s in ss:
-                polished[s] = pol[x:x + len(merged[s])]; x += len(merged[s])
-        T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
-    for s in live:
-        reps = tab[s][0]
-        out[s]["centers"] = [(m[0], m[1], m[2], polished[s][i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged[s])]
-    if support:
-        t0 = time.perf_counter()
-        sup = _support_of(api, rs, [q for s in live for q in polished[s]], [l for s in live for l in pooled[s]], k, w)
-        x = 0
-        for s in live:
-            out[s]["support"] = sup[x:x + len(merged[s])]; x += len(merged[s])
-        T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
     if classify is not None:
-        from . import classify as classify_mod
-        t0 = time.perf_counter()
-        hits = classify_mod.identify(api, classify, [q for s in live for q in polished[s]], **(classify_kwargs or {}))
-        for o in out: o["classify"] = []                                        # samples without a centre
-        x = 0
-        for s in live:
-            out[s]["classify"] = hits[x:x + len(merged[s])]; x += len(merged[s])
-        T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
+        for o in out: o["classify"] = []                                        # what stays for a sample without a centre
+    if not do_consensus:
+        return out
+    t0 = time.perf_counter()
+    bands = _bands_alone(rs, so, band)
+    T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
+    _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs)
     return out
