@@ -258,13 +258,13 @@ static int32_t launch16(ngsid_ctx* ctx, const AlignJob& job, const StripPlan& L,
 // Paired kernel k_sg_align16p<R>: one wave per work item of two pairs, both traceback halves in one scratch slice (words_half words each); in LDS two targets,
 // two queries and a 4 KB traceback block
 struct PairedPlan { uint64_t words_half, nwaves; uint32_t seq_lds; size_t lds; };
-template <int R>
+template <int R, bool SKEW>
 static int32_t plan16p(ngsid_ctx* ctx, uint64_t npairs, uint32_t max_tlen, PairedPlan* L)
 {
     L->seq_lds = (std::max<uint32_t>(max_tlen, 64u * R) + 15u) & ~15u;
     L->lds = 4 * (size_t)L->seq_lds + 4096;
     L->words_half = ((uint64_t)max_tlen + 63) * 64;
-    return plan_waves(ctx, (const void*)k_sg_align16p<R>, 1, L->lds, (npairs + 1) / 2, 2 * L->words_half * 8, &L->nwaves);
+    return plan_waves(ctx, (const void*)k_sg_align16p<R, SKEW>, 1, L->lds, (npairs + 1) / 2, 2 * L->words_half * 8, &L->nwaves);
 }
 
 // ---- binning of one length class by (n - 1) mod R for the paired kernel.  `list` / `count` = the class list of k_pair_classes (queries of 513 - 896 bases: n >= 1).
@@ -309,8 +309,8 @@ void k_bin_scatter(const uint32_t* __restrict__ list, const uint32_t* __restrict
 }
 
 // length class `cls` of a partitioned batch (class lists of ngsid_partition_pairs) through the paired kernel on stream st; tb = this launch's slice of the
-// traceback scratch (plan16p)
-template <int R>
+// traceback scratch (plan16p).  SKEW: the instance with the skewed gap frame (the caller has checked ngsid_align16p_skew_exact)
+template <int R, bool SKEW>
 static int32_t launch16p(ngsid_ctx* ctx, const AlignJob& job, int cls, uint32_t max_tlen, hipStream_t st, uint64_t* tb)
 {
     const uint64_t n = job.npairs;
@@ -327,10 +327,10 @@ static int32_t launch16p(ngsid_ctx* ctx, const AlignJob& job, int cls, uint32_t 
     hipLaunchKernelGGL(k_bin_offsets, dim3(1), dim3(64), 0, st, (const uint32_t*)bin_cnt, bin_off, item_off, cursor);
     hipLaunchKernelGGL(k_bin_scatter, dim3(nb), dim3(256), 0, st, list, count, (const uint8_t*)bin_of, (const uint32_t*)bin_off, cursor, sorted);
     HIPCHK(ctx, hipGetLastError());
-    PairedPlan L; int32_t rc = plan16p<R>(ctx, n, max_tlen, &L); if (rc) return rc;
-    HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sg_align16p<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    PairedPlan L; int32_t rc = plan16p<R, SKEW>(ctx, n, max_tlen, &L); if (rc) return rc;
+    HIPCHK(ctx, hipFuncSetAttribute((const void*)k_sg_align16p<R, SKEW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
     { ProfScope ps_(ctx, st == ctx->stream ? "k_sg_align" : "k_sg_align_side", st);
-      hipLaunchKernelGGL((k_sg_align16p<R>), dim3((unsigned)L.nwaves), dim3(64), L.lds, st, job, (const uint32_t*)sorted, (const uint32_t*)bin_off, (const uint32_t*)item_off, tb, L.words_half, L.seq_lds, wctr); }
+      hipLaunchKernelGGL((k_sg_align16p<R, SKEW>), dim3((unsigned)L.nwaves), dim3(64), L.lds, st, job, (const uint32_t*)sorted, (const uint32_t*)bin_off, (const uint32_t*)item_off, tb, L.words_half, L.seq_lds, wctr); }
     HIPCHK(ctx, hipGetLastError());
     return NGSID_OK;
 }
@@ -394,8 +394,9 @@ int32_t ngsid_partition_pairs(ngsid_ctx* ctx, const AlignJob& job, uint32_t long
 }
 
 // A partitioned batch: one launch per length class that has pairs, the classes of up to 896 bases through the paired kernel unless
-// ngsid_ctx_option("align_paired", 0).  long_len > 0: max_qlen / max_tlen are clamped to it, the longer pairs land in list NCLS for the caller.
-static int32_t launch_classes(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t min_qlen, uint32_t long_len)
+// ngsid_ctx_option("align_paired", 0); the paired kernel in its skewed-frame instances where they are exact for this call (ngsid_align16p_skew_exact) unless
+// ngsid_ctx_option("align_skew", 0).  long_len > 0: max_qlen / max_tlen are clamped to it, the longer pairs land in list NCLS for the caller.
+static int32_t launch_classes(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open, uint32_t min_qlen, uint32_t long_len)
 {
     const uint64_t n = job.npairs;
     { int32_t rc = ngsid_partition_pairs(ctx, job, long_len); if (rc) return rc; }
@@ -403,6 +404,7 @@ static int32_t launch_classes(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
     // pairs costs the latency of one pair, which would otherwise be paid once per class and call.  Every launch has its own scratch slice.
     { int32_t rc = ngsid_side_streams(ctx); if (rc) return rc; }
     const bool paired = ngsid_opt(ctx, "align_paired", 1) != 0;
+    const bool skew = ngsid_opt(ctx, "align_skew", 1) != 0 && ngsid_align16p_skew_exact(job, max_qlen, max_tlen, max_open);
     bool used[NCLS]; uint64_t tbo[NCLS + 1] = {0}, bo[NCLS + 1] = {0};
     for (int c = 0; c < NCLS; ++c) {
         used[c] = (c == 0 || max_qlen > kAlignClass[c - 1].bound) && min_qlen <= std::min(max_qlen, kAlignClass[c].bound);
@@ -411,7 +413,7 @@ static int32_t launch_classes(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
             int32_t rc = with_class(c, [&](auto C) -> int32_t {
                 constexpr AlignClass K = kAlignClass[decltype(C)::value];
                 if constexpr (K.r > 0) {
-                    if (paired) { PairedPlan P; int32_t r = plan16p<K.r>(ctx, n, max_tlen, &P); words = P.nwaves * 2 * P.words_half; return r; }
+                    if (paired) { PairedPlan P; int32_t r = skew ? plan16p<K.r, true>(ctx, n, max_tlen, &P) : plan16p<K.r, false>(ctx, n, max_tlen, &P); words = P.nwaves * 2 * P.words_half; return r; }
                 }
                 StripPlan L; int32_t r = plan16<K.rp>(ctx, n, std::min(max_qlen, K.bound), max_tlen, &L); words = L.nwaves * L.words; bwords = L.nwaves * 2ull * L.bnd_stride; return r;
             });
@@ -431,7 +433,7 @@ static int32_t launch_classes(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
             int32_t rc = with_class(c, [&](auto C) -> int32_t {
                 constexpr AlignClass K = kAlignClass[decltype(C)::value];
                 if constexpr (K.r > 0) {
-                    if (paired) return launch16p<K.r>(ctx, job, c, max_tlen, st, ctx->tb.p + tbo[c]);
+                    if (paired) return skew ? launch16p<K.r, true>(ctx, job, c, max_tlen, st, ctx->tb.p + tbo[c]) : launch16p<K.r, false>(ctx, job, c, max_tlen, st, ctx->tb.p + tbo[c]);
                 }
                 AlignJob jc = job; jc.pair_list = ctx->aln_cls.p + (size_t)c * n; jc.npairs_dev = ctx->aln_ctr.p + 8 + c;
                 StripPlan L; int32_t r = plan16<K.rp>(ctx, n, std::min(max_qlen, K.bound), max_tlen, &L); if (r) return r;
@@ -448,6 +450,17 @@ bool ngsid_align16_applicable(const AlignJob& job, uint32_t max_qlen, uint32_t m
 {
     return max_qlen <= NGSID_ALIGN16_MAXLEN && max_tlen <= NGSID_ALIGN16_MAXLEN && job.match >= 0 && job.match <= 4 && job.mismatch <= 0 && job.mismatch >= -8 &&
            job.ext >= 0 && job.ext <= 4 && max_open >= 0 && max_open <= 16;
+}
+
+// The skewed-frame instances of the paired kernel (k_align16p.hip) are exact while no difference of two values of a DP cell leaves int16.  The frame adds up to
+// (n + m) ext to a value, so the bound depends on the lengths of THIS call: the longest query that reaches the paired kernel (its classes end at 896 bases) and the
+// longest target.  With ext <= 1 it holds for everything ngsid_align16_applicable accepts; a call it does not hold for runs the plain instances.
+bool ngsid_align16p_skew_exact(const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open)
+{
+    uint32_t qmax = 0;
+    for (int c = 0; c < NCLS; ++c) if (kAlignClass[c].r > 0) qmax = std::max(qmax, kAlignClass[c].bound);
+    return ngsid_align16_applicable(job, max_qlen, max_tlen, max_open) &&
+           sg16p_flag_span(job.match, job.ext, max_open, std::min(max_qlen, qmax), max_tlen, true) < 32768;
 }
 
 // measurement (profiling on): DP cells of the call = sum of n x m over its pairs, one atomic per workgroup
@@ -482,7 +495,7 @@ int32_t ngsid_launch_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qle
         const bool has_long = max_qlen > q16 || max_tlen > t16;
         if (ngsid_align16_applicable(job, q16, t16, max_open)) {
             if (job.npairs >= 4096 && q16 > 256 && !job.pair_list && !ngsid_opt(ctx, "align_noclass", 0)) {
-                int32_t rc = launch_classes(ctx, job, q16, t16, min_qlen, has_long ? NGSID_ALIGN16_MAXLEN : 0);
+                int32_t rc = launch_classes(ctx, job, q16, t16, max_open, min_qlen, has_long ? NGSID_ALIGN16_MAXLEN : 0);
                 if (rc || !has_long) return rc;
                 AlignJob jl = job; jl.pair_list = ctx->aln_cls.p + (size_t)NCLS * job.npairs; jl.npairs_dev = ctx->aln_ctr.p + 8 + NCLS;
                 return launch_rpl<16>(ctx, jl, max_qlen, max_tlen, true);

@@ -18,11 +18,32 @@
 // The row state is g = h - open rather than h (one subtraction per cell instead of the two of e_opn / f_opn).  The bound holds unchanged in that frame: the four
 // differences are the same numbers as before (e_opn = g_left, f_opn = g_up, d = g_diag + (score + open)); the one new value g = h - open stays above NEG16 - ext
 // (an h is at least -open - ext * 4000, a gap along a whole target of the int16 range); the diagonal constant match + open is at most 20.
-static_assert(-(NEG16) + 4 /* ext */ + 16 /* open */ + 4 /* match */ * 896 /* query rows */ < 32768, "packed sign-bit flags of k_sg_align16p would wrap");
+static_assert(sg16p_flag_span(4 /* match */, 4 /* ext */, 16 /* open */, 896 /* query rows */, NGSID_ALIGN16_MAXLEN, false) < 32768, "packed sign-bit flags of k_sg_align16p would wrap");
+//
+// The SKEW instances keep every value of cell (i, j) in the frame X^ = X + (i + j) ext (the column skew k_poa.hip uses for its in-row gap chain, here in both gap
+// directions), with the row state g' = H - open + ext:
+//     E^(i, j) = max(E^(i, j-1), g'^(i, j-1))        F^(i, j) = max(F^(i-1, j), g'^(i-1, j))        (no "- ext": the frame of the neighbour is one ext behind)
+//     d^ = g'^(i-1, j-1) + (score + open + ext)      h^ = max(d^, E^, F^)                           g'^ = h^ - (open - ext)
+// All candidates of a cell carry the same skew, so every maximum, every tie-break and the four flag differences (d^ - h^, E^ - mx^, E^left - E^, F^up - F^) are the
+// numbers of the plain frame: the traceback words do not change.  The frame is undone where values of different cells meet (the maxima over the last row and the
+// last column) and where one leaves the kernel (best).
+// Range.  The real values of the frame lie in [-2 open - ext + mismatch, match min(n, m) + (n + m) ext]: below, H(i, j) >= -open - min(i, j) ext (a gap from the nearer border),
+// which the skew lifts to >= -open; above, H <= match min(n, m) and the skew of the last cell plus the ext of g' is at most (n + m) ext.  The one value outside is the
+// "minus infinity" NEG16 of E in column -1 and of F in row -1, which the frame neither lifts nor (without the "- ext") lowers.  So every same-cell difference, one
+// against NEG16 included, is below -(NEG16) + ext + open + match min(n, m) + (n + m + 1) ext = sg16p_flag_span(..., true), and must stay below 2^15: with ext = 1 that
+// holds for every length of the paired classes (static_assert below); a call with a larger ext and long targets runs the plain instances (the host decides per call,
+// from its own maximum lengths: ngsid_align16p_skew_exact in k_align.hip).
+// In the NOWILD SKEW instances the score of a row is one byte permute: a lane's target letter is fixed for a step, so the step builds per pair a table of four bytes,
+// byte c = score + open + ext of query letter c against that target letter, and row r selects byte q_r (pair 0: low half) and byte 4 + q_r (pair 1: high half) with
+// zero high bytes.  It needs 0 <= mismatch + open + ext and match + open + ext <= 255; an item that does not satisfy it runs the instance with the select (mad form).
+static_assert(sg16p_flag_span(4, 1, 16, 896, NGSID_ALIGN16_MAXLEN, true) < 32768, "the skewed frame of k_sg_align16p must hold every paired length with ext = 1");
 // (inline asm: the masks and selectors live in SGPRs - gfx9 VOP3 takes no literal)
 __device__ __forceinline__ int pp_bfi(int mask_s, int a, int b) { int d; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "s"(mask_s), "v"(a), "v"(b)); return d; }        // (a & mask) | (b & ~mask)
 // byte permute of {a : b} (b = bytes 0..3); selectors 8..11 give 0xFF or 0x00 by the sign of bits 15, 31, 47, 63 = of the halves b.lo, b.hi, a.lo, a.hi
 __device__ __forceinline__ int pp_perm(int a, int b, int sel_s) { int d; asm("v_perm_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(sel_s)); return d; }
+__device__ __forceinline__ int pp_permv(int a, int b, int sel_v) { int d; asm("v_perm_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(sel_v)); return d; }          // per-lane selector
+// 0xFFFF / 0 by the sign of each half (the shift count comes packed from an SGPR: an inline constant would reach the low half only)
+__device__ __forceinline__ int pk_ashr15_i16(int a) { int d; asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(d) : "s"(0x000F000F), "v"(a)); return d; }
 __device__ __forceinline__ int pp_sel(int mask, int a, int b) { return (a & mask) | (b & ~mask); }      // per bit: mask ? a : b (one v_bfi)
 
 // traceback layout: the word of cell (i, j) is at step j + l, lane l = i / R (one strip); row r = i % R is bit r % 8 of the four flag bytes of the 32-bit half r / 8,
@@ -38,8 +59,9 @@ struct Planes {
     }
 };
 
-template <int R>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
+// (the SKEW instances name the occupancy of the plain ones as their minimum: left to itself the scheduler spends registers up to the next occupancy step)
+template <int R, bool SKEW>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SKEW ? (R <= 8 ? 4 : 3) : 2, 4)))
 void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ bin_off /* [PBINS + 1] pairs */, const uint32_t* __restrict__ item_off /* [PBINS + 1] items */,
                    uint64_t* __restrict__ tb, uint64_t tb_words_per_wave /* per half */, uint32_t seq_lds, uint32_t* __restrict__ work_ctr)
 {
@@ -85,9 +107,18 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
 
-        const int OPEN2 = sgpr(PK(J.open[p0], J.open[p1])), NOPEN2 = sgpr(PK(-J.open[p0], -J.open[p1])), EXT2 = sgpr(PK(J.ext, J.ext));
-        const int MATCHO2 = PK(J.match + J.open[p0], J.match + J.open[p1]), NDIFF2 = sgpr(PK(J.mismatch - J.match, J.mismatch - J.match));   // diagonal: g_diag + score + open
+        // SKEW: ext and the lane's first row are made values of THIS item (the empty asm hides where they come from).  As kernel invariants, the per-row frame
+        // offsets (i0 + r) ext are hoisted out of the item loop and hold R registers for the whole kernel - the difference between 3 and 2 waves per SIMD at R = 12
+        int ext = J.ext; if constexpr (SKEW) asm volatile("" : "+s"(ext));
+        const int open0 = sgpr(J.open[p0]), open1 = sgpr(J.open[p1]), skx = SKEW ? ext : 0;
+        const int NOPEN2 = sgpr(PK(-open0, -open1)), EXT2 = sgpr(PK(ext, ext));
+        const int dk0 = open0 + skx, dk1 = open1 + skx;                      // the diagonal adds back what the row state lacks: g_diag + score + open (SKEW: + ext)
+        const int DIAG2 = sgpr(PK(dk0, dk1)), GSUB2 = sgpr(PK(open0 - skx, open1 - skx));   // score 0 on the diagonal (wildcards); h -> row state
+        const int MATCHO2 = PK(J.match + dk0, J.match + dk1), NDIFF2 = sgpr(PK(J.mismatch - J.match, J.mismatch - J.match));
         const int ONE2 = sgpr(0x00010001);
+        // SKEW, permute score table: byte c of the table of a target letter t is the diagonal constant of query letter c; XX = mismatch in all four bytes, MX turns byte t into match
+        const bool tbl_ok = SKEW && J.mismatch + dk0 >= 0 && J.mismatch + dk1 >= 0 && J.match + dk0 <= 255 && J.match + dk1 <= 255;
+        const int XX0 = sgpr((J.mismatch + dk0) * 0x01010101), XX1 = sgpr((J.mismatch + dk1) * 0x01010101), MX0 = sgpr((J.match + dk0) ^ (J.mismatch + dk0)), MX1 = sgpr((J.match + dk1) ^ (J.mismatch + dk1));
         // (the v_perm selectors and the row masks of the flag planes are constants for the "s" operands of the asm: s_mov, which the compiler can rematerialise)
         constexpr int SGN = 0x0B0A0908;                                   // v_perm: the signs of b.lo, b.hi, a.lo, a.hi as 0x00 / 0xFF bytes
         constexpr int SEL0 = 0x06040200, SEL1 = 0x07050301;               // v_perm: the pair 0 / pair 1 bytes of the two accumulators of a row group
@@ -95,19 +126,27 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
         const int steps = mmax + 63;
         const int own_lane0 = n0 > 0 ? (n0 - 1) / R : -1, own_lane1 = n1 > 0 ? (n1 - 1) / R : -1;
         int bestRowV0 = -(1 << 29), bestRowJ0 = 0, bestRowV1 = -(1 << 29), bestRowJ1 = 0;
-        int hl2[R], e2[R], qc2[R], nwq2[R];                                // hl2 = g = H - open of the last column (column -1: H = 0)
-        const int i0 = lane * R;
+        int hl2[R], e2[R], qc2[R], nwq2[R];                                // hl2 = g = H - open of the last column (column -1: H = 0; SKEW: g' = -open + ext in the frame of cell (i, -1))
+        int i0 = lane * R; if constexpr (SKEW) asm volatile("" : "+v"(i0));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = i0 + r;
             const int ca = i < n0 ? qry0[i] : 0x7C, cb = i < n1 ? qry1[i] : 0x7C;
-            qc2[r] = PK(ca & 3, cb & 3); nwq2[r] = PK((ca & 0x7C) ? 0 : 0xffff, (cb & 0x7C) ? 0 : 0xffff);
-            hl2[r] = NOPEN2; e2[r] = PK(NEG16, NEG16);
+            // (SKEW: a wildcard is the SIGN of the letter's half instead of a mask register per row - the wildcard instance pays one shift per row for R registers less;
+            // the flag makes such a letter differ from every target letter, which the wildcard select overrides)
+            if constexpr (SKEW) { qc2[r] = PK((ca & 3) | ((ca & 0x7C) ? 0x8000 : 0), (cb & 3) | ((cb & 0x7C) ? 0x8000 : 0)); nwq2[r] = 0; }
+            else { qc2[r] = PK(ca & 3, cb & 3); nwq2[r] = PK((ca & 0x7C) ? 0 : 0xffff, (cb & 0x7C) ? 0 : 0xffff); }
+            hl2[r] = SKEW ? PK(i * ext - open0, i * ext - open1) : NOPEN2; e2[r] = PK(NEG16, NEG16);
         }
 
         auto forward = [&](auto OPc, auto NWc) {
             constexpr int OWN_P = decltype(OPc)::value; constexpr bool NOWILD = decltype(NWc)::value;
-            int hdiag2 = NOPEN2;                                          // g[i0-1][j-1], both pairs
+            constexpr bool TABLE = SKEW && NOWILD;                        // (a SKEW item the table cannot hold runs the !NOWILD instance: see the switch below)
+            int hdiag2 = SKEW ? PK((i0 - 1) * ext - open0, (i0 - 1) * ext - open1) : NOPEN2;      // g[i0-1][j-1], both pairs (SKEW: cell (i0 - 1, -1))
+            if constexpr (TABLE) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) qc2[r] += 0x0C040C00;         // v_perm selectors of the row: byte q of pair 0's table, zero, byte 4 + q = of pair 1's table, zero
+            }
             int send_h = NOPEN2, send_f = PK(NEG16, NEG16);               // bottom row (g, F) of this lane for the next one
             int keyRow0 = (int)0x80000000u, keyRow1 = (int)0x80000000u; const int jinv0 = 0xFFFF + lane;      // steady steps: packed (last-row g, -column) maxima
             // The steps in which EVERY lane stands inside both targets (tau - lane in [0, min(m0, m1)) for all 64 lanes: 63 <= tau < min(m0, m1), 84 % of the steps of a 750-base
@@ -116,10 +155,13 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                 constexpr bool STEADY = decltype(STc)::value;
                 const int j = tau - lane;
                 // lane 0 has no source lane: the shift leaves it the `old` operand - -open for g (H = 0 in row -1 of the matrix), minus infinity for F (no select needed)
-                const int hup = __builtin_amdgcn_update_dpp(NOPEN2, send_h, 0x138, 0xf, 0xf, false), fup = __builtin_amdgcn_update_dpp(PK(NEG16, NEG16), send_f, 0x138, 0xf, 0xf, false);
+                // (SKEW: row -1 stands in the frame of cell (-1, j), j = tau for lane 0)
+                const int top2 = SKEW ? PK(tau * ext - open0, tau * ext - open1) : NOPEN2;
+                const int hup = __builtin_amdgcn_update_dpp(top2, send_h, 0x138, 0xf, 0xf, false), fup = __builtin_amdgcn_update_dpp(PK(NEG16, NEG16), send_f, 0x138, 0xf, 0xf, false);
                 const bool a0 = STEADY || (j >= 0 && j < m0), a1 = STEADY || (j >= 0 && j < m1);      // STEADY: every lane stands inside both targets
                 const int l0 = tgt0[STEADY ? j : (a0 ? j : 0)], l1 = tgt1[STEADY ? j : (a1 ? j : 0)];
-                const int tc2 = PK(l0 & 3, l1 & 3);
+                const int tc2 = TABLE ? 0 : PK(l0 & 3, l1 & 3);
+                int tb0 = 0, tb1 = 0; if constexpr (TABLE) { tb0 = XX0 ^ (MX0 << ((l0 << 3) & 31)); tb1 = XX1 ^ (MX1 << ((l1 << 3) & 31)); }     // (letter & 3) * 8: the shift keeps five bits
                 int nwt2 = 0; if constexpr (!NOWILD) nwt2 = PK((a0 && !(l0 & 0x7C)) ? 0xffff : 0, (a1 && !(l1 & 0x7C)) ? 0xffff : 0);
                 const int am2 = STEADY ? -1 : PK(a0 ? 0xffff : 0, a1 ? 0xffff : 0);
                 int hu2 = hup, f2 = fup, hd2 = hdiag2;
@@ -127,14 +169,19 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     // the row state is g = H - open: the gap opens of E and F are the g of the left and of the upper cell, and the diagonal adds open back
-                    const int e_ext = pk_sub_i16_s(e2[r], EXT2); const int E = pk_max_i16(e_ext, hl2[r]);
-                    const int f_ext = pk_sub_i16_s(f2, EXT2); const int F = pk_max_i16(f_ext, hu2);
-                    const int z = pk_min_u16_s(qc2[r] ^ tc2, ONE2);                                // 1 = letters differ
-                    int sc = pk_mad_i16_sv(z, NDIFF2, MATCHO2);                                    // match / mismatch + open ...
-                    if constexpr (!NOWILD) { const int nw = nwq2[r] & nwt2; sc = pp_sel(nw, sc, OPEN2); }   // ... / 0 + open for wildcards (and for columns outside the target, whose cells nothing reads)
+                    // (SKEW: the extension candidates are the E of the left and the F of the upper cell as they are - their frame is one ext behind)
+                    const int e_ext = SKEW ? e2[r] : pk_sub_i16_s(e2[r], EXT2); const int E = pk_max_i16(e_ext, hl2[r]);
+                    const int f_ext = SKEW ? f2 : pk_sub_i16_s(f2, EXT2); const int F = pk_max_i16(f_ext, hu2);
+                    int sc;
+                    if constexpr (TABLE) sc = pp_permv(tb1, tb0, qc2[r]);                          // match / mismatch + open + ext from the step's tables
+                    else {
+                        const int z = pk_min_u16_s(qc2[r] ^ tc2, ONE2);                            // 1 = letters differ
+                        sc = pk_mad_i16_sv(z, NDIFF2, MATCHO2);                                    // match / mismatch + open ...
+                    }
+                    if constexpr (!NOWILD) { const int nw = SKEW ? (~pk_ashr15_i16(qc2[r]) & nwt2) : (nwq2[r] & nwt2); sc = pp_sel(nw, sc, DIAG2); }   // ... / 0 + open for wildcards (and for columns outside the target, whose cells nothing reads)
                     const int d = pk_add_i16(hd2, sc);
                     const int mx = pk_max_i16(E, F); const int h = pk_max_i16(d, mx);
-                    const int g = pk_sub_i16_s(h, OPEN2);
+                    const int g = pk_sub_i16_s(h, GSUB2);
                     // COMPLEMENT flags (1 = "not equal"): 0 h!=d, 1 mx!=E (F>E), 2 E!=e_ext (opened), 3 F!=f_ext (opened)
                     // each flag is the SIGN of a packed difference (smaller - larger: negative iff they differ).  One v_perm turns the four signs of two differences into
                     // 0x00 / 0xFF bytes (flag 0 pair 0, flag 0 pair 1, flag 1 pair 0, flag 1 pair 1; flags 2 / 3 alike) and one bit-field insert keeps bit r & 7 of each:
@@ -146,7 +193,9 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                     else { a01 = pp_bfi(0x01010101 << (r & 7), pa, a01); a23 = pp_bfi(0x01010101 << (r & 7), pb, a23); }
                     hd2 = hl2[r];
                     hl2[r] = STEADY ? g : pp_sel(am2, g, hl2[r]);
-                    e2[r] = E;                 // not masked (see k_align16.hip: before a lane's first column E only relaxes to -open, after its last it is not used)
+                    // not masked in the plain frame (see k_align16.hip: before a lane's first column E only relaxes to -open, after its last it is not used).  SKEW: without the
+                    // "- ext" a relaxed E would EQUAL the open candidate of column 0 and turn its "opened" flag: E stays at minus infinity until the lane's first column
+                    e2[r] = (SKEW && !STEADY) ? pp_sel(am2, E, e2[r]) : E;
                     hu2 = g; f2 = F;
                     if (r == OWN_P) cap2 = g;
                 }
@@ -162,6 +211,9 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
                 mytb1[(uint64_t)tau * 64 + lane] = w1;
                 if (STEADY) { hdiag2 = hup; send_h = hu2; send_f = f2; }
                 else { hdiag2 = pp_sel(am2, hup, hdiag2); send_h = pp_sel(am2, hu2, send_h); send_f = pp_sel(am2, f2, send_f); }
+                // SKEW: the columns of the last row are compared without the part of the frame that moves with the step (tau ext; the rest, (n - 1 - lane) ext, is the same
+                // for all columns of the owner lane and is taken off after the loop)
+                if constexpr (SKEW) cap2 = pk_sub_i16_s(cap2, sgpr(PK(tau * ext, tau * ext)));
                 if (STEADY) {
                     // last query row, first maximum over the columns, as ONE signed maximum per pair of (value << 16 | 0xFFFF - column): equal values keep the larger low
                     // half = the smaller column.  Every lane runs it, only the lane that owns the last row is read (merged into bestRow* after the steady steps).
@@ -190,17 +242,18 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
             for (; tau < steps; ++tau) step(tau, std::false_type{});
         };
         switch (own_p) {
-#define PCASE(k) case k: if (nowild) forward(std::integral_constant<int, (R > k ? k : 0)>{}, std::true_type{}); else forward(std::integral_constant<int, (R > k ? k : 0)>{}, std::false_type{}); break;
+#define PCASE(k) case k: if (SKEW ? (nowild && tbl_ok) : nowild) forward(std::integral_constant<int, (R > k ? k : 0)>{}, std::true_type{}); else forward(std::integral_constant<int, (R > k ? k : 0)>{}, std::false_type{}); break;
             PCASE(0) PCASE(1) PCASE(2) PCASE(3) PCASE(4) PCASE(5) PCASE(6) PCASE(7) PCASE(8) PCASE(9) PCASE(10) PCASE(11) PCASE(12) PCASE(13) PCASE(14)
 #undef PCASE
-            default: if (nowild) forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::true_type{}); else forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::false_type{}); break;
+            default: if (SKEW ? (nowild && tbl_ok) : nowild) forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::true_type{}); else forward(std::integral_constant<int, (R > 15 ? 15 : 0)>{}, std::false_type{}); break;
         }
-        bestRowV0 += LO16(OPEN2); bestRowV1 += HI16(OPEN2);                  // g -> H
+        bestRowV0 += open0 - skx * (n0 - own_lane0); bestRowV1 += open1 - skx * (n1 - own_lane1);      // g -> H (SKEW: g' = H - open + ext, plus the (n - 1 - lane) ext of the frame)
         // last target column of each pair: the state holds g[i][m-1] = H[i][m-1] - open for every row
         int bestColV0 = -(1 << 29), bestColI0 = 0x7fffffff, bestColV1 = -(1 << 29), bestColI1 = 0x7fffffff;
+        if constexpr (SKEW) { i0 = lane * R; asm volatile("" : "+v"(i0)); }      // (not kept across the step loops: see above)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int i = i0 + r; const int v0 = LO16(hl2[r]) + LO16(OPEN2), v1 = HI16(hl2[r]) + HI16(OPEN2);
+            const int i = i0 + r; const int v0 = LO16(hl2[r]) + open0 - skx * (i + m0), v1 = HI16(hl2[r]) + open1 - skx * (i + m1);     // (SKEW: g' of cell (i, m - 1) -> H)
             if (i < n0 && v0 > bestColV0) { bestColV0 = v0; bestColI0 = i; }
             if (i < n1 && v1 > bestColV1) { bestColV1 = v1; bestColI1 = i; }
         }
@@ -228,7 +281,11 @@ void k_sg_align16p(AlignJob J, const uint32_t* __restrict__ sorted, const uint32
     }
 }
 
-template __global__ void k_sg_align16p<4>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
-template __global__ void k_sg_align16p<8>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
-template __global__ void k_sg_align16p<12>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
-template __global__ void k_sg_align16p<14>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<4, false>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<4, true>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<8, false>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<8, true>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<12, false>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<12, true>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<14, false>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);
+template __global__ void k_sg_align16p<14, true>(AlignJob, const uint32_t*, const uint32_t*, const uint32_t*, uint64_t*, uint64_t, uint32_t, uint32_t*);

@@ -7,10 +7,17 @@
 // the int16 kernels (launched from k_align.hip; the instances are instantiated in their own files)
 template <int RP> __global__ void k_sg_align16(AlignJob J, uint64_t* tb, uint64_t tb_words_per_wave, int32_t* bnd, uint32_t bnd_stride, uint32_t lds_per_wave, uint32_t* work_ctr);
 #define PBINS 32          // bins of one length class of the paired kernel: residues (n - 1) mod R, R <= 16 (the rest unused)
-template <int R> __global__ void k_sg_align16p(AlignJob J, const uint32_t* sorted, const uint32_t* bin_off, const uint32_t* item_off, uint64_t* tb, uint64_t tb_words_per_wave, uint32_t seq_lds, uint32_t* work_ctr);
+template <int R, bool SKEW> __global__ void k_sg_align16p(AlignJob J, const uint32_t* sorted, const uint32_t* bin_off, const uint32_t* item_off, uint64_t* tb, uint64_t tb_words_per_wave, uint32_t seq_lds, uint32_t* work_ctr);
 
 // ---- packed 16-bit helpers
 #define NEG16 (-20000)
+// Paired kernel: bound on the magnitude of a difference of two values of one DP cell, the "minus infinity" NEG16 included (its traceback flags are sign bits of such
+// differences, so the bound must stay below 2^15).  skew: the instances that keep cell (i, j) in the frame X + (i + j) ext, which lifts the largest value by the frame
+// of the last cell (derivation at the top of k_align16p.hip).  Shared by the kernel's static_asserts and the host's choice of the instance.
+constexpr long long sg16p_flag_span(int match, int ext, int open, long long qlen, long long tlen, bool skew)
+{
+    return -(long long)(NEG16) + ext + open + match * (qlen < tlen ? qlen : tlen) + (skew ? (qlen + tlen + 1) * ext : 0);
+}
 // Packed 16-bit VALU ops through inline asm: with plain vector types the compiler "simplifies" the flag arithmetic back into
 // per-half compares + selects (no packed compare exists), which costs more than the 32-bit kernel.
 #define PKOP2(name, mnem) __device__ __forceinline__ int name(int a, int b) { int d; asm(mnem " %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }

@@ -205,6 +205,7 @@ struct AlignJob {            // device pointers
 // the clustering / polishing aligner (k_align.hip: routes every pair to one of the kernels of k_align.hip, k_align16.hip, k_align16p.hip)
 int32_t ngsid_launch_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open = 1 << 20, uint32_t min_qlen = 0);   // min_qlen: lower bound of the query lengths (lets empty length classes be skipped)
 bool ngsid_align16_applicable(const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open);
+bool ngsid_align16p_skew_exact(const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int max_open);      // the paired kernel's skewed-frame instances are exact for a call of these maxima
 #define NGSID_ALIGN16_MAXLEN 4000u      // sequences up to this length run the packed int16 aligners (score range)
 int32_t ngsid_partition_pairs(ngsid_ctx* ctx, const AlignJob& job, uint32_t long_len = 0);      // query-length classes {<=256, <=512, <=768, <=896, rest}: lists in ctx->aln_cls, counts in ctx->aln_ctr[8..12]
 int32_t ngsid_side_streams(ngsid_ctx* ctx);          // creates ctx->side / events on first use
