@@ -64,6 +64,21 @@ class ClassifyParams(C.Structure):
 CLASSIFY_MAX_TOPK, CLASSIFY_MAX_K = 64, 21
 
 
+CHIMERA_FIELDS = ("one_pair", "one_cost", "two_cost", "pair_a", "pair_b", "bp_lo", "bp_hi")   # the seven integers per query of Api.chimera_model (include/ngsid_chimera.h)
+CHIMERA_NFIELD, CHIMERA_ROWS, CHIMERA_LDS_QUERY = 7, 12, 2048                      # NGSID_CHIMERA_NFIELD, _ROWS (R of k_chimera_profile), _LDS_QUERY
+CHIMERA_STRIP = 64 * CHIMERA_ROWS                                                   # NGSID_CHIMERA_STRIP: parent rows per pass of a wave
+MAX_CONSENSUS_LEN = 16384                                                           # include/ngsid.h NGSID_MAX_CONSENSUS_LEN
+
+
+def chimera_profile_offsets(query_lens, pair_off):
+    """-> prof_off [n_pairs + 1] uint64: where the block of pair k (F_k[0 .. n] then B_k[0 .. n], n = its query's length) starts in the profiles of Api.chimera_model"""
+    po = np.asarray(pair_off).astype(np.int64)
+    cnt = np.maximum(np.diff(po), 0)
+    off = np.zeros(int(cnt.sum()) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(np.repeat(2 * (np.asarray(query_lens).astype(np.int64) + 1), cnt))
+    return off
+
+
 DEMUX_FIELDS = ("tag", "ed", "start", "end", "ed2")                                # the five integers per (read, side) of Api.demux_locate
 DEMUX_MAX_TAG_LEN, DEMUX_MAX_WINDOW = 64, 256
 
@@ -738,6 +753,34 @@ class Api:
         rc = self._call("classify_search", refdb.handle, C.byref(queries.c), C.byref(prm), _p(ref), _p(sh), _p(st), _p(nc))
         if rc: self._err(rc)
         return (ref, sh, st, nc) if n_codes else (ref, sh, st)
+
+    # ---- include/ngsid_chimera.h
+    def _need_chimera(self):
+        if not hasattr(self.lib, self.prefix + "chimera_model"):
+            raise NgsidError(-2, "the bound library does not export %schimera_model (include/ngsid_chimera.h): rebuild it from this tree" % self.prefix)
+
+    def chimera_model(self, queries, parents, pair_off, pair_parent, pair_gid=None, profiles=False):
+        """ngsid_chimera_model: the best one-parent and two-parent model of every query over its pairs pair_parent[pair_off[q]:pair_off[q + 1]] (indices into parents;
+        pair_gid: pairs of one gid are never combined, None = the parent index) -> fields [n, 7] int32 in CHIMERA_FIELDS order, -1 where a model does not exist;
+        profiles=True: (fields, prof uint16, prof_off [n_pairs + 1]): prof[prof_off[k]:prof_off[k + 1]] = F_k[0 .. n] then B_k[0 .. n] of pair k.  queries / parents: lists of
+        strings or read sets; the pair arrays are host arrays.  There is no CPU implementation: a library without the entry point is an error."""
+        self._need_chimera()
+        qs = queries if isinstance(queries, ReadSet) else ReadSet.from_strings(list(queries))
+        ps = parents if isinstance(parents, ReadSet) else ReadSet.from_strings(list(parents))
+        po = np.ascontiguousarray(pair_off, dtype=np.uint64)
+        pp = np.ascontiguousarray(pair_parent, dtype=np.uint32)
+        pg = None if pair_gid is None else np.ascontiguousarray(pair_gid, dtype=np.int32)
+        if len(po) != qs.n + 1: raise ValueError("chimera_model: pair_off has one entry per query + 1")
+        if len(pp) != int(po[-1]) or (pg is not None and len(pg) != len(pp)): raise ValueError("chimera_model: pair_parent / pair_gid hold pair_off[-1] entries")
+        fields = np.full((qs.n, CHIMERA_NFIELD), -1, dtype=np.int32)
+        prof = prof_off = None
+        if profiles:
+            if qs.mem != MEM_HOST: raise ValueError("chimera_model: profiles=True takes the queries as a host read set (their lengths size the result)")
+            prof_off = chimera_profile_offsets(np.diff(qs.off.astype(np.int64)), po)
+            prof = np.zeros(max(int(prof_off[-1]), 1), dtype=np.uint16)
+        rc = self._call("chimera_model", C.byref(qs.c), C.byref(ps.c), _p(po), _p(pp if len(pp) else np.zeros(1, np.uint32)), _p(pg if pg is None or len(pg) else np.zeros(1, np.int32)), _p(fields if qs.n else np.zeros(CHIMERA_NFIELD, np.int32)), _p(prof))
+        if rc: self._err(rc)
+        return (fields, prof[:int(prof_off[-1])], prof_off) if profiles else fields
 
 
 class RefDb:

@@ -48,7 +48,7 @@ DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are h
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
-                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db",
+                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--version', action='version', version='%(prog)s 0.3.1-mi355x')
     p.add_argument('--debug', action='store_true')
@@ -94,6 +94,9 @@ def build_parser():
     p.add_argument('--reference_db', type=str, default=None, help='extension: FASTA of reference barcodes (BOLD, UNITE, SILVA, ...). Every final consensus (the polished one with --racon, else the draft) is searched in it on the GPU by shared minimizers, both strands, and its best candidates are verified by alignment; writes <outfolder>/classification.tsv (consensus_id n_reads rank reference strand shared identity aln_cols n_match q_cov r_cov called header; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/classification_all.tsv). Needs --consensus')
     from . import classify as _classify
     _classify.add_flags(p)
+    from . import chimera as _chimera
+    p.add_argument('--chimeras', action='store_true', help='extension: flag PCR chimeras among the final consensuses. Every consensus is modelled on the GPU as the head of one and the tail of another more abundant consensus of the same sample (both strands, unit-cost edit distance, every breakpoint); writes <outfolder>/chimeras.tsv (id n_reads length chimeric best_parent best_strand best_ed parent_a strand_a parent_b strand_b model_ed gain bp_lo bp_hi; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/chimeras_all.tsv). No other output changes. Needs --consensus')
+    _chimera.add_flags(p)
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -125,6 +128,23 @@ def _classify_subparser(cf):
     return cf
 
 
+def _chimeras_subparser(cf):
+    """the `chimeras` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import chimera as _chimera
+    cf.add_argument('--fasta', type=str, required=True, help='sequences of one sample; read counts are taken from names of this tool\'s consensuses (..._total_supporting_reads_N), else 0')
+    cf.add_argument('--outfile', type=str, required=True, help='the table (columns of chimeras.tsv)')
+    _chimera.add_flags(cf)
+    cf.set_defaults(which='chimeras')
+    return cf
+
+
+def _check_chimeras(args):
+    from . import chimera as _chimera
+    err = _chimera.check_args(args)
+    if err:
+        logging.error(err); sys.exit(1)
+
+
 def _check_classify(args):
     from . import classify as _classify
     err = _classify.check_args(args)
@@ -138,6 +158,8 @@ def cli(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == 'classify':              # `classify --fasta X --reference_db DB --outfile T` needs none of the main command's inputs
         args = _classify_subparser(argparse.ArgumentParser(prog='classify', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'chimeras':
+        args = _chimeras_subparser(argparse.ArgumentParser(prog='chimeras', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
         args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if getattr(args, 'debug', False) else logging.INFO, format='%(message)s')
@@ -149,6 +171,14 @@ def cli(argv=None):
         _check_classify(args)
         from . import classify as _classify
         rows = _classify.classify_fasta(args)
+        logging.info("Wrote %d rows to %s." % (len(rows), args.outfile))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'chimeras':
+        _check_chimeras(args)
+        if not os.path.isfile(args.fasta):
+            logging.error("--fasta %s is not a file." % args.fasta); sys.exit(1)
+        from . import chimera as _chimera
+        rows = _chimera.chimeras_fasta(args)
         logging.info("Wrote %d rows to %s." % (len(rows), args.outfile))
         sys.exit(0)
     if args.ont and args.isoseq:
@@ -188,6 +218,10 @@ def cli(argv=None):
         if not args.consensus:
             logging.error("--reference_db classifies consensus sequences: it needs --consensus."); sys.exit(1)
         _check_classify(args)
+    if getattr(args, "chimeras", False):
+        if not args.consensus:
+            logging.error("--chimeras models consensus sequences: it needs --consensus."); sys.exit(1)
+        _check_chimeras(args)
     if args.medaka:
         logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
     if args.k > 32 or args.k < 1:

@@ -723,6 +723,8 @@ def _main(args, api):
         res["haplotypes"] = getattr(args, "_hap_entries", [])
     if getattr(args, "reference_db", None) and args.consensus:
         _classify_step(args, api, [(None, args.outfolder, res["centers"])], res["timings"], extra=getattr(args, "_hap_named", None) if getattr(args, "split_haplotypes", False) else None)
+    if getattr(args, "chimeras", False) and args.consensus:
+        _chimera_step(args, api, [(None, args.outfolder, res["centers"])], res["timings"])
     return res
 
 
@@ -736,6 +738,16 @@ def _classify_step(args, api, groups, T, extra=None):
         named[0] = (named[0][0], named[0][1], named[0][2] + list(extra))
     classify.run(args, api, named)
     T["classify"] = time() - t0
+
+
+def _chimera_step(args, api, groups, T):
+    """--chimeras: the final consensuses of every (sample, folder, centres) group modelled from the more abundant consensuses of the same group, all groups in one
+    library call (chimera.run) -> chimeras.tsv per folder (+ chimeras_all.tsv with samples)"""
+    from . import chimera
+    t0 = time()
+    named = [(sample, folder, [("consensus_cl_id_{0}_total_supporting_reads_{1}".format(c_id, nr), nr, seq) for nr, c_id, seq, _ in centers]) for sample, folder, centers in groups]
+    chimera.run(args, api, named)
+    T["chimeras"] = time() - t0
 
 
 def sample_files(folder):
@@ -788,6 +800,8 @@ def _main_samples(args, api):
         out[os.path.basename(a.outfolder)] = _finish(a, api, st, clustered, t1)
     if getattr(args, "reference_db", None) and args.consensus:
         _classify_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
+    if getattr(args, "chimeras", False) and args.consensus:
+        _chimera_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 

@@ -149,7 +149,7 @@ def _support_of(api, rs, seqs, lists, k, w):
 
 
 def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs):
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None):
     """Everything behind the clustering call, once for a list of samples: reads [seg_off[s], seg_off[s+1]) of rs are sample s, out[s] is its result dict (rep_of in read
     indices local to the sample) and bands[s] the band of its draft and polishing calls.  Per sample the cluster table and the selection with the sample's own cut-off, the
     reverse-complement bookkeeping and the pooled read lists; for all samples ONE alignment call, one consensus_support call and one search, and per distinct band one draft
@@ -223,13 +223,20 @@ def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ra
         for s, part in zip(tab, _deal(classify_mod.identify(api, classify, flat, **(classify_kwargs or {})), sizes)):
             out[s]["classify"] = part
         T["classify"] = T.get("classify", 0.0) + time.perf_counter() - t0
+    if chimeras:
+        from . import chimera as chimera_mod
+        t0 = time.perf_counter()
+        per = chimera_mod.detect(api, flat, [m[0] for s in tab for m in merged[s]], np.concatenate(([0], np.cumsum(sizes))), **(chimera_kwargs or {}))
+        for s, part in zip(tab, per):
+            out[s]["chimeras"] = part
+        T["chimeras"] = T.get("chimeras", 0.0) + time.perf_counter() - t0
     return polished, pooled, prms
 
 
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None):
+                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None, chimeras=False, chimera_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
@@ -239,7 +246,10 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     split_haplotypes=True (extension; phase.py, include/ngsid_phase.h): also haplotypes = one entry per centre, None or dict(sites, alleles [H, S], n_reads [H], assign
     [per pooled read] int8, draft [H], polished [H], used [H] and, with classify, classify [H]): the centre's pooled reads split by linked variant sites of its final sequence, every
     haplotype drafted and polished with the parameters of the cluster's own draft and polish (haplotype_kwargs: the policy arguments of phase.split_many); every other key
-    is what split_haplotypes=False returns."""
+    is what split_haplotypes=False returns.
+    chimeras=True (extension; chimera.py, include/ngsid_chimera.h): also chimeras = one dict per centre (chimera.describe: chimeric, the best single parent, the best
+    two-parent model and its breakpoint interval, parents as centre numbers) - every centre's final sequence modelled from the more abundant centres, both strands
+    (chimera_kwargs: min_abskew, min_gain, max_model_frac); every other key is what chimeras=False returns."""
     T = timings if timings is not None else {}
     t0 = time.perf_counter()
     prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
@@ -257,12 +267,13 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         T["strand_merge"] = T.get("strand_merge", 0.0) + time.perf_counter() - t0
     if classify is not None: res["classify"] = []                               # what stays without a centre: nothing to name, nothing to split
     if split_haplotypes: res["haplotypes"] = []
+    if chimeras: res["chimeras"] = []
     if not do_consensus:
         return res
     # one sample, reads [0, n); band goes through as it is: for band <= 0 the library applies the POA_BAND64_MAXLEN rule to the reads of the call, which here are the sample's
     # (reading the lengths of a device-resident set here would cost a copy of its offsets to the host in every step)
     stages = _consensus_stages(api, rs, score, [0, n], [res], [band], T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                               do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs)
+                               do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs)
     if split_haplotypes and stages is not None:
         from . import phase
         t0 = time.perf_counter()
@@ -297,13 +308,14 @@ def _bands_alone(rs, so, band):
 def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                         strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None):
+                         strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
     are grouped by the band they would get alone (a sample with a read above POA_BAND64_MAXLEN bases gets 128 columns, the others 64), so at most two consensus
     and two polishing calls.  support=True: the support key of run_hot_path per sample, from one consensus_support call for all samples.  classify=RefDb: the classify
-    key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  strand_aware is not supported here (ValueError)."""
+    key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  chimeras=True: the chimeras
+    key of run_hot_path per sample, ALL samples in one model call (parents within a sample only).  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     T = timings if timings is not None else {}
@@ -315,11 +327,13 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     out = [dict(rep_of=rep_of[so[s]:so[s + 1]] - np.int32(so[s]), status=status[so[s]:so[s + 1]], counters=counters[s], hpc_err=herr[so[s]:so[s + 1]], centers=[]) for s in range(ns)]
     if classify is not None:
         for o in out: o["classify"] = []                                        # what stays for a sample without a centre
+    if chimeras:
+        for o in out: o["chimeras"] = []
     if not do_consensus:
         return out
     t0 = time.perf_counter()
     bands = _bands_alone(rs, so, band)
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs)
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs)
     return out
