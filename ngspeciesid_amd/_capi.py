@@ -185,6 +185,31 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _groups(grp_off, read_order):
+    """-> (grp_off uint64, read_order uint32 or None, n_groups) as the C-ABI takes them"""
+    grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
+    return grp_off, None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32), len(grp_off) - 1
+
+
+def _strings(buf, off, n):
+    """the n strings of a CSR result (bytes buf, offsets off)"""
+    return [buf[int(off[i]):int(off[i + 1])].tobytes().decode() for i in range(n)]
+
+
+def _as_reads(x):
+    return x if isinstance(x, ReadSet) else ReadSet.from_strings(list(x))
+
+
+def _consensus_cap(rs, ng):
+    """bytes for the consensuses of ng groups: four times the longest read each (a host set tells its lengths)"""
+    lens = np.diff(rs.off.astype(np.int64)) if rs.mem == MEM_HOST else None
+    return int(4 * (lens.max() if lens is not None and len(lens) else 16384) * max(ng, 1) + 1024)
+
+
+def _polish_cap(backbones):
+    return int(4 * len(backbones.seq) + 4096) if backbones.mem == MEM_HOST else 1 << 24
+
+
 LANES = int(os.environ.get("NGSID_LANES", "2"))           # contexts a consensus / polishing call is dealt to (Api.lanes); 1 = off
 LANE_MIN_READS = 100_000                                   # below: one context (measured on the bench workload: 100 k reads 109.5 ms either way, 300 k reads 248 -> 242 ms, 1 M 719 -> 708 ms)
 LANE_MAX_READS = 4_000_000                                 # above: one context (a second one doubles the grow-only scratch: 130 - 140 GB at 10 M reads)
@@ -400,13 +425,13 @@ class Api:
         return ReadSet(out.seq, out.qual, out.off, MEM_DEVICE, dict(n=len(idx), api=self)), int(foreign.value)
 
     def _err(self, rc):
-        if self.has_ctx:
-            g = getattr(self.lib, self.prefix + "last_error"); g.restype = C.c_char_p
-            txt = g(self.ctx)
-        else:
-            g = getattr(self.lib, self.prefix + "last_error"); g.restype = C.c_char_p
-            txt = g()
+        g = getattr(self.lib, self.prefix + "last_error"); g.restype = C.c_char_p
+        txt = g(self.ctx) if self.has_ctx else g()
         raise NgsidError(rc, (txt or b"").decode(errors="replace"))
+
+    def _need(self, header, *names):
+        if not all(hasattr(self.lib, self.prefix + n) for n in names):
+            raise NgsidError(-2, "the bound library does not export %s (include/%s): rebuild it from this tree" % (" / ".join(self.prefix + n for n in names), header))
 
     # ---- (f1)
     def score_reads(self, rs: ReadSet, k, q_threshold=7.0):
@@ -500,7 +525,7 @@ class Api:
         rc = self._call("sg_align_cigar_batch", C.byref(q.c), C.byref(t.c), _p(q_idx), _p(t_idx), C.c_uint64(n), C.c_int32(match), C.c_int32(mismatch),
                         _p(open_), C.c_int32(ext), _p(score), _p(off), _p(ops), C.c_uint64(cap), C.byref(needed))
         if rc: self._err(rc)
-        return score, [ops[int(off[p]):int(off[p + 1])].tobytes().decode() for p in range(n)]
+        return score, _strings(ops, off, n)
 
     def ed_align_batch(self, q: ReadSet, t: ReadSet, q_idx, t_idx, window=500, bp_windows=0):
         """edit-distance (read inside backbone) alignment of the polisher: distance, span[n,4], bp[n,bp_windows,4]"""
@@ -527,44 +552,28 @@ class Api:
             for x, g in enumerate(gs): out[g] = r[x]
         return out
 
-    def _poa_consensus1(self, rs: ReadSet, grp_off, prm: PoaParams, cap=None, read_order=None):
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1
-        if cap is None:
-            lens = np.diff(rs.off.astype(np.int64)) if rs.mem == MEM_HOST else None
-            cap = int(4 * (lens.max() if lens is not None and len(lens) else 16384) * max(ng, 1) + 1024)
+    def _poa_call(self, name, rs, grp_off, prm, cap, read_order, *extra, cov=False):
+        """one of the three ngsid_poa_consensus* calls (extra: the arguments between prm and the outputs) -> (consensus strings, coverage array or None, offsets)"""
+        grp_off, ro, ng = _groups(grp_off, read_order)
+        if cap is None: cap = _consensus_cap(rs, ng)
         coff = np.zeros(ng + 1, dtype=np.uint64); cons = np.zeros(cap, dtype=np.uint8); needed = C.c_uint64(0)
-        rc = self._call("poa_consensus", C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(coff), _p(cons), C.c_uint64(cap), C.byref(needed))
+        cv = np.zeros(cap, dtype=np.uint32) if cov else None
+        rc = self._call(name, C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), *extra, _p(coff), _p(cons), *([_p(cv)] if cov else []), C.c_uint64(cap), C.byref(needed))
         if rc: self._err(rc)
-        return [cons[int(coff[g]):int(coff[g + 1])].tobytes().decode() for g in range(ng)]
+        return _strings(cons, coff, ng), cv, coff
+
+    def _poa_consensus1(self, rs: ReadSet, grp_off, prm: PoaParams, cap=None, read_order=None):
+        return self._poa_call("poa_consensus", rs, grp_off, prm, cap, read_order)[0]
 
     def poa_consensus_weighted(self, rs: ReadSet, grp_off, prm: PoaParams, weight, cap=None, read_order=None):
         """ngsid_poa_consensus_weighted: sequence i stands for weight[i] reads (the merge of per-shard partial consensuses)"""
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
         wv = np.ascontiguousarray(weight, dtype=np.uint32); assert len(wv) == rs.n
-        ng = len(grp_off) - 1
-        if cap is None:
-            lens = np.diff(rs.off.astype(np.int64)) if rs.mem == MEM_HOST else None
-            cap = int(4 * (lens.max() if lens is not None and len(lens) else 16384) * max(ng, 1) + 1024)
-        coff = np.zeros(ng + 1, dtype=np.uint64); cons = np.zeros(cap, dtype=np.uint8); needed = C.c_uint64(0)
-        rc = self._call("poa_consensus_weighted", C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(wv), _p(coff), _p(cons), C.c_uint64(cap), C.byref(needed))
-        if rc: self._err(rc)
-        return [cons[int(coff[g]):int(coff[g + 1])].tobytes().decode() for g in range(ng)]
+        return self._poa_call("poa_consensus_weighted", rs, grp_off, prm, cap, read_order, _p(wv))[0]
 
     def poa_consensus_cov(self, rs: ReadSet, grp_off, prm: PoaParams, cap=None, read_order=None):
         """-> [(consensus string, uint32 coverage array)] per group"""
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1
-        if cap is None:
-            lens = np.diff(rs.off.astype(np.int64)) if rs.mem == MEM_HOST else None
-            cap = int(4 * (lens.max() if lens is not None and len(lens) else 16384) * max(ng, 1) + 1024)
-        coff = np.zeros(ng + 1, dtype=np.uint64); cons = np.zeros(cap, dtype=np.uint8); cov = np.zeros(cap, dtype=np.uint32); needed = C.c_uint64(0)
-        rc = self._call("poa_consensus_cov", C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(coff), _p(cons), _p(cov), C.c_uint64(cap), C.byref(needed))
-        if rc: self._err(rc)
-        return [(cons[int(coff[g]):int(coff[g + 1])].tobytes().decode(), cov[int(coff[g]):int(coff[g + 1])].copy()) for g in range(ng)]
+        seqs, cov, coff = self._poa_call("poa_consensus_cov", rs, grp_off, prm, cap, read_order, cov=True)
+        return [(s, cov[int(coff[g]):int(coff[g + 1])].copy()) for g, s in enumerate(seqs)]
 
     # ---- (a16,a17)
     def polish(self, backbones: ReadSet, rs: ReadSet, grp_off, prm: PolishParams, cap=None, read_order=None):
@@ -582,15 +591,12 @@ class Api:
         return seqs, used
 
     def _polish1(self, backbones: ReadSet, rs: ReadSet, grp_off, prm: PolishParams, cap=None, read_order=None):
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1
-        if cap is None:
-            cap = int(4 * len(backbones.seq) + 4096) if backbones.mem == MEM_HOST else 1 << 24
+        grp_off, ro, ng = _groups(grp_off, read_order)
+        if cap is None: cap = _polish_cap(backbones)
         ooff = np.zeros(ng + 1, dtype=np.uint64); out = np.zeros(cap, dtype=np.uint8); needed = C.c_uint64(0); used = np.zeros(max(ng, 1), dtype=np.uint64)
         rc = self._call("polish", C.byref(backbones.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(ooff), _p(out), C.c_uint64(cap), C.byref(needed), _p(used))
         if rc: self._err(rc)
-        return [out[int(ooff[g]):int(ooff[g + 1])].tobytes().decode() for g in range(ng)], used[:ng]
+        return _strings(out, ooff, ng), used[:ng]
 
     def polish_trace(self, backbones: ReadSet, rs: ReadSet, grp_off, prm: PolishParams, cap=None, read_order=None, aln=False):
         """ngsid_polish_trace: -> (seqs[it][g], used[it][g]): every group's sequence after every iteration (the last one is what polish() returns).
@@ -616,11 +622,8 @@ class Api:
         return (seqs, used, LaneRecords(go, iters, where)) if aln else (seqs, used)
 
     def _polish_trace1(self, backbones: ReadSet, rs: ReadSet, grp_off, prm: PolishParams, cap=None, read_order=None, aln=False):
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1; iters = int(prm.iters); n = iters * ng
-        if cap is None:
-            cap = (int(4 * len(backbones.seq) + 4096) if backbones.mem == MEM_HOST else 1 << 24) * max(iters, 1)
+        grp_off, ro, ng = _groups(grp_off, read_order); iters = int(prm.iters); n = iters * ng
+        if cap is None: cap = _polish_cap(backbones) * max(iters, 1)
         ooff = np.zeros(n + 1, dtype=np.uint64); out = np.zeros(cap, dtype=np.uint8); needed = C.c_uint64(0); used = np.zeros(max(n, 1), dtype=np.uint64)
         if aln:
             nl = int(grp_off[-1]); rec = np.empty((iters, nl, 6), dtype=np.int32)
@@ -628,7 +631,7 @@ class Api:
         else:
             rc = self._call("polish_trace", C.byref(backbones.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(ooff), _p(out), C.c_uint64(cap), C.byref(needed), _p(used))
         if rc: self._err(rc)
-        seqs = [[out[int(ooff[it * ng + g]):int(ooff[it * ng + g + 1])].tobytes().decode() for g in range(ng)] for it in range(iters)]
+        flat = _strings(out, ooff, n); seqs = [flat[it * ng:(it + 1) * ng] for it in range(iters)]
         u = used[:n].reshape(iters, ng) if n else used[:0].reshape(0, ng)
         return (seqs, u, rec) if aln else (seqs, u)
 
@@ -639,11 +642,8 @@ class Api:
         Rows cen_off[g] .. cen_off[g + 1] of counts are centre g.  Grouping as in polish(); clip=True counts a read between its first and last run of 15 equal
         columns only (the polisher's aln_mode 3).  There is no CPU implementation: a library without the entry point is an error."""
         if centres.mem != MEM_HOST: raise ValueError("consensus_support takes the centres as a host read set")
-        if not hasattr(self.lib, self.prefix + "consensus_support"):
-            raise NgsidError(-2, "the bound library does not export %sconsensus_support (include/ngsid_support.h): rebuild it from this tree" % self.prefix)
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1
+        self._need("ngsid_support.h", "consensus_support")
+        grp_off, ro, ng = _groups(grp_off, read_order)
         cen_off = centres.off.copy(); total = int(cen_off[-1]) if len(cen_off) else 0
         counts = np.zeros((total, 8), dtype=np.uint32); used = np.zeros(max(ng, 1), dtype=np.uint64); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
         prm = SupportParams(int(k), int(w), 1 if clip else 0)
@@ -652,21 +652,15 @@ class Api:
         return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
 
     # ---- include/ngsid_phase.h
-    def _need_phase(self):
-        if not all(hasattr(self.lib, self.prefix + n) for n in ("phase_genotypes", "phase_pair_tables", "phase_assign")):
-            raise NgsidError(-2, "the bound library does not export %sphase_genotypes / _pair_tables / _assign (include/ngsid_phase.h): rebuild it from this tree" % self.prefix)
-
     def phase_genotypes(self, centres: ReadSet, rs: ReadSet, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):
         """ngsid_phase_genotypes: the allele of every listed read at the sites site_pos[site_off[g]:site_off[g + 1]] (ascending centre positions, at most PHASE_MAX_SITES) of
         its group -> (geno uint8, geno_off [n_groups + 1], strand [n_listed] int8).  geno[geno_off[g]:geno_off[g + 1]].reshape(R_g, S_g) is group g, [listed read][site]:
         0-3 = A C G T, GENO_DEL, GENO_OTHER (mismatch with a read base outside ACGT), GENO_NONE (not counted).  Grouping, strands and counted columns as in consensus_support().
         There is no CPU implementation: a library without the entry point is an error."""
         if centres.mem != MEM_HOST: raise ValueError("phase_genotypes takes the centres as a host read set")
-        self._need_phase()
-        grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
+        self._need("ngsid_phase.h", "phase_genotypes", "phase_pair_tables", "phase_assign")
+        grp_off, ro, ng = _groups(grp_off, read_order); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
         site_pos = np.ascontiguousarray(site_pos, dtype=np.uint32)
-        ro = None if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-        ng = len(grp_off) - 1
         if len(site_off) != ng + 1 or len(site_pos) != int(site_off[-1]): raise ValueError("phase_genotypes: site_off has one entry per group + 1 and site_pos site_off[-1] entries")
         geno_off, _ = phase_offsets(grp_off, site_off)
         geno = np.full(max(int(geno_off[-1]), 1), GENO_NONE, dtype=np.uint8); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
@@ -679,7 +673,7 @@ class Api:
     def phase_pair_tables(self, geno, grp_off, site_off):
         """ngsid_phase_pair_tables -> (tables uint32, tab_off [n_groups + 1]): tables[tab_off[g]:tab_off[g + 1]].reshape(S_g, S_g, 5, 5)[s, t, a, b], s < t, = listed reads of
         group g with code a at site s and code b at site t (both <= GENO_DEL); zero for s >= t."""
-        self._need_phase()
+        self._need("ngsid_phase.h", "phase_genotypes", "phase_pair_tables", "phase_assign")
         grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
         geno_off, tab_off = phase_offsets(grp_off, site_off)
         geno = np.ascontiguousarray(geno, dtype=np.uint8)
@@ -693,7 +687,7 @@ class Api:
         """ngsid_phase_assign: haplotypes hap_off[g]:hap_off[g + 1] (at most PHASE_MAX_HAPS) belong to group g, hap_alleles holds their [haplotype][site] blocks group after
         group (0 - GENO_DEL, or HAP_ANY) -> (best int8, dist uint8, dist2 uint8) per listed read: the nearest haplotype within the group (the lowest on ties), its distance
         over the sites both cover, and the smallest distance over the other haplotypes (255: none).  -1 / 255 / 255 for a read without a covered site or a group without haplotypes."""
-        self._need_phase()
+        self._need("ngsid_phase.h", "phase_genotypes", "phase_pair_tables", "phase_assign")
         grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64); site_off = np.ascontiguousarray(site_off, dtype=np.uint64); hap_off = np.ascontiguousarray(hap_off, dtype=np.uint64)
         geno_off, _ = phase_offsets(grp_off, site_off)
         geno = np.ascontiguousarray(geno, dtype=np.uint8); hal = np.ascontiguousarray(hap_alleles, dtype=np.uint8).ravel()
@@ -712,9 +706,8 @@ class Api:
         """ngsid_demux_locate: every tag located in both end windows of every read -> hits [n, 2, 5] int32 in DEMUX_FIELDS order (side 1 in reverse-complement
         coordinates); matrices=True: (hits, ed_all [n, 2, T] int16, end_all [n, 2, T] int16), ed and end of every tag.  tags: a list of strings or a host ReadSet.
         There is no CPU implementation: a library without the entry point is an error."""
-        if not hasattr(self.lib, self.prefix + "demux_locate"):
-            raise NgsidError(-2, "the bound library does not export %sdemux_locate (include/ngsid_demux.h): rebuild it from this tree" % self.prefix)
-        tg = tags if isinstance(tags, ReadSet) else ReadSet.from_strings(list(tags))
+        self._need("ngsid_demux.h", "demux_locate")
+        tg = _as_reads(tags)
         if tg.mem != MEM_HOST: raise ValueError("demux_locate takes the tags as a host read set")
         n, T = rs.n, tg.n
         hits = np.full((n, 2, 5), -1, dtype=np.int32)
@@ -726,15 +719,11 @@ class Api:
         return (hits, ed_all, end_all) if matrices else hits
 
     # ---- include/ngsid_classify.h
-    def _need_classify(self):
-        if not hasattr(self.lib, self.prefix + "classify_search") or not hasattr(self.lib, self.prefix + "refdb_build"):
-            raise NgsidError(-2, "the bound library does not export %srefdb_build / %sclassify_search (include/ngsid_classify.h): rebuild it from this tree" % (self.prefix, self.prefix))
-
     def refdb_build(self, refs, k=13, w=20) -> "RefDb":
         """ngsid_refdb_build: the minimizer index of a reference library (a list of strings or a host ReadSet) on the device -> RefDb handle (.info(), .release(),
         context manager).  There is no CPU implementation: a library without the entry point is an error."""
-        self._need_classify()
-        rs = refs if isinstance(refs, ReadSet) else ReadSet.from_strings(list(refs))
+        self._need("ngsid_classify.h", "refdb_build", "classify_search")
+        rs = _as_reads(refs)
         if rs.mem != MEM_HOST: raise ValueError("refdb_build takes the references as a host read set")
         prm = RefDbParams(int(k), int(w)); h = C.c_void_p()
         rc = self._call("refdb_build", C.byref(rs.c), C.byref(prm), C.byref(h))
@@ -744,7 +733,7 @@ class Api:
     def classify_search(self, refdb: "RefDb", queries: ReadSet, top_k=8, min_shared=3, n_codes=False):
         """ngsid_classify_search -> (cand_ref [n, top_k] int32, cand_shared [n, top_k] int32, cand_strand [n, top_k] int8), -1 where a query has fewer candidates;
         n_codes=True: + n_codes [n, 2] int32, the distinct minimizer codes of each query strand."""
-        self._need_classify()
+        self._need("ngsid_classify.h", "refdb_build", "classify_search")
         if refdb.api is not self or refdb.handle is None: raise NgsidError(-2, "the reference library was released or belongs to another context")
         n = queries.n; K = max(int(top_k), 0)
         ref = np.full((n, K), -1, dtype=np.int32); sh = np.full((n, K), -1, dtype=np.int32); st = np.full((n, K), -1, dtype=np.int8)
@@ -755,18 +744,13 @@ class Api:
         return (ref, sh, st, nc) if n_codes else (ref, sh, st)
 
     # ---- include/ngsid_chimera.h
-    def _need_chimera(self):
-        if not hasattr(self.lib, self.prefix + "chimera_model"):
-            raise NgsidError(-2, "the bound library does not export %schimera_model (include/ngsid_chimera.h): rebuild it from this tree" % self.prefix)
-
     def chimera_model(self, queries, parents, pair_off, pair_parent, pair_gid=None, profiles=False):
         """ngsid_chimera_model: the best one-parent and two-parent model of every query over its pairs pair_parent[pair_off[q]:pair_off[q + 1]] (indices into parents;
         pair_gid: pairs of one gid are never combined, None = the parent index) -> fields [n, 7] int32 in CHIMERA_FIELDS order, -1 where a model does not exist;
         profiles=True: (fields, prof uint16, prof_off [n_pairs + 1]): prof[prof_off[k]:prof_off[k + 1]] = F_k[0 .. n] then B_k[0 .. n] of pair k.  queries / parents: lists of
         strings or read sets; the pair arrays are host arrays.  There is no CPU implementation: a library without the entry point is an error."""
-        self._need_chimera()
-        qs = queries if isinstance(queries, ReadSet) else ReadSet.from_strings(list(queries))
-        ps = parents if isinstance(parents, ReadSet) else ReadSet.from_strings(list(parents))
+        self._need("ngsid_chimera.h", "chimera_model")
+        qs, ps = _as_reads(queries), _as_reads(parents)
         po = np.ascontiguousarray(pair_off, dtype=np.uint64)
         pp = np.ascontiguousarray(pair_parent, dtype=np.uint32)
         pg = None if pair_gid is None else np.ascontiguousarray(pair_gid, dtype=np.int32)

@@ -23,7 +23,7 @@
 //        indices attaining both bounds - or gid(a) == g, so gid(b) != g - then F_a >= F best, B_b >= B second, likewise for (F best, B second);
 //     3. the smallest (value, a, b) over the two classes is therefore the smallest over those candidates, all of which are admissible.
 //   The lanes keep their smallest (value, i), a butterfly picks the wave's; a second pass over the winning pair's two profiles gives bp_hi.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_chimera.h"
 #include <algorithm>
 
@@ -48,17 +48,6 @@ CHM_PK2S(chm_add_s, "v_pk_add_u16")
 CHM_PK2S(chm_min_s, "v_pk_min_u16")
 __device__ __forceinline__ int chm_pk(int x) { return (x & 0xffff) | (x << 16); }
 __device__ __forceinline__ int chm_shr1(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, false); }      // lane l receives lane l - 1's value
-
-__global__ __launch_bounds__(256)
-void k_chimera_check(const uint8_t* __restrict__ seq, u64 total, uint32_t* __restrict__ bad)
-{
-    bool b = false;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += (u64)gridDim.x * 256) {
-        const uint8_t c = seq[i];
-        b |= !(c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N');
-    }
-    if (b) atomicOr(bad, 1u);
-}
 
 __global__ __launch_bounds__(64)
 void k_chimera_profile(const uint8_t* __restrict__ qseq, const uint64_t* __restrict__ qoff, const uint8_t* __restrict__ pseq, const uint64_t* __restrict__ poff,
@@ -232,16 +221,9 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
     {
         DevBuf<uint32_t> bad; HIPCHK(ctx, bad.alloc(1));
         HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), ctx->stream));
-        const DevReads* sets[2] = {&Q, &Pr};
-        for (const DevReads* S : sets) {
-            const uint64_t b0 = S->n ? S->h_off[0] : 0, T = S->n ? S->h_off[S->n] - b0 : 0;
-            if (!T) continue;
-            ProfScope ps_(ctx, "k_chimera_check");
-            hipLaunchKernelGGL(k_chimera_check, dim3((unsigned)std::min<uint64_t>((T + 255) / 256, 4096)), dim3(256), 0, ctx->stream, S->seq + b0, (u64)T, bad.p);
-            HIPCHK(ctx, hipGetLastError());
-        }
+        NGSID_TRY(ngsid_alphabet_scan(ctx, Q, bad.p, "k_chimera_check")); NGSID_TRY(ngsid_alphabet_scan(ctx, Pr, bad.p, "k_chimera_check"));
         uint32_t h_bad = 0;
-        HIPCHK(ctx, hipMemcpyAsync(&h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, ctx->stream));
+        NGSID_TRY(dev_get(ctx, &h_bad, bad.p, 1));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         if (h_bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a query or a parent holds a base outside upper-case ACGTN");
     }
@@ -262,8 +244,7 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
     const long long opt = ngsid_opt(ctx, "chimera_chunk_queries", 0);
     if (opt > 0) { for (uint64_t c = (uint64_t)opt; c < N; c += (uint64_t)opt) cuts.push_back(c); }
     else {
-        size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)4 << 30;
-        const size_t budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (4 * (size_t)ngsid_pool_contexts()), (size_t)64 << 20), (size_t)16 << 30);
+        const size_t budget = ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30);
         uint64_t acc = 0;
         for (uint64_t q = 0; q < N; ++q) { if (acc && acc + qbytes[q] > budget) { cuts.push_back(q); acc = 0; } acc += qbytes[q]; }
     }
@@ -276,15 +257,9 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
     const unsigned max_grid = (unsigned)ctx->n_cu * (strips ? 8u : 32u);
     HIPCHK(ctx, ctx->chm_bnd.reserve(strips ? (size_t)max_grid * 2 * bnd_stride : 1));
     DevBuf<uint32_t> d_pq, d_pp, d_ctr; DevBuf<int32_t> d_gid, d_fields; DevBuf<uint64_t> d_po, d_poff;
-    HIPCHK(ctx, d_pq.alloc(NP)); HIPCHK(ctx, d_pp.alloc(NP)); HIPCHK(ctx, d_gid.alloc(NP)); HIPCHK(ctx, d_po.alloc(NP + 1)); HIPCHK(ctx, d_poff.alloc(N + 1));
+    NGSID_TRY(dev_put(ctx, d_pq, h_pq.data(), NP)); NGSID_TRY(dev_put(ctx, d_pp, pair_parent, NP)); NGSID_TRY(dev_put(ctx, d_gid, h_gid.data(), NP));
+    NGSID_TRY(dev_put(ctx, d_po, h_po.data(), NP + 1)); NGSID_TRY(dev_put(ctx, d_poff, pair_off, N + 1));
     HIPCHK(ctx, d_ctr.alloc(cuts.size())); HIPCHK(ctx, d_fields.alloc(N * NGSID_CHIMERA_NFIELD));
-    if (NP) {
-        HIPCHK(ctx, hipMemcpyAsync(d_pq.p, h_pq.data(), sizeof(uint32_t) * NP, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_pp.p, pair_parent, sizeof(uint32_t) * NP, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_gid.p, h_gid.data(), sizeof(int32_t) * NP, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d_po.p, h_po.data(), sizeof(uint64_t) * (NP + 1), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_poff.p, pair_off, sizeof(uint64_t) * (N + 1), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, sizeof(uint32_t) * cuts.size(), ctx->stream));
     for (size_t c = 0; c + 1 < cuts.size(); ++c) {
         const uint64_t qa = cuts[c], qb = cuts[c + 1], ka = pair_off[qa], kb = pair_off[qb], v0 = h_po[ka], nv = h_po[kb] - v0;
@@ -299,10 +274,10 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
         { ProfScope ps_(ctx, "k_chimera_reduce");
           hipLaunchKernelGGL(k_chimera_reduce, dim3((unsigned)(qb - qa)), dim3(64), 0, ctx->stream, Q.off, (u64)qa, d_poff.p, (u64)ka, d_po.p + ka, (u64)v0, d_gid.p + ka, prof, d_fields.p); }
         HIPCHK(ctx, hipGetLastError());
-        if (profiles && nv) HIPCHK(ctx, hipMemcpyAsync(profiles + v0, ctx->chm_prof.p, sizeof(uint16_t) * nv, hipMemcpyDeviceToHost, ctx->stream));
+        if (profiles) NGSID_TRY(dev_get(ctx, profiles + v0, ctx->chm_prof.p, nv));
         if (c + 2 < cuts.size()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the next chunk rewrites the scratch
     }
-    HIPCHK(ctx, hipMemcpyAsync(fields, d_fields.p, sizeof(int32_t) * N * NGSID_CHIMERA_NFIELD, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, fields, d_fields.p, N * NGSID_CHIMERA_NFIELD));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }

@@ -17,7 +17,7 @@
 //      reference above t goes to the survivor list, the waves count their references at t;  4. the lowest-indexed references at t fill the list: a wave knows its rank
 //      base from the waves before it and ranks its own by ballot;  5. the at most 64 survivors are ordered by (shared descending, ref ascending) by rank counting.
 //   Integer LDS atomics build the histogram and hand out the slots of step 3; neither decides an order: the histogram is a sum and the slots are sorted in step 5.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_classify.h"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -247,10 +247,9 @@ extern "C" int32_t ngsid_refdb_build(ngsid_ctx* ctx, const ngsid_reads_t* refs, 
     ngsid_reads_t noq = *refs; noq.qual = nullptr;                       // qualities never influence a code
     DevReads R; rc = ngsid_upload_reads(ctx, &noq, &R, false); if (rc) return rc;
     const uint64_t n = R.n;
-    DevBuf<uint64_t> ccode, coff; DevBuf<uint32_t> cpos, dcnt, dhl; DevBuf<double> dherr, draw; PinVec<uint64_t> hmoff; PinVec<uint32_t> hcnt(n), hhl(n);
-    HIPCHK(ctx, dcnt.alloc(n)); HIPCHK(ctx, dhl.alloc(n)); HIPCHK(ctx, dherr.alloc(n)); HIPCHK(ctx, draw.alloc(n));
-    long long bad = -1;
-    rc = ngsid_minimizers_csr(ctx, R, prm->k, prm->w, MzOut{&ccode, &cpos, &coff, &hmoff}, dcnt.p, dhl.p, dherr.p, draw.p, hcnt.data(), hhl.data(), &bad); if (rc) return rc;
+    SketchBufs K; long long bad;
+    rc = ngsid_sketch(ctx, R, prm->k, prm->w, K, &bad); if (rc) return rc;
+    DevBuf<uint64_t> &ccode = K.code, &coff = K.off; DevBuf<uint32_t>& cpos = K.pos; const PinVec<uint64_t>& hmoff = K.h_off;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "reference %lld: base outside upper-case ACGTN", bad);
     const uint64_t M = hmoff[n];
@@ -342,18 +341,16 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
     DevReads D2; D2.n = 2 * N; D2.total = 2 * T; D2.maxlen = RD.maxlen; D2.minlen = RD.minlen; D2.h_off.resize(2 * N + 1);
     for (uint64_t q = 0; q < N; ++q) { const uint64_t a = RD.h_off[q] - b0, L = RD.h_off[q + 1] - RD.h_off[q]; D2.h_off[2 * q] = 2 * a; D2.h_off[2 * q + 1] = 2 * a + L; }
     D2.h_off[2 * N] = 2 * T;
-    HIPCHK(ctx, D2.own_seq.alloc(2 * T + 16)); HIPCHK(ctx, D2.own_off.alloc(2 * N + 1));
-    HIPCHK(ctx, hipMemcpyAsync(D2.own_off.p, D2.h_off.data(), sizeof(uint64_t) * (2 * N + 1), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, D2.own_seq.alloc(2 * T + 16)); NGSID_TRY(dev_put(ctx, D2.own_off, D2.h_off.data(), 2 * N + 1));
     { ProfScope ps_(ctx, "k_classify_revcomp");
       hipLaunchKernelGGL(k_classify_revcomp, dim3((unsigned)N), dim3(256), 0, ctx->stream, RD.seq, RD.off, (u64)N, D2.own_off.p, D2.own_seq.p); }
     HIPCHK(ctx, hipGetLastError());
     D2.seq = D2.own_seq.p; D2.off = D2.own_off.p; D2.qual = nullptr;
     // ---- their sketches: sorted distinct codes per (query, strand)
     const uint64_t S = 2 * N;
-    DevBuf<uint64_t> ccode, coff, scode, ucode; DevBuf<uint32_t> cpos, dcnt, dhl, ucnt; DevBuf<double> dherr, draw; PinVec<uint64_t> hmoff; PinVec<uint32_t> hcnt(S), hhl(S);
-    HIPCHK(ctx, dcnt.alloc(S)); HIPCHK(ctx, dhl.alloc(S)); HIPCHK(ctx, dherr.alloc(S)); HIPCHK(ctx, draw.alloc(S));
-    long long bad = -1;
-    rc = ngsid_minimizers_csr(ctx, D2, db->k, db->w, MzOut{&ccode, &cpos, &coff, &hmoff}, dcnt.p, dhl.p, dherr.p, draw.p, hcnt.data(), hhl.data(), &bad); if (rc) return rc;
+    DevBuf<uint64_t> scode, ucode; DevBuf<uint32_t> ucnt; SketchBufs K; long long bad;
+    rc = ngsid_sketch(ctx, D2, db->k, db->w, K, &bad); if (rc) return rc;
+    DevBuf<uint64_t> &ccode = K.code, &coff = K.off; const PinVec<uint64_t>& hmoff = K.h_off;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "query %lld: base outside upper-case ACGTN", bad / 2);
     const uint64_t M = hmoff[S];
@@ -376,11 +373,7 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
     uint64_t chunk = N;
     const long long opt = ngsid_opt(ctx, "classify_chunk_queries", 0);
     if (opt > 0) chunk = std::min<uint64_t>(N, (uint64_t)opt);
-    else {
-        size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)4 << 30;
-        const size_t budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (4 * (size_t)ngsid_pool_contexts()), (size_t)64 << 20), (size_t)16 << 30);
-        chunk = std::min<uint64_t>(N, std::max<uint64_t>(1, budget / row_bytes));
-    }
+    else chunk = std::min<uint64_t>(N, std::max<uint64_t>(1, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30) / row_bytes));
     HIPCHK(ctx, ctx->cls_cnt.reserve((size_t)chunk * 2 * n_refs));
     DevBuf<int32_t> d_ref, d_sh; DevBuf<int8_t> d_st;
     HIPCHK(ctx, d_ref.alloc(N * top_k)); HIPCHK(ctx, d_sh.alloc(N * top_k)); HIPCHK(ctx, d_st.alloc(N * top_k));
@@ -395,10 +388,8 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
           hipLaunchKernelGGL(k_classify_topk, dim3((unsigned)nq), dim3(CLS_THREADS), 0, ctx->stream, ctx->cls_cnt.p, n_refs, (u64)c0, ucnt.p, top_k, prm->min_shared, d_ref.p, d_sh.p, d_st.p); }
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipMemcpyAsync(cand_ref, d_ref.p, sizeof(int32_t) * N * top_k, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cand_shared, d_sh.p, sizeof(int32_t) * N * top_k, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(cand_strand, d_st.p, sizeof(int8_t) * N * top_k, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_codes) HIPCHK(ctx, hipMemcpyAsync(n_codes, ucnt.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, cand_ref, d_ref.p, N * top_k)); NGSID_TRY(dev_get(ctx, cand_shared, d_sh.p, N * top_k)); NGSID_TRY(dev_get(ctx, cand_strand, d_st.p, N * top_k));
+    if (n_codes) NGSID_TRY(dev_get(ctx, (uint32_t*)n_codes, ucnt.p, S));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }

@@ -11,7 +11,7 @@
 // staging), 4 x G x W bytes (at most 32 KB).  Registers: Pv, Mv, Eq (3 x 2), score / best / end, two keys.
 // The start of the WINNING tag only is computed, by the reversed pass of the host function (reversed tag = bit-reversed masks, reversed window prefix read backwards
 // from `end`, anchored): all lanes of the read-side run it redundantly, which costs one more pass per read-side.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_demux.h"
 #include <algorithm>
 
@@ -156,6 +156,16 @@ void k_demux_locate(const uint8_t* __restrict__ seq, const uint64_t* __restrict_
     }
 }
 
+int32_t ngsid_alphabet_scan(ngsid_ctx* ctx, const DevReads& R, uint32_t* d_flag, const char* prof_name)
+{
+    const uint64_t b0 = R.n ? R.h_off[0] : 0, nbases = R.n ? R.h_off[R.n] - b0 : 0;
+    if (!nbases) return NGSID_OK;
+    const auto launch = [&] { hipLaunchKernelGGL(k_demux_alphabet, dim3((unsigned)std::min<uint64_t>((nbases + 255) / 256, (uint64_t)ctx->n_cu * 16)), dim3(256), 0, ctx->stream, R.seq + b0, (u64)nbases, d_flag); };
+    if (prof_name) { ProfScope ps_(ctx, prof_name); launch(); } else launch();
+    HIPCHK(ctx, hipGetLastError());
+    return NGSID_OK;
+}
+
 bool ngsid_iupac_eq(uint8_t a, uint8_t b, int iupac);      // host_io.hip: the equality rule of ngsid_host_infix_locate
 
 extern "C" int32_t ngsid_demux_locate(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_reads_t* tags, const ngsid_demux_params_t* prm,
@@ -186,15 +196,9 @@ extern "C" int32_t ngsid_demux_locate(ngsid_ctx* ctx, const ngsid_reads_t* reads
         for (int c = 0; c < 5; ++c) { u64 v = 0; for (int i = 0; i < m; ++i) if (ngsid_iupac_eq(q[i], (uint8_t)"ACGTN"[c], prm->iupac)) v |= 1ull << i; h_peq[((size_t)(t >> 6) * 5 + c) * 64 + (t & 63)] = v; }
     }
     DevBuf<u64> d_peq; DevBuf<int32_t> d_tlen, d_hits; DevBuf<uint32_t> d_flag; DevBuf<int16_t> d_ed, d_end;
-    HIPCHK(ctx, d_peq.alloc(h_peq.size())); HIPCHK(ctx, d_tlen.alloc(h_tlen.size())); HIPCHK(ctx, d_hits.alloc(N * 2 * NGSID_DEMUX_NFIELD)); HIPCHK(ctx, d_flag.alloc(1));
-    HIPCHK(ctx, hipMemcpyAsync(d_peq.p, h_peq.data(), sizeof(u64) * h_peq.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_tlen.p, h_tlen.data(), sizeof(int32_t) * h_tlen.size(), hipMemcpyHostToDevice, ctx->stream));
+    NGSID_TRY(dev_put(ctx, d_peq, h_peq.data(), h_peq.size())); NGSID_TRY(dev_put(ctx, d_tlen, h_tlen.data(), h_tlen.size())); HIPCHK(ctx, d_hits.alloc(N * 2 * NGSID_DEMUX_NFIELD)); HIPCHK(ctx, d_flag.alloc(1));
     HIPCHK(ctx, hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), ctx->stream));
-    const uint64_t b0 = RD.h_off[0], nbases = RD.h_off[N] - b0;
-    if (nbases) {
-        hipLaunchKernelGGL(k_demux_alphabet, dim3((unsigned)std::min<uint64_t>((nbases + 255) / 256, (uint64_t)ctx->n_cu * 16)), dim3(256), 0, ctx->stream, RD.seq + b0, (u64)nbases, d_flag.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
+    NGSID_TRY(ngsid_alphabet_scan(ctx, RD, d_flag.p));
     // ---- lane mapping
     const int W = prm->window, Wpad = (W + 3) & ~3;
     int logTp = 0; while ((1 << logTp) < std::min(T, 64)) ++logTp;
@@ -205,11 +209,7 @@ extern "C" int32_t ngsid_demux_locate(ngsid_ctx* ctx, const ngsid_reads_t* reads
     uint64_t rows = N;
     const long long opt = ngsid_opt(ctx, "demux_chunk_reads", 0);
     if (opt > 0) rows = std::min<uint64_t>(N, (uint64_t)opt);
-    else if (nmat) {
-        size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)4 << 30;
-        const size_t budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (4 * (size_t)ngsid_pool_contexts()), (size_t)64 << 20), (size_t)2 << 30);
-        rows = std::min<uint64_t>(N, std::max<uint64_t>(1024, budget / ((size_t)2 * T * sizeof(int16_t) * nmat)));
-    }
+    else if (nmat) rows = std::min<uint64_t>(N, std::max<uint64_t>(1024, ngsid_mem_share(4, (size_t)64 << 20, (size_t)2 << 30, (size_t)4 << 30) / ((size_t)2 * T * sizeof(int16_t) * nmat)));
     if (ed_all) HIPCHK(ctx, d_ed.alloc(rows * 2 * T));
     if (end_all) HIPCHK(ctx, d_end.alloc(rows * 2 * T));
     for (uint64_t c0 = 0; c0 < N; c0 += rows) {
@@ -220,13 +220,12 @@ extern "C" int32_t ngsid_demux_locate(ngsid_ctx* ctx, const ngsid_reads_t* reads
                              RD.seq, RD.off, (u64)c0, (u64)nrs, d_peq.p, d_tlen.p, T, logTp, G, npass, W, Wpad, prm->max_ed,
                              d_hits.p + c0 * 2 * NGSID_DEMUX_NFIELD, ed_all ? d_ed.p : nullptr, end_all ? d_end.p : nullptr); }
         HIPCHK(ctx, hipGetLastError());
-        if (ed_all) HIPCHK(ctx, hipMemcpyAsync(ed_all + c0 * 2 * T, d_ed.p, sizeof(int16_t) * nrs * T, hipMemcpyDeviceToHost, ctx->stream));
-        if (end_all) HIPCHK(ctx, hipMemcpyAsync(end_all + c0 * 2 * T, d_end.p, sizeof(int16_t) * nrs * T, hipMemcpyDeviceToHost, ctx->stream));
+        if (ed_all) NGSID_TRY(dev_get(ctx, ed_all + c0 * 2 * T, d_ed.p, nrs * T));
+        if (end_all) NGSID_TRY(dev_get(ctx, end_all + c0 * 2 * T, d_end.p, nrs * T));
         if (nmat) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // the next chunk writes the same two buffers
     }
     uint32_t bad = 0;
-    HIPCHK(ctx, hipMemcpyAsync(hits, d_hits.p, sizeof(int32_t) * N * 2 * NGSID_DEMUX_NFIELD, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&bad, d_flag.p, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, hits, d_hits.p, N * 2 * NGSID_DEMUX_NFIELD)); NGSID_TRY(dev_get(ctx, &bad, d_flag.p, 1));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a read base outside upper-case ACGTN");
     return NGSID_OK;

@@ -133,13 +133,6 @@ static int32_t phase_layout(ngsid_ctx* ctx, const u64* grp_off, const u64* site_
     return NGSID_OK;
 }
 
-template <typename T> static int32_t phase_upload(ngsid_ctx* ctx, DevBuf<T>& d, const T* h, size_t n)
-{
-    HIPCHK(ctx, d.alloc(n));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-    return NGSID_OK;
-}
-
 extern "C" int32_t ngsid_phase_genotypes(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order,
                                          const uint64_t* grp_off, uint64_t n_groups, const ngsid_support_params_t* prm,
                                          const uint64_t* site_off, const uint32_t* site_pos, uint8_t* geno, int8_t* strand)
@@ -149,7 +142,7 @@ extern "C" int32_t ngsid_phase_genotypes(ngsid_ctx* ctx, const ngsid_reads_t* ce
     if (!grp_off || !site_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     const uint32_t G = (uint32_t)n_groups;
     std::vector<u64> geno_off; uint32_t max_s = 0;
-    DevBuf<u64> d_site_off, d_geno_off; DevBuf<uint32_t> d_site_pos, d_pair_x; DevBuf<uint8_t> d_geno; bool started = false; int lp_shift = 0;
+    DevBuf<u64> d_site_off, d_geno_off; DevBuf<uint32_t> d_site_pos, d_pair_x; DevBuf<uint8_t> d_geno; std::vector<uint32_t> pair_x; bool started = false; int lp_shift = 0;
     auto init = [&](const RecPlan& P) -> int32_t {
         int32_t rc = phase_layout(ctx, grp_off, site_off, G, geno_off, &max_s); if (rc) return rc;
         if (site_off[G] && !site_pos) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null site_pos");
@@ -164,8 +157,11 @@ extern "C" int32_t ngsid_phase_genotypes(ngsid_ctx* ctx, const ngsid_reads_t* ce
     auto start = [&](const RecPlan& P) -> int32_t {
         if (!geno_off[G]) return NGSID_OK;                                        // no site anywhere: the strands are the whole result
         int32_t rc;
-        if ((rc = phase_upload(ctx, d_site_off, site_off, (size_t)G + 1)) || (rc = phase_upload(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) ||
-            (rc = phase_upload(ctx, d_site_pos, site_pos, (size_t)site_off[G])) || (rc = phase_upload(ctx, d_pair_x, P.pair_x, (size_t)P.NP))) return rc;
+        if ((rc = dev_put(ctx, d_site_off, site_off, (size_t)G + 1)) || (rc = dev_put(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) ||
+            (rc = dev_put(ctx, d_site_pos, site_pos, (size_t)site_off[G]))) return rc;
+        pair_x.resize(P.NP);                                                      // position of every pair's read in the list of its group
+        for (u64 p = 0; p < P.NP; ++p) pair_x[p] = (uint32_t)(P.pair_x[p] - grp_off[P.pair_group[p]]);
+        NGSID_TRY(dev_put(ctx, d_pair_x, pair_x.data(), pair_x.size()));
         HIPCHK(ctx, d_geno.alloc(geno_off[G]));
         HIPCHK(ctx, hipMemsetAsync(d_geno.p, NGSID_GENO_NONE, geno_off[G], ctx->stream));
         while ((1u << lp_shift) < max_s) ++lp_shift;
@@ -182,7 +178,7 @@ extern "C" int32_t ngsid_phase_genotypes(ngsid_ctx* ctx, const ngsid_reads_t* ce
     };
     int32_t rc = ngsid_rec_walk(ctx, centres, reads, read_order, grp_off, n_groups, prm, strand, init, start, chunk); if (rc) return rc;
     if (!started) return NGSID_OK;
-    HIPCHK(ctx, hipMemcpyAsync(geno, d_geno.p, geno_off[G], hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, geno, d_geno.p, geno_off[G]));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }
@@ -207,14 +203,14 @@ extern "C" int32_t ngsid_phase_pair_tables(ngsid_ctx* ctx, const uint8_t* geno, 
     }
     if (items.empty()) return NGSID_OK;
     DevBuf<uint8_t> d_geno; DevBuf<u64> d_geno_off, d_site_off, d_tab_off; DevBuf<uint32_t> d_items, d_tables;
-    if ((rc = phase_upload(ctx, d_geno, geno, (size_t)geno_off[G])) || (rc = phase_upload(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) || (rc = phase_upload(ctx, d_site_off, site_off, (size_t)G + 1)) ||
-        (rc = phase_upload(ctx, d_tab_off, tab_off.data(), (size_t)G + 1)) || (rc = phase_upload(ctx, d_items, items.data(), items.size()))) return rc;
+    if ((rc = dev_put(ctx, d_geno, geno, (size_t)geno_off[G])) || (rc = dev_put(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) || (rc = dev_put(ctx, d_site_off, site_off, (size_t)G + 1)) ||
+        (rc = dev_put(ctx, d_tab_off, tab_off.data(), (size_t)G + 1)) || (rc = dev_put(ctx, d_items, items.data(), items.size()))) return rc;
     HIPCHK(ctx, d_tables.alloc(tab_off[G]));
     HIPCHK(ctx, hipMemsetAsync(d_tables.p, 0, sizeof(uint32_t) * tab_off[G], ctx->stream));
     { ProfScope ps_(ctx, "k_phase_pairs");
       hipLaunchKernelGGL(k_phase_pairs, dim3((unsigned)(items.size() / 4)), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_site_off.p, d_tab_off.p, d_items.p, d_tables.p); }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(tables, d_tables.p, sizeof(uint32_t) * tab_off[G], hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, tables, d_tables.p, tab_off[G]));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }
@@ -245,18 +241,16 @@ extern "C" int32_t ngsid_phase_assign(ngsid_ctx* ctx, const uint8_t* geno, const
     }
     if (items.empty()) return NGSID_OK;
     DevBuf<uint8_t> d_geno, d_hal, d_dist, d_dist2; DevBuf<int8_t> d_best; DevBuf<u64> d_geno_off, d_grp_off, d_site_off, d_hap_off, d_hal_off; DevBuf<uint32_t> d_items;
-    if ((rc = phase_upload(ctx, d_geno, geno, (size_t)geno_off[G])) || (rc = phase_upload(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) || (rc = phase_upload(ctx, d_grp_off, grp_off, (size_t)G + 1)) ||
-        (rc = phase_upload(ctx, d_site_off, site_off, (size_t)G + 1)) || (rc = phase_upload(ctx, d_hap_off, hap_off, (size_t)G + 1)) || (rc = phase_upload(ctx, d_hal_off, hal_off.data(), (size_t)G + 1)) ||
-        (rc = phase_upload(ctx, d_hal, hap_alleles, (size_t)hal_off[G])) || (rc = phase_upload(ctx, d_items, items.data(), items.size()))) return rc;
+    if ((rc = dev_put(ctx, d_geno, geno, (size_t)geno_off[G])) || (rc = dev_put(ctx, d_geno_off, geno_off.data(), (size_t)G + 1)) || (rc = dev_put(ctx, d_grp_off, grp_off, (size_t)G + 1)) ||
+        (rc = dev_put(ctx, d_site_off, site_off, (size_t)G + 1)) || (rc = dev_put(ctx, d_hap_off, hap_off, (size_t)G + 1)) || (rc = dev_put(ctx, d_hal_off, hal_off.data(), (size_t)G + 1)) ||
+        (rc = dev_put(ctx, d_hal, hap_alleles, (size_t)hal_off[G])) || (rc = dev_put(ctx, d_items, items.data(), items.size()))) return rc;
     HIPCHK(ctx, d_best.alloc(NL)); HIPCHK(ctx, d_dist.alloc(NL)); HIPCHK(ctx, d_dist2.alloc(NL));
     HIPCHK(ctx, hipMemsetAsync(d_best.p, 0xff, NL, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(d_dist.p, 0xff, NL, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(d_dist2.p, 0xff, NL, ctx->stream));
     { ProfScope ps_(ctx, "k_phase_assign");
       hipLaunchKernelGGL(k_phase_assign, dim3((unsigned)(items.size() / 2)), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_grp_off.p, d_site_off.p, d_hap_off.p, d_hal_off.p, d_hal.p,
                          d_items.p, d_best.p, d_dist.p, d_dist2.p); }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(best, d_best.p, NL, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dist, d_dist.p, NL, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dist2, d_dist2.p, NL, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, best, d_best.p, NL)); NGSID_TRY(dev_get(ctx, dist, d_dist.p, NL)); NGSID_TRY(dev_get(ctx, dist2, d_dist2.p, NL));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }

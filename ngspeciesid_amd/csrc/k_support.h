@@ -1,6 +1,6 @@
 // k_support.h - the store pass of ngsid_consensus_support (k_support.hip), shared with ngsid_phase_genotypes (k_phase.hip)
 #pragma once
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_support.h"
 #include <functional>
 
@@ -9,7 +9,7 @@ struct RecPlan {
     uint64_t total = 0, NP = 0;                      // bases of all centres, pairs (= listed reads with a strand)
     std::vector<uint64_t> boff;                      // host offsets of the centres
     std::vector<uint64_t> gbeg;                      // pairs [gbeg[g], gbeg[g + 1]) are group g's, in list order
-    const uint32_t* pair_x = nullptr;                // host: position of every pair's read in the list of its group
+    const uint32_t* pair_x = nullptr; const uint32_t* pair_group = nullptr;      // host: position of every pair's read in the caller's list, its group
     const uint32_t* d_pair_group = nullptr;          // device: group of every pair
     const uint8_t* d_cen_seq = nullptr; const uint64_t* d_cen_off = nullptr;      // device: the centres
 };

@@ -6,7 +6,6 @@
 // per (workgroup, position) with atomicAdd on uint32.  The traceback itself never touches the counters: its 64 lanes walk 64 reads of the same centre in near lockstep, so
 // every step would be 64 atomics on one address.  Integer adds commute: the result does not depend on the schedule.
 #include "k_support.h"
-#include <algorithm>
 
 typedef unsigned long long u64;
 
@@ -59,67 +58,29 @@ int32_t ngsid_rec_walk(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid
                        const ngsid_support_params_t* prm, int8_t* strand, const std::function<int32_t(const RecPlan&)>& init,
                        const std::function<int32_t(const RecPlan&)>& start, const std::function<int32_t(const RecPlan&, const RecChunk&)>& chunk)
 {
-    if (!centres || !reads || !grp_off || !prm) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    if (centres->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one centre per group expected");
+    if (!prm) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     if (prm->clip != 0 && prm->clip != 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_support_params_t.clip must be 0 or 1");
-    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
-    const uint64_t N = RD.n, NL = grp_off[n_groups]; const uint32_t G = (uint32_t)n_groups;
-    if (!read_order && NL > N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
-    if (read_order) for (uint64_t x = 0; x < NL; ++x) if (read_order[x] >= N) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
-    // centres to host strings (the strand detection takes them like the polisher's backbones)
-    RecPlan P; P.G = G; P.boff.assign(G + 1, 0);
-    std::vector<std::string> B(G); std::vector<uint64_t>& boff = P.boff; std::vector<uint8_t> bseq;
-    if (G) {
-        if (centres->mem == NGSID_MEM_DEVICE) {
-            HIPCHK(ctx, hipMemcpy(boff.data(), centres->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
-            if (boff[G]) HIPCHK(ctx, hipMemcpy(bseq.data(), centres->seq, boff[G], hipMemcpyDeviceToHost));
-        } else { memcpy(boff.data(), centres->off, 8 * (G + 1)); bseq.assign(centres->seq, centres->seq + boff[G]); bseq.push_back(0); }
-    }
-    const uint64_t total = boff[G]; uint32_t maxb = 0;
-    for (uint32_t g = 0; g < G; ++g) { B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g])); maxb = std::max<uint32_t>(maxb, (uint32_t)B[g].size()); }
-    P.total = total; P.maxb = maxb;
-    rc = init(P); if (rc) return rc;
-    if (strand) for (uint64_t x = 0; x < NL; ++x) strand[x] = -1;
+    GroupedReads S; NGSID_TRY(ngsid_groups_open(ctx, centres, reads, read_order, grp_off, n_groups, S));
+    const DevReads& RD = S.RD; const uint32_t G = S.G, maxb = S.maxb; const uint64_t total = S.boff[G];
+    RecPlan P; P.G = G; P.boff = S.boff; P.total = total; P.maxb = maxb;
+    int32_t rc = init(P); if (rc) return rc;
+    if (strand) for (uint64_t x = 0; x < S.NL; ++x) strand[x] = -1;
     if (maxb > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "centre longer than %d", NGSID_MAX_CONSENSUS_LEN);
-    // ---- read -> group map
-    std::vector<uint32_t> h_rgroup(N, 0xffffffffu);
-    for (uint32_t g = 0; g < G; ++g) for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-        const uint64_t r = read_order ? read_order[x] : x;
-        if (h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): list every read under one centre", (unsigned long long)r, h_rgroup[r], g);
-        h_rgroup[r] = g;
-    }
-    if (N == 0 || G == 0 || NL == 0) return NGSID_OK;
-    // ---- strand + oriented reads: the polisher's first stage
-    OrientBufs ob; static thread_local PinVec<uint8_t> h_orient;
-    rc = ngsid_polish_orient(ctx, RD, B, h_rgroup, prm->k, prm->w, ob, h_orient); if (rc) return rc;
-    // ---- pairs in list order (group by group); pairs [gbeg[g], gbeg[g+1]) are group g's
-    static thread_local PinVec<uint32_t> pair_read, pair_group, pair_x; pair_read.clear(); pair_group.clear(); pair_x.clear();
-    std::vector<uint64_t>& gbeg = P.gbeg; gbeg.assign(G + 1, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-            const uint64_t r = read_order ? read_order[x] : x;
-            if (h_orient[r] == 255) continue;
-            pair_read.push_back((uint32_t)r); pair_group.push_back(g); pair_x.push_back((uint32_t)(x - grp_off[g])); if (strand) strand[x] = (int8_t)h_orient[r];
-        }
-        gbeg[g + 1] = pair_read.size();
-    }
-    const uint64_t NP = pair_read.size(); P.NP = NP; P.pair_x = pair_x.data();
+    if (S.N == 0 || G == 0 || S.NL == 0) return NGSID_OK;
+    NGSID_TRY(ngsid_groups_pairs(ctx, read_order, grp_off, prm->k, prm->w, S, strand));
+    const uint64_t NP = S.NP; P.NP = NP; P.gbeg = S.gbeg;
     if (NP == 0 || total == 0) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return NGSID_OK; }
+    P.pair_x = S.pair_x->data(); P.pair_group = S.pair_group->data();
     DevBuf<uint32_t> d_pair_read, d_pair_group, d_rec; DevBuf<int32_t> d_span;
-    HIPCHK(ctx, d_pair_read.alloc(NP)); HIPCHK(ctx, d_pair_group.alloc(NP));
-    HIPCHK(ctx, hipMemcpyAsync(d_pair_read.p, pair_read.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(d_pair_group.p, pair_group.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
-    ngsid_reads_t br{bseq.data(), nullptr, boff.data(), G, NGSID_MEM_HOST, 0};
+    NGSID_TRY(dev_put(ctx, d_pair_read, S.pair_read->data(), NP)); NGSID_TRY(dev_put(ctx, d_pair_group, S.pair_group->data(), NP));
+    ngsid_reads_t br{S.bseq.data(), nullptr, S.boff.data(), G, NGSID_MEM_HOST, 0};
     DevReads BB; rc = ngsid_upload_reads(ctx, &br, &BB, false); if (rc) return rc;
     // ---- chunks of pairs under the byte budget of the path matrix (the share of the free device memory the POA batches take; option "support_budget_mb")
     const uint32_t stride = ((maxb + 63u) & ~63u) / 8;                    // dwords per row
     P.stride = stride; P.d_cen_seq = BB.seq; P.d_cen_off = BB.off; P.d_pair_group = d_pair_group.p;
     rc = start(P); if (rc) return rc;
-    size_t budget = 0;
-    { const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
-      if (mb > 0) budget = (size_t)mb << 20;
-      else { size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)16 << 30;
-             budget = std::min<size_t>(std::max<size_t>((freeb + ngsid_pool_cached_bytes()) / (3 * (size_t)ngsid_pool_contexts()), (size_t)256 << 20), (size_t)16 << 30); } }
+    const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
+    const size_t budget = mb > 0 ? (size_t)mb << 20 : ngsid_mem_share(3, (size_t)256 << 20, (size_t)16 << 30, (size_t)16 << 30);
     const uint64_t rows = std::min<uint64_t>(NP, std::max<uint64_t>(64, budget / ((size_t)stride * 4)));
     HIPCHK(ctx, d_rec.alloc(rows * stride)); HIPCHK(ctx, d_span.alloc(rows * 4));
     for (uint64_t c0 = 0; c0 < NP; c0 += rows) {
@@ -173,8 +134,7 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
     if (!started) return NGSID_OK;
     const uint32_t G = (uint32_t)n_groups; const uint64_t total = d_counts.n / NGSID_SUPPORT_NCOUNT;
     std::vector<u64> h_used(G);
-    HIPCHK(ctx, hipMemcpyAsync(counts, d_counts.p, sizeof(uint32_t) * NGSID_SUPPORT_NCOUNT * total, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(h_used.data(), d_used.p, sizeof(u64) * G, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, counts, d_counts.p, NGSID_SUPPORT_NCOUNT * total)); NGSID_TRY(dev_get(ctx, h_used.data(), d_used.p, G));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (n_used) for (uint32_t g = 0; g < G; ++g) n_used[g] = h_used[g];
     return NGSID_OK;

@@ -1,5 +1,5 @@
 // ngsid_api.hip - C-ABI entry points that are thin (context, uploads, aligner batch, minimizer CSR, scoring)
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_merge_schedule.h"
 #include "../../include/ngsid_tables.h"
 #include <math.h>
@@ -242,36 +242,24 @@ extern "C" int32_t ngsid_sg_align_cigar_batch(ngsid_ctx* ctx, const ngsid_reads_
                                               int32_t* score, uint64_t* ops_off, uint8_t* ops, uint64_t cap, uint64_t* needed)
 {
     if (!ctx) return NGSID_ERR_ARG;
-    if (!queries || !targets || !ops_off || (n_pairs && (!q_idx || !t_idx || !open))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    DevReads Q, T;
-    int32_t rc = ngsid_upload_reads(ctx, queries, &Q, false); if (rc) return rc;
-    rc = ngsid_upload_reads(ctx, targets, &T, false); if (rc) return rc;
+    if (!ops_off || (n_pairs && !open)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    PairBatch PB; int32_t rc = ngsid_pair_batch(ctx, queries, targets, q_idx, t_idx, n_pairs, PB); if (rc) return rc;
+    const DevReads &Q = PB.Q, &T = PB.T;
     ops_off[0] = 0;
     if (n_pairs == 0) { if (needed) *needed = 0; return NGSID_OK; }
-    uint32_t mq = 0, mt = 0;
     std::vector<uint64_t> h_off(n_pairs + 1, 0);
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        if (q_idx[p] >= Q.n || t_idx[p] >= T.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "pair %llu out of range", (unsigned long long)p);
-        const uint32_t ql = (uint32_t)(Q.h_off[q_idx[p] + 1] - Q.h_off[q_idx[p]]), tl = (uint32_t)(T.h_off[t_idx[p] + 1] - T.h_off[t_idx[p]]);
-        mq = std::max(mq, ql); mt = std::max(mt, tl);
-        h_off[p + 1] = h_off[p] + ql + tl;                    // capacity of the pair: every column consumes at least one base
-    }
-    DevBuf<uint32_t> dq, dt; DevBuf<int32_t> dopen, dout; DevBuf<uint64_t> doff; DevBuf<uint8_t> dops;
-    HIPCHK(ctx, dq.alloc(n_pairs)); HIPCHK(ctx, dt.alloc(n_pairs)); HIPCHK(ctx, dopen.alloc(n_pairs)); HIPCHK(ctx, dout.alloc(n_pairs * 4)); HIPCHK(ctx, doff.alloc(n_pairs + 1)); HIPCHK(ctx, dops.alloc(h_off[n_pairs] + 1));
-    HIPCHK(ctx, hipMemcpyAsync(dq.p, q_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dt.p, t_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dopen.p, open, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(doff.p, h_off.data(), 8 * (n_pairs + 1), hipMemcpyHostToDevice, ctx->stream));
+    for (uint64_t p = 0; p < n_pairs; ++p)                    // capacity of a pair: every column consumes at least one base
+        h_off[p + 1] = h_off[p] + (Q.h_off[q_idx[p] + 1] - Q.h_off[q_idx[p]]) + (T.h_off[t_idx[p] + 1] - T.h_off[t_idx[p]]);
+    DevBuf<int32_t> dopen, dout; DevBuf<uint64_t> doff; DevBuf<uint8_t> dops;
+    NGSID_TRY(dev_put(ctx, dopen, open, n_pairs)); NGSID_TRY(dev_put(ctx, doff, h_off.data(), n_pairs + 1)); HIPCHK(ctx, dout.alloc(n_pairs * 4)); HIPCHK(ctx, dops.alloc(h_off[n_pairs] + 1));
     AlignJob J{};
-    J.qseq = Q.seq; J.qoff = Q.off; J.tseq = T.seq; J.toff = T.off; J.qidx = dq.p; J.tidx = dt.p; J.npairs = n_pairs;
+    J.qseq = Q.seq; J.qoff = Q.off; J.tseq = T.seq; J.toff = T.off; J.qidx = PB.dq.p; J.tidx = PB.dt.p; J.npairs = n_pairs;
     J.match = match; J.mismatch = mismatch; J.ext = ext; J.k = 1; J.open = dopen.p; J.match_id = nullptr;
     J.score = dout.p; J.ncols = dout.p + n_pairs; J.nmatch = nullptr; J.region = nullptr; J.bp = nullptr; J.bp_windows = 0; J.window = 1; J.span = nullptr;
     J.ops = dops.p; J.ops_off = doff.p;
-    int mo = 0; for (uint64_t p = 0; p < n_pairs; ++p) { if (open[p] < 0) { mo = 1 << 20; break; } mo = std::max(mo, (int)open[p]); }
-    rc = ngsid_launch_align(ctx, J, mq, mt, mo); if (rc) return rc;
+    rc = ngsid_launch_align(ctx, J, PB.mq, PB.mt, ngsid_max_open(open, n_pairs)); if (rc) return rc;
     std::vector<int32_t> h(n_pairs * 2); std::vector<uint8_t> hops(h_off[n_pairs] + 1);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), dout.p, 8 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(hops.data(), dops.p, h_off[n_pairs], hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, h.data(), dout.p, 2 * n_pairs)); NGSID_TRY(dev_get(ctx, hops.data(), dops.p, h_off[n_pairs]));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (score) memcpy(score, h.data(), 4 * n_pairs);
     uint64_t total = 0; for (uint64_t p = 0; p < n_pairs; ++p) { total += (uint64_t)h[n_pairs + p]; ops_off[p + 1] = total; }
@@ -295,32 +283,19 @@ extern "C" int32_t ngsid_sg_align_batch(ngsid_ctx* ctx, const ngsid_reads_t* que
 {
     ApiClock api_clock_(ctx, "sg_align_batch");
     if (!ctx) return NGSID_ERR_ARG;
-    if (!queries || !targets || (n_pairs && (!q_idx || !t_idx || !open))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    DevReads Q, T;
-    int32_t rc = ngsid_upload_reads(ctx, queries, &Q, false); if (rc) return rc;
-    rc = ngsid_upload_reads(ctx, targets, &T, false); if (rc) return rc;
+    if (n_pairs && !open) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    PairBatch PB; int32_t rc = ngsid_pair_batch(ctx, queries, targets, q_idx, t_idx, n_pairs, PB); if (rc) return rc;
     if (n_pairs == 0) return NGSID_OK;
-    uint32_t mq = 0, mt = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        if (q_idx[p] >= Q.n || t_idx[p] >= T.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "pair %llu out of range", (unsigned long long)p);
-        mq = std::max<uint32_t>(mq, (uint32_t)(Q.h_off[q_idx[p] + 1] - Q.h_off[q_idx[p]]));
-        mt = std::max<uint32_t>(mt, (uint32_t)(T.h_off[t_idx[p] + 1] - T.h_off[t_idx[p]]));
-    }
-    DevBuf<uint32_t> dq, dt; DevBuf<int32_t> dopen, dmid, dout;
-    HIPCHK(ctx, dq.alloc(n_pairs)); HIPCHK(ctx, dt.alloc(n_pairs)); HIPCHK(ctx, dopen.alloc(n_pairs)); HIPCHK(ctx, dmid.alloc(n_pairs)); HIPCHK(ctx, dout.alloc(n_pairs * 4));
-    HIPCHK(ctx, hipMemcpyAsync(dq.p, q_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dt.p, t_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dopen.p, open, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    if (match_id) HIPCHK(ctx, hipMemcpyAsync(dmid.p, match_id, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    DevBuf<int32_t> dopen, dmid, dout;
+    NGSID_TRY(dev_put(ctx, dopen, open, n_pairs)); NGSID_TRY(dev_put(ctx, dmid, match_id, match_id ? n_pairs : 0)); HIPCHK(ctx, dout.alloc(n_pairs * 4));
     AlignJob J{};
-    J.qseq = Q.seq; J.qoff = Q.off; J.tseq = T.seq; J.toff = T.off; J.qidx = dq.p; J.tidx = dt.p; J.npairs = n_pairs;
+    J.qseq = PB.Q.seq; J.qoff = PB.Q.off; J.tseq = PB.T.seq; J.toff = PB.T.off; J.qidx = PB.dq.p; J.tidx = PB.dt.p; J.npairs = n_pairs;
     J.match = match; J.mismatch = mismatch; J.ext = ext; J.k = k; J.open = dopen.p; J.match_id = match_id ? dmid.p : nullptr;
     J.score = dout.p; J.ncols = dout.p + n_pairs; J.nmatch = dout.p + 2 * n_pairs; J.region = dout.p + 3 * n_pairs;
     J.bp = nullptr; J.bp_windows = 0; J.window = 1; J.span = nullptr;
-    int mo = 0; for (uint64_t p = 0; p < n_pairs; ++p) { if (open[p] < 0) { mo = 1 << 20; break; } mo = std::max(mo, (int)open[p]); }
-    rc = ngsid_launch_align(ctx, J, mq, mt, mo); if (rc) return rc;
+    rc = ngsid_launch_align(ctx, J, PB.mq, PB.mt, ngsid_max_open(open, n_pairs)); if (rc) return rc;
     std::vector<int32_t> h(n_pairs * 4);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), dout.p, 16 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, h.data(), dout.p, 4 * n_pairs));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (score) memcpy(score, h.data(), 4 * n_pairs);
     if (n_cols) memcpy(n_cols, h.data() + n_pairs, 4 * n_pairs);
@@ -335,30 +310,19 @@ extern "C" int32_t ngsid_ed_align_batch(ngsid_ctx* ctx, const ngsid_reads_t* que
                                         int32_t window, int32_t bp_windows, int32_t* distance, int32_t* span, int32_t* bp)
 {
     if (!ctx) return NGSID_ERR_ARG;
-    if (!queries || !targets || (n_pairs && (!q_idx || !t_idx))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     if (bp && (bp_windows <= 0 || window <= 0)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "bp needs window > 0 and bp_windows > 0");
-    DevReads Q, T;
-    int32_t rc = ngsid_upload_reads(ctx, queries, &Q, false); if (rc) return rc;
-    rc = ngsid_upload_reads(ctx, targets, &T, false); if (rc) return rc;
+    PairBatch PB; int32_t rc = ngsid_pair_batch(ctx, queries, targets, q_idx, t_idx, n_pairs, PB); if (rc) return rc;
     if (n_pairs == 0) return NGSID_OK;
-    uint32_t mq = 0, mt = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        if (q_idx[p] >= Q.n || t_idx[p] >= T.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "pair %llu out of range", (unsigned long long)p);
-        mq = std::max<uint32_t>(mq, (uint32_t)(Q.h_off[q_idx[p] + 1] - Q.h_off[q_idx[p]]));
-        mt = std::max<uint32_t>(mt, (uint32_t)(T.h_off[t_idx[p] + 1] - T.h_off[t_idx[p]]));
-    }
-    DevBuf<uint32_t> dq, dt; DevBuf<int32_t> ddist, dspan, dbp;
-    HIPCHK(ctx, dq.alloc(n_pairs)); HIPCHK(ctx, dt.alloc(n_pairs)); HIPCHK(ctx, ddist.alloc(n_pairs)); HIPCHK(ctx, dspan.alloc(n_pairs * 4));
+    DevBuf<int32_t> ddist, dspan, dbp;
+    HIPCHK(ctx, ddist.alloc(n_pairs)); HIPCHK(ctx, dspan.alloc(n_pairs * 4));
     if (bp) HIPCHK(ctx, dbp.alloc(n_pairs * (uint64_t)bp_windows * 4));
-    HIPCHK(ctx, hipMemcpyAsync(dq.p, q_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(dt.p, t_idx, 4 * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     AlignJob J{};
-    J.qseq = Q.seq; J.qoff = Q.off; J.tseq = T.seq; J.toff = T.off; J.qidx = dq.p; J.tidx = dt.p; J.npairs = n_pairs;
+    J.qseq = PB.Q.seq; J.qoff = PB.Q.off; J.tseq = PB.T.seq; J.toff = PB.T.off; J.qidx = PB.dq.p; J.tidx = PB.dt.p; J.npairs = n_pairs;
     J.bp = bp ? dbp.p : nullptr; J.bp_windows = bp ? bp_windows : 0; J.window = window; J.span = dspan.p;
-    rc = ngsid_launch_ed_align(ctx, J, mq, mt, ddist.p); if (rc) return rc;
-    if (distance) HIPCHK(ctx, hipMemcpyAsync(distance, ddist.p, 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    if (span) HIPCHK(ctx, hipMemcpyAsync(span, dspan.p, 16 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    if (bp) HIPCHK(ctx, hipMemcpyAsync(bp, dbp.p, 16ull * n_pairs * bp_windows, hipMemcpyDeviceToHost, ctx->stream));
+    rc = ngsid_launch_ed_align(ctx, J, PB.mq, PB.mt, ddist.p); if (rc) return rc;
+    if (distance) NGSID_TRY(dev_get(ctx, distance, ddist.p, n_pairs));
+    if (span) NGSID_TRY(dev_get(ctx, span, dspan.p, 4 * n_pairs));
+    if (bp) NGSID_TRY(dev_get(ctx, bp, dbp.p, 4 * n_pairs * (uint64_t)bp_windows));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }
@@ -372,17 +336,16 @@ extern "C" int32_t ngsid_hpc_minimizers(ngsid_ctx* ctx, const ngsid_reads_t* rea
     if (!reads || !mz_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     DevReads R; int32_t rc = ngsid_upload_reads(ctx, reads, &R, false); if (rc) return rc;
     const uint64_t n = R.n;
-    DevBuf<uint64_t> ccode, coff; DevBuf<uint32_t> cpos, dcnt, dhl; DevBuf<double> dherr, draw; PinVec<uint64_t> hmoff; PinVec<uint32_t> hcnt(n), hhl(n);
-    HIPCHK(ctx, dcnt.alloc(n)); HIPCHK(ctx, dhl.alloc(n)); HIPCHK(ctx, dherr.alloc(n)); HIPCHK(ctx, draw.alloc(n));
-    long long bad = -1;
-    rc = ngsid_minimizers_csr(ctx, R, k, w, MzOut{&ccode, &cpos, &coff, &hmoff}, dcnt.p, dhl.p, dherr.p, draw.p, hcnt.data(), hhl.data(), &bad); if (rc) return rc;      // (chunked: the sparse image of the kernel never exceeds 3 GB)
+    SketchBufs K; long long bad;
+    rc = ngsid_sketch(ctx, R, k, w, K, &bad); if (rc) return rc;      // (chunked: the sparse image of the kernel never exceeds 3 GB)
     if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "read %lld: base outside ACGTN", bad);
+    const PinVec<uint64_t>& hmoff = K.h_off; DevBuf<uint64_t> &ccode = K.code, &coff = K.off; DevBuf<uint32_t>& cpos = K.pos;
     std::vector<double> hherr(n);
-    if (n) HIPCHK(ctx, hipMemcpyAsync(hherr.data(), dherr.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    NGSID_TRY(dev_get(ctx, hherr.data(), K.herr.p, n));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t total = hmoff[n];
     if (needed) *needed = total;
-    if (hpc_len) memcpy(hpc_len, hhl.data(), 4 * n);
+    if (hpc_len) memcpy(hpc_len, K.h_hlen.data(), 4 * n);
     if (hpc_err) memcpy(hpc_err, hherr.data(), 8 * n);
     const bool dev_out = reads->mem == NGSID_MEM_DEVICE;
     if (total > cap || (total && (!codes || !pos))) {

@@ -1,0 +1,83 @@
+// ngsid_host.h - host-side plumbing the entry points share: transfers, the memory budget, list checks, the grouped-reads front end, pair batches, sketch scratch, the alphabet scan
+#pragma once
+#include "ngsid_internal.h"
+#include <algorithm>
+
+#define NGSID_TRY(call) do { const int32_t rc_ = (call); if (rc_) return rc_; } while (0)
+
+// ---- transfers on ctx->stream (asynchronous: the caller synchronises before the host side is read or reused)
+template <typename T> static inline int32_t dev_put(ngsid_ctx* ctx, DevBuf<T>& d, const T* h, size_t n)      // allocates n entries and fills them from the host
+{
+    HIPCHK(ctx, d.alloc(n));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
+    return NGSID_OK;
+}
+template <typename T> static inline int32_t dev_get(ngsid_ctx* ctx, T* h, const T* d, size_t n)
+{
+    if (n) HIPCHK(ctx, hipMemcpyAsync(h, d, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream));
+    return NGSID_OK;
+}
+
+// ---- the byte budget of a chunked call: the 1 / divisor share of the device memory that is free now (+ what the allocator's cache and the caller's own grow-only
+// buffers hold: both are reused), divided among the live contexts of the process, clamped to [floor, ceiling]
+static inline size_t ngsid_mem_share(size_t divisor, size_t floor, size_t ceiling, size_t free_if_unknown, size_t own_bytes = 0)
+{
+    size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = free_if_unknown;
+    return std::min(std::max((freeb + own_bytes + ngsid_pool_cached_bytes()) / (divisor * (size_t)ngsid_pool_contexts()), floor), ceiling);
+}
+
+// ---- read lists of a grouped call: reads read_order[grp_off[g] .. grp_off[g + 1]) (or the range itself without read_order) are group g
+static inline int32_t ngsid_check_lists(ngsid_ctx* ctx, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups, uint64_t n_reads)
+{
+    const uint64_t NL = grp_off[n_groups];
+    if (!read_order && NL > n_reads) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
+    if (read_order) for (uint64_t x = 0; x < NL; ++x) if (read_order[x] >= n_reads) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
+    return NGSID_OK;
+}
+
+// ---- grouped-reads front end (poa_host.hip) of ngsid_polish* and of the support walk (k_support.hip): reads listed under one centre (backbone) per group.
+// ngsid_groups_open: argument and list checks, the reads on the device, the centres on the host.  The caller validates and clears its own outputs, returns early where
+// nothing is listed (N == 0 || G == 0), then ngsid_groups_pairs: the read -> group map (one pass over the lists; a read listed twice is an error), strands and oriented
+// copies (ngsid_polish_orient), the pairs = listed reads with a strand, in list order.  The pair vectors are pinned and belong to the calling thread: valid until its next call.
+struct GroupedReads {
+    DevReads RD; uint64_t N = 0, NL = 0, NP = 0; uint32_t G = 0, maxb = 0;      // reads of the set, listed reads, pairs, groups, longest centre
+    std::vector<uint64_t> boff; std::vector<uint8_t> bseq; std::vector<std::string> B;      // the centres: host offsets, bytes (+ one 0), strings
+    std::vector<uint32_t> h_rgroup; std::vector<uint64_t> gbases;                           // group of every read (0xffffffff: none), bases listed per group
+    OrientBufs ob; PinVec<uint8_t>* h_orient = nullptr;                                     // per read 0 forward, 1 reverse complement, 255 no strand; oriented copies in ctx->pol_oseq / pol_oqual
+    PinVec<uint32_t> *pair_read = nullptr, *pair_group = nullptr, *pair_x = nullptr;        // per pair: read, group, position of the read in the caller's list
+    std::vector<uint64_t> gbeg;                                                             // pairs [gbeg[g], gbeg[g + 1]) are group g's
+};
+int32_t ngsid_groups_open(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups, GroupedReads& S);
+int32_t ngsid_groups_pairs(ngsid_ctx* ctx, const uint32_t* read_order, const uint64_t* grp_off, int k, int w, GroupedReads& S, int8_t* strand = nullptr);      // strand: [NL], written for the pairs
+
+// ---- pair batches of the aligner entry points: both read sets on the device, the index lists checked and uploaded, the longest query and target of the batch
+struct PairBatch { DevReads Q, T; DevBuf<uint32_t> dq, dt; uint32_t mq = 0, mt = 0; };
+static inline int32_t ngsid_pair_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs, PairBatch& B)
+{
+    if (!queries || !targets || (n_pairs && (!q_idx || !t_idx))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    NGSID_TRY(ngsid_upload_reads(ctx, queries, &B.Q, false)); NGSID_TRY(ngsid_upload_reads(ctx, targets, &B.T, false));
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        if (q_idx[p] >= B.Q.n || t_idx[p] >= B.T.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "pair %llu out of range", (unsigned long long)p);
+        B.mq = std::max<uint32_t>(B.mq, (uint32_t)(B.Q.h_off[q_idx[p] + 1] - B.Q.h_off[q_idx[p]]));
+        B.mt = std::max<uint32_t>(B.mt, (uint32_t)(B.T.h_off[t_idx[p] + 1] - B.T.h_off[t_idx[p]]));
+    }
+    if (n_pairs) { NGSID_TRY(dev_put(ctx, B.dq, q_idx, n_pairs)); NGSID_TRY(dev_put(ctx, B.dt, t_idx, n_pairs)); }
+    return NGSID_OK;
+}
+static inline int ngsid_max_open(const int32_t* open, uint64_t n)      // bound of the gap-open costs for ngsid_launch_align (a negative one: no bound)
+{
+    int mo = 0; for (uint64_t p = 0; p < n; ++p) { if (open[p] < 0) return 1 << 20; mo = std::max(mo, (int)open[p]); }
+    return mo;
+}
+
+// ---- the temporaries of one ngsid_minimizers_csr call: the CSR, the per-read device arrays and their host mirrors
+struct SketchBufs { DevBuf<uint64_t> code, off; DevBuf<uint32_t> pos, cnt, hlen; DevBuf<double> herr, rawerr; PinVec<uint64_t> h_off; PinVec<uint32_t> h_cnt, h_hlen; };
+static inline int32_t ngsid_sketch(ngsid_ctx* ctx, const DevReads& R, int k, int w, SketchBufs& S, long long* bad)      // *bad: a read with a base outside ACGTN, or -1
+{
+    const uint64_t n = R.n; S.h_cnt.resize(n); S.h_hlen.resize(n); *bad = -1;
+    HIPCHK(ctx, S.cnt.alloc(n)); HIPCHK(ctx, S.hlen.alloc(n)); HIPCHK(ctx, S.herr.alloc(n)); HIPCHK(ctx, S.rawerr.alloc(n));
+    return ngsid_minimizers_csr(ctx, R, k, w, MzOut{&S.code, &S.pos, &S.off, &S.h_off}, S.cnt.p, S.hlen.p, S.herr.p, S.rawerr.p, S.h_cnt.data(), S.h_hlen.data(), bad);
+}
+
+// ---- k_demux.hip: enqueues the scan of R's bases; *d_flag (cleared by the caller) becomes non-zero when one is outside upper-case ACGTN.  The caller reads the flag.
+int32_t ngsid_alphabet_scan(ngsid_ctx* ctx, const DevReads& R, uint32_t* d_flag, const char* prof_name = nullptr);

@@ -1,6 +1,6 @@
 // poa_host.hip - host drivers over the POA tile engine: the depth-tiled hierarchy, ngsid_poa_consensus (a13,a14)
 // and ngsid_polish (a16,a17).  Mirrors oracle/ngsid_oracle_poa.c: run_hierarchy / ongsid_poa_consensus / ongsid_polish.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "k_poa.h"
 #include <thread>
 #include <atomic>
@@ -567,14 +567,9 @@ int32_t run_hierarchy(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0, co
         if (!any) return NGSID_OK;
         return run_hierarchy(ctx, d_level0, maxlen0, d_bbs, bb_len, units, hb);      // the large units (the others are done: every loop below skips them)
     }
-    size_t budget = 0;
-    { const long long mb = ngsid_opt(ctx, "poa_level_budget_mb", 0);
-      if (mb > 0) budget = (size_t)mb << 20;
-      else {
-          size_t freeb = 0, totalb = 0; if (hipMemGetInfo(&freeb, &totalb) != hipSuccess) freeb = (size_t)16 << 30;
-          size_t own = 0; for (auto& L : ctx->poa_lv) own += L.out.abytes + L.out_cov.abytes + L.seqs.abytes;       // grow-only buffers of this context that the call will reuse
-          budget = std::min<size_t>(std::max<size_t>((freeb + own + ngsid_pool_cached_bytes()) / (3 * (size_t)ngsid_pool_contexts()), (size_t)1 << 30), (size_t)48 << 30);      // (contexts of one process share the device: eight virtual ranks each take a 24th)
-      } }
+    size_t own = 0; for (auto& L : ctx->poa_lv) own += L.out.abytes + L.out_cov.abytes + L.seqs.abytes;       // grow-only buffers of this context that the call will reuse
+    const long long mb = ngsid_opt(ctx, "poa_level_budget_mb", 0);
+    const size_t budget = mb > 0 ? (size_t)mb << 20 : ngsid_mem_share(3, (size_t)1 << 30, (size_t)48 << 30, (size_t)16 << 30, own);      // (contexts of one process share the device: eight virtual ranks each take a 24th)
     // bytes per level-0 tile: both ping-pong level buffers (the second holds ~slots / D of the first + 25 %), as run_hierarchy_dev sizes them
     int maxbb = 0; for (const Unit& U : units) if (!U.done && U.bb >= 0) maxbb = std::max(maxbb, bb_len[U.bb]);
     const int Lb = std::max<int>((int)maxlen0, maxbb), Lb2 = Lb + Lb / 4 + 16;
@@ -640,11 +635,10 @@ static int32_t poa_consensus_impl(ngsid_ctx* ctx, const ngsid_reads_t* reads, co
     HostTimer htc(ctx->stream, "consensus");
     DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
     htc.mark("upload");
-    if (!read_order && grp_off[n_groups] > RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
-    if (read_order) for (uint64_t x = 0; x < grp_off[n_groups]; ++x) if (read_order[x] >= RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
+    NGSID_TRY(ngsid_check_lists(ctx, read_order, grp_off, n_groups, RD.n));
     htc.mark("checks");
     DevBuf<PSeq> d_seqs; HIPCHK(ctx, d_seqs.alloc(RD.n));
-    DevBuf<uint32_t> d_weight; if (weight && RD.n) { HIPCHK(ctx, d_weight.alloc(RD.n)); HIPCHK(ctx, hipMemcpyAsync(d_weight.p, weight, 4 * RD.n, hipMemcpyHostToDevice, ctx->stream)); }
+    DevBuf<uint32_t> d_weight; if (weight && RD.n) NGSID_TRY(dev_put(ctx, d_weight, weight, RD.n));
     if (RD.n) hipLaunchKernelGGL(k_make_pseq_reads, dim3((unsigned)((RD.n + 255) / 256)), dim3(256), 0, ctx->stream, RD.seq, RD.qual, RD.off, RD.n, prm->mode, weight ? d_weight.p : (const uint32_t*)nullptr, d_seqs.p);
     HIPCHK(ctx, hipGetLastError());
     std::vector<Unit> units(n_groups);
@@ -827,8 +821,7 @@ int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vecto
     // ---- strand detection (replaces minimap2's strand call): shared HPC minimizers with the initial backbone, fw vs rc
     DevBuf<uint64_t>& mzcode = ctx->pol_mzcode; DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen; DevBuf<uint32_t>& d_rgroup = S.d_rgroup; DevBuf<double>& herr = S.herr; DevBuf<double>& rawerr = S.rawerr; DevBuf<uint8_t>& d_orient = S.d_orient;
     HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N));
-    HIPCHK(ctx, d_rgroup.alloc(N)); HIPCHK(ctx, d_orient.alloc(N));
-    HIPCHK(ctx, hipMemcpyAsync(d_rgroup.p, h_rgroup.data(), 4 * N, hipMemcpyHostToDevice, ctx->stream));
+    NGSID_TRY(dev_put(ctx, d_rgroup, h_rgroup.data(), N)); HIPCHK(ctx, d_orient.alloc(N));
     const int sk = std::min(k, 21), sw = std::max(w, sk);       // strand detection only needs SOME minimizer scheme: one-word codes, comparable between the two launches
     {   // the clustering call that preceded this one left the minimizers of the same reads in the context (same bases, offsets, k, w): reuse them
         bool hit = false;
@@ -851,34 +844,79 @@ int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vecto
         std::vector<uint64_t> toff(2 * G + 1, 0); std::string cat; for (size_t i = 0; i < two.size(); ++i) { cat += two[i]; toff[i + 1] = cat.size(); }
         ngsid_reads_t br{(const uint8_t*)cat.data(), nullptr, toff.data(), 2ull * G, NGSID_MEM_HOST, 0};
         DevReads BR; rc = ngsid_upload_reads(ctx, &br, &BR, false); if (rc) return rc;
-        DevBuf<uint64_t> bc, boff_; DevBuf<uint32_t> bp_, bcnt, bhl; DevBuf<double> be, bw; static thread_local PinVec<uint64_t> hmo; static thread_local PinVec<uint32_t> hcnt, hhl; hcnt.resize(2 * G); hhl.resize(2 * G);
-        HIPCHK(ctx, bcnt.alloc(2 * G)); HIPCHK(ctx, bhl.alloc(2 * G)); HIPCHK(ctx, be.alloc(2 * G)); HIPCHK(ctx, bw.alloc(2 * G));
-        long long bad = -1;
-        rc = ngsid_minimizers_csr(ctx, BR, sk, sw, MzOut{&bc, &bp_, &boff_, &hmo}, bcnt.p, bhl.p, be.p, bw.p, hcnt.data(), hhl.data(), &bad); if (rc) return rc;
+        SketchBufs K; long long bad;
+        rc = ngsid_sketch(ctx, BR, sk, sw, K, &bad); if (rc) return rc;
         if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "base outside ACGTN in a backbone");
-        const uint64_t btot = hmo[2 * G];
+        const PinVec<uint64_t>& hmo = K.h_off; const uint64_t btot = hmo[2 * G];
         std::vector<uint64_t> hc(btot + 1);
-        if (btot) HIPCHK(ctx, hipMemcpyAsync(hc.data(), bc.p, 8 * btot, hipMemcpyDeviceToHost, ctx->stream));
+        NGSID_TRY(dev_get(ctx, hc.data(), K.code.p, btot));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         std::vector<uint64_t> lists, loff(2 * G + 1, 0);
         for (uint32_t i = 0; i < 2 * G; ++i) {
-            const uint32_t c = hhl[i] >= (uint32_t)sk ? hcnt[i] : 0;
+            const uint32_t c = K.h_hlen[i] >= (uint32_t)sk ? K.h_cnt[i] : 0;
             std::vector<uint64_t> v(hc.begin() + hmo[i], hc.begin() + hmo[i] + c); std::sort(v.begin(), v.end());
             lists.insert(lists.end(), v.begin(), v.end()); loff[i + 1] = lists.size();
         }
-        DevBuf<uint64_t> d_lists, d_loff; HIPCHK(ctx, d_lists.alloc(lists.size() + 1)); HIPCHK(ctx, d_loff.alloc(loff.size()));
-        if (!lists.empty()) HIPCHK(ctx, hipMemcpyAsync(d_lists.p, lists.data(), 8 * lists.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(d_loff.p, loff.data(), 8 * loff.size(), hipMemcpyHostToDevice, ctx->stream));
+        DevBuf<uint64_t> d_lists, d_loff; NGSID_TRY(dev_put(ctx, d_lists, lists.data(), lists.size())); NGSID_TRY(dev_put(ctx, d_loff, loff.data(), loff.size()));
         { ProfScope ps_(ctx, "k_strand"); hipLaunchKernelGGL(k_strand, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, ctx->mz_off.p, mzcnt.p, hlen.p, mzcode.p, sk, d_rgroup.p, d_lists.p, d_loff.p, G, N, d_orient.p); }
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     h_orient.resize(N);
-    HIPCHK(ctx, hipMemcpyAsync(h_orient.data(), d_orient.p, N, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    NGSID_TRY(dev_get(ctx, h_orient.data(), d_orient.p, N)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // ---- oriented copies of the reads
     DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual; HIPCHK(ctx, oseq.reserve(RD.total + 16)); if (RD.qual) HIPCHK(ctx, oqual.reserve(RD.total + 16));
     { ProfScope ps_(ctx, "k_orient"); hipLaunchKernelGGL(k_orient, dim3((unsigned)N), dim3(128), 0, ctx->stream, RD.seq, RD.qual, RD.off, N, d_orient.p, oseq.p, RD.qual ? oqual.p : nullptr); }
     HIPCHK(ctx, hipGetLastError());
+    return NGSID_OK;
+}
+
+// The grouped-reads front end (ngsid_host.h), first half: argument and list checks, the reads on the device, the centres on the host
+int32_t ngsid_groups_open(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups, GroupedReads& S)
+{
+    if (!centres || !reads || !grp_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    if (centres->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one centre (backbone) per group expected");
+    NGSID_TRY(ngsid_upload_reads(ctx, reads, &S.RD, false));
+    NGSID_TRY(ngsid_check_lists(ctx, read_order, grp_off, n_groups, S.RD.n));
+    const uint32_t G = (uint32_t)n_groups; S.G = G; S.N = S.RD.n; S.NL = grp_off[n_groups];
+    S.boff.assign(G + 1, 0); S.B.resize(G);
+    if (G) {
+        if (centres->mem == NGSID_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpy(S.boff.data(), centres->off, 8 * (G + 1), hipMemcpyDeviceToHost)); S.bseq.resize(S.boff[G] + 1);
+            if (S.boff[G]) HIPCHK(ctx, hipMemcpy(S.bseq.data(), centres->seq, S.boff[G], hipMemcpyDeviceToHost));
+        } else { memcpy(S.boff.data(), centres->off, 8 * (G + 1)); S.bseq.assign(centres->seq, centres->seq + S.boff[G]); S.bseq.push_back(0); }
+    }
+    for (uint32_t g = 0; g < G; ++g) { S.B[g].assign((const char*)S.bseq.data() + S.boff[g], (size_t)(S.boff[g + 1] - S.boff[g])); S.maxb = std::max<uint32_t>(S.maxb, (uint32_t)S.B[g].size()); }
+    return NGSID_OK;
+}
+
+// ... second half: the read -> group map, strands and oriented copies, the pairs in list order (group by group)
+int32_t ngsid_groups_pairs(ngsid_ctx* ctx, const uint32_t* read_order, const uint64_t* grp_off, int k, int w, GroupedReads& S, int8_t* strand)
+{
+    static thread_local PinVec<uint8_t> h_orient; static thread_local PinVec<uint32_t> pair_read, pair_group, pair_x;
+    S.h_orient = &h_orient; S.pair_read = &pair_read; S.pair_group = &pair_group; S.pair_x = &pair_x; pair_read.clear(); pair_group.clear(); pair_x.clear();
+    const uint32_t G = S.G; const OffView& off = S.RD.h_off;
+    S.h_rgroup.assign(S.N, 0xffffffffu); S.gbases.assign(G, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        uint64_t tot = 0;
+        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
+            const uint64_t r = read_order ? read_order[x] : x;
+            if (S.h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): strand and layers are kept per read, list every read under one centre (backbone)", (unsigned long long)r, S.h_rgroup[r], g);
+            S.h_rgroup[r] = g; tot += off[r + 1] - off[r];
+        }
+        S.gbases[g] = tot;
+    }
+    NGSID_TRY(ngsid_polish_orient(ctx, S.RD, S.B, S.h_rgroup, k, w, S.ob, h_orient));
+    S.gbeg.assign(G + 1, 0);
+    for (uint32_t g = 0; g < G; ++g) {
+        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
+            const uint64_t r = read_order ? read_order[x] : x;
+            if (h_orient[r] == 255) continue;
+            pair_read.push_back((uint32_t)r); pair_group.push_back(g); pair_x.push_back((uint32_t)x); if (strand) strand[x] = (int8_t)h_orient[r];
+        }
+        S.gbeg[g + 1] = pair_read.size();
+    }
+    S.NP = pair_read.size();
     return NGSID_OK;
 }
 
@@ -887,25 +925,13 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
                            uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used, PolishTrace* trace)
 {
     if (!ctx) return NGSID_ERR_ARG;
-    if (!backbones || !reads || !grp_off || !prm || !out_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    if (backbones->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one backbone per group expected");
+    if (!prm || !out_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     HostTimer ht(ctx->stream, "polish");
-    DevReads RD; int32_t rc = ngsid_upload_reads(ctx, reads, &RD, false); if (rc) return rc;
-    if (!read_order && grp_off[n_groups] > RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "group offsets exceed the read set");
-    if (read_order) for (uint64_t x = 0; x < grp_off[n_groups]; ++x) if (read_order[x] >= RD.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read_order[%llu] out of range", (unsigned long long)x);
-    const uint64_t N = RD.n; const uint32_t G = (uint32_t)n_groups;
+    GroupedReads S; int32_t rc = ngsid_groups_open(ctx, backbones, reads, read_order, grp_off, n_groups, S); if (rc) return rc;
+    const DevReads& RD = S.RD; std::vector<std::string>& B = S.B;       // (the backbones are tiny and are rebuilt on the host after every iteration)
+    const uint64_t N = S.N; const uint32_t G = S.G;
     const int W = prm->window > 0 ? prm->window : 500;
     ht.mark("upload + checks");
-    // backbones to host strings (they are tiny and are rebuilt on the host after every iteration)
-    std::vector<std::string> B(G);
-    {
-        std::vector<uint64_t> boff(G + 1); std::vector<uint8_t> bseq;
-        if (backbones->mem == NGSID_MEM_DEVICE) {
-            HIPCHK(ctx, hipMemcpy(boff.data(), backbones->off, 8 * (G + 1), hipMemcpyDeviceToHost)); bseq.resize(boff[G] + 1);
-            if (boff[G]) HIPCHK(ctx, hipMemcpy(bseq.data(), backbones->seq, boff[G], hipMemcpyDeviceToHost));
-        } else { memcpy(boff.data(), backbones->off, 8 * (G + 1)); bseq.assign(backbones->seq, backbones->seq + boff[G]); bseq.push_back(0); }
-        for (uint32_t g = 0; g < G; ++g) B[g].assign((const char*)bseq.data() + boff[g], (size_t)(boff[g + 1] - boff[g]));
-    }
     if (N == 0 || G == 0) {
         uint64_t total = 0; out_off[0] = 0; bool ovf = false;
         for (uint32_t g = 0; g < G; ++g) { if (trace) {} else if (total + B[g].size() <= out_cap && out) memcpy(out + total, B[g].data(), B[g].size()); else if (B[g].size()) ovf = true; total += B[g].size(); out_off[g + 1] = total; if (n_used) n_used[g] = 0; }
@@ -913,34 +939,21 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
         if (trace && trace->aln) for (uint64_t x = 0; x < (uint64_t)prm->iters * grp_off[n_groups] * 6; ++x) trace->aln[x] = -1;
         if (needed) *needed = total; if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "output buffer too small"); return NGSID_OK;
     }
-    // ---- read -> group map, mean read length per group (TGS/NGS window type)
-    std::vector<uint32_t> h_rgroup(N, 0xffffffffu); std::vector<uint8_t> tgs(G, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        double tot = 0; const uint64_t ns = grp_off[g + 1] - grp_off[g];
-        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-            const uint64_t r = read_order ? read_order[x] : x;
-            if (h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): strand and layers are kept per read, list every read under one backbone", (unsigned long long)r, h_rgroup[r], g);
-            h_rgroup[r] = g; tot += (double)(RD.h_off[r + 1] - RD.h_off[r]);
-        }
-        tgs[g] = ns > 0 && (tot / (double)ns) > 1000.0;
-    }
-    ht.mark("group map");
-    OrientBufs ob; DevBuf<int> flag; HIPCHK(ctx, flag.alloc(1)); static thread_local PinVec<uint8_t> h_orient;
-    rc = ngsid_polish_orient(ctx, RD, B, h_rgroup, prm->k, prm->w, ob, h_orient); if (rc) return rc;
+    // ---- strands and pairs (usable reads of reads that belong to a group), fixed over the iterations; the TGS/NGS window type of a group from the mean length of its reads
+    DevBuf<int> flag; HIPCHK(ctx, flag.alloc(1));
+    rc = ngsid_groups_pairs(ctx, read_order, grp_off, prm->k, prm->w, S); if (rc) return rc;
+    std::vector<uint8_t> tgs(G, 0);
+    for (uint32_t g = 0; g < G; ++g) { const uint64_t ns = grp_off[g + 1] - grp_off[g]; tgs[g] = ns > 0 && ((double)S.gbases[g] / (double)ns) > 1000.0; }
     DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual;
-    ht.mark("minimizers + strand + orient");
-    // ---- pairs (usable reads of reads that belong to a group), fixed over the iterations
-    static thread_local PinVec<uint32_t> pair_read, pair_group; pair_read.clear(); pair_group.clear();
+    PinVec<uint8_t>& h_orient = *S.h_orient; PinVec<uint32_t> &pair_read = *S.pair_read, &pair_group = *S.pair_group, &pair_pos = *S.pair_x;      // (pair_pos: the alignment trace's position of a pair's read in the caller's list)
+    ht.mark("group map + minimizers + strand + orient");
     const bool want_aln = trace && trace->aln; const uint64_t NL = grp_off[n_groups];
-    std::vector<uint64_t> pair_pos;                    // (alignment trace) position of a pair's read in the caller's list
-    for (uint64_t x = 0; x < grp_off[n_groups]; ++x) { const uint64_t r = read_order ? read_order[x] : x; if (h_orient[r] != 255) { pair_read.push_back((uint32_t)r); pair_group.push_back(h_rgroup[r]); if (want_aln) pair_pos.push_back(x); } }
     DevBuf<int32_t> d_dist; static thread_local PinVec<int32_t> h_span, h_dist;
     if (want_aln) { HIPCHK(ctx, d_dist.alloc(pair_read.size() + 1)); h_span.resize(pair_read.size() * 4 + 4); h_dist.resize(pair_read.size() + 1); }
     uint64_t NP = pair_read.size();
     DevBuf<uint32_t> d_pair_read, d_pair_group; DevBuf<int32_t> d_open, d_span, d_blen; DevBuf<int32_t>& d_bp = ctx->pol_bp; DevBuf<uint8_t>& d_lay_raw = ctx->pol_lay; DevBuf<uint16_t>& d_valid = ctx->pol_valid;
-    HIPCHK(ctx, d_pair_read.alloc(NP)); HIPCHK(ctx, d_pair_group.alloc(NP)); HIPCHK(ctx, d_open.alloc(NP)); HIPCHK(ctx, d_span.alloc(NP * 4)); HIPCHK(ctx, d_blen.alloc(G));
-    if (NP) { HIPCHK(ctx, hipMemcpyAsync(d_pair_read.p, pair_read.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream)); HIPCHK(ctx, hipMemcpyAsync(d_pair_group.p, pair_group.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream));
-              HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)d_open.p, prm->aln_open, NP, ctx->stream)); }
+    NGSID_TRY(dev_put(ctx, d_pair_read, pair_read.data(), NP)); NGSID_TRY(dev_put(ctx, d_pair_group, pair_group.data(), NP)); HIPCHK(ctx, d_open.alloc(NP)); HIPCHK(ctx, d_span.alloc(NP * 4)); HIPCHK(ctx, d_blen.alloc(G));
+    if (NP) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)d_open.p, prm->aln_open, NP, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> used(G, 0);
     ht.mark("orient + pairs");
@@ -992,7 +1005,7 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
                 int32_t* A = trace->aln + (size_t)it * NL * 6;
                 if (it == 0) for (uint64_t x = 0; x < NL * 6; ++x) A[x] = -1; else memcpy(A, A - NL * 6, sizeof(int32_t) * NL * 6);
                 for (uint64_t p = 0; p < NP; ++p) {
-                    int32_t* a = A + pair_pos[p] * 6; const uint32_t r = pair_read[p]; const int32_t ql = (int32_t)(RD.h_off[r + 1] - RD.h_off[r]);
+                    int32_t* a = A + (size_t)pair_pos[p] * 6; const uint32_t r = pair_read[p]; const int32_t ql = (int32_t)(RD.h_off[r + 1] - RD.h_off[r]);
                     const int32_t qf = h_span[p * 4], qe = h_span[p * 4 + 1], tf = h_span[p * 4 + 2], te = h_span[p * 4 + 3];
                     if (qf < 0) { for (int c = 0; c < 6; ++c) a[c] = -1; continue; }
                     const bool rcs = h_orient[r] == 1;
@@ -1076,8 +1089,7 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
             PSeq S; S.s = BB.seq + boff[g] + ws; S.q = nullptr; S.len = wlen; S.uw = 0; S.cw = 0; S.mode = NGSID_POA_GLOBAL; S.a0 = 0; S.a1 = -1;
             units[u].bb = (int)bbs.size(); bbs.push_back(S); bb_len.push_back(wlen);
         }
-        DevBuf<PSeq> d_bbs; HIPCHK(ctx, d_bbs.alloc(bbs.size()));
-        if (!bbs.empty()) HIPCHK(ctx, hipMemcpyAsync(d_bbs.p, bbs.data(), sizeof(PSeq) * bbs.size(), hipMemcpyHostToDevice, ctx->stream));
+        DevBuf<PSeq> d_bbs; NGSID_TRY(dev_put(ctx, d_bbs, bbs.data(), bbs.size()));
         bool any_tgs = prm->trim == 2; for (uint32_t g = 0; g < G; ++g) any_tgs = any_tgs || (tgs[g] && prm->trim);
         HierParams hp{prm->match, prm->mismatch, prm->gap, prm->band > 0 ? prm->band : (RD.maxlen <= NGSID_POA_BAND64_MAXLEN ? 64 : 128), prm->node_cap, prm->tile_depth, NGSID_POA_GLOBAL, any_tgs, (prm->trim >= 2 ? 1 : 0) | (prm->trim == 3 ? 4 : 0)};      // trim_tiles: 1 = trim tile consensuses, 4 = except the tile that ends a unit (trim 3)
         hp.single_below = prm->single_below > 0 ? prm->single_below : 0;
