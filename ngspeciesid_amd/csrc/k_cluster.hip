@@ -303,12 +303,15 @@ struct PosBatch { uint32_t pos[64]; };
 // workgroup t sorts + uniques the codes of read t (bitonic in LDS) and appends them to the pool behind workgroup t-1: the offsets are chained
 // through `chain` (zero before the launch; all <= 64 workgroups are resident, so waiting on the predecessor cannot deadlock).
 // Also registers the slot: rep_read[slot0 + t] = read t, pool_off[slot0 + t + 1] = pool_off[slot0 + t] + #unique
+// A read with more than REP_SORT_LDS_MAX minimizers (a long read at w = k: every k-mer is one) does not fit the LDS of a CU: the batch that holds one sorts in global
+// memory instead - gsort, gstride codes per workgroup, the same passes (each workgroup only touches its own stretch, __syncthreads orders its accesses).
+constexpr uint32_t REP_SORT_LDS_MAX = 16384;      // codes: 128 KiB of the 160 KiB of a CU
 __global__ __launch_bounds__(256)
 void k_rep_build_batch(const uint64_t* __restrict__ mzcode, RepBatch B, uint64_t* __restrict__ pool, uint64_t* __restrict__ pool_off,
-                       uint32_t* __restrict__ rep_read, uint32_t slot0, uint32_t* __restrict__ chain)
+                       uint32_t* __restrict__ rep_read, uint32_t slot0, uint32_t* __restrict__ chain, uint64_t* gsort, uint32_t gstride)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t* a = (uint64_t*)smem;
+    uint64_t* a = gsort ? gsort + (size_t)blockIdx.x * gstride : (uint64_t*)smem;
     __shared__ uint32_t s_u; __shared__ uint64_t s_off;
     const uint32_t t = blockIdx.x, M = B.M[t]; const uint64_t base = B.base[t];
     uint32_t P2 = 2; while (P2 < M) P2 <<= 1;
@@ -495,6 +498,7 @@ struct RepStore {
     DevBuf<uint32_t> rep_read; DevBuf<uint64_t> pool, pool_off; std::vector<uint64_t> h_pool_off;
     DevBuf<uint64_t> dbc[2]; DevBuf<uint32_t> dbs[2]; int cur = 0; uint64_t n_db = 0;
     DevBuf<uint32_t> d_count;
+    DevBuf<uint64_t> sortbuf;      // build_reps: sort space of a batch with a representative too large for the LDS
 };
 
 // Builds the representatives of `reads` in the slots S.R, S.R+1, ... (pool offsets chained on the device) without registering them on the host:
@@ -514,10 +518,15 @@ static int32_t build_reps(ngsid_ctx* ctx, RepStore& S, const uint32_t* reads, ui
         RepBatch B; uint32_t maxM = 2;
         for (uint32_t t = 0; t < nb; ++t) { B.read[t] = reads[t0 + t]; B.M[t] = h_mzcnt[reads[t0 + t]]; B.base[t] = h_off[reads[t0 + t]]; maxM = std::max(maxM, B.M[t]); }
         uint32_t P2 = 2; while (P2 < maxM) P2 <<= 1;
-        const size_t lds = (size_t)P2 * 8;
+        const bool in_lds = P2 <= REP_SORT_LDS_MAX;
+        const size_t lds = in_lds ? (size_t)P2 * 8 : 0;
         if (lds > 48 * 1024) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_rep_build_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (!in_lds && S.sortbuf.n < (size_t)nb * P2) {      // (an earlier launch may still sort in the buffer this replaces)
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, S.sortbuf.alloc((size_t)nb * P2));
+        }
         HIPCHK(ctx, hipMemsetAsync(S.d_count.p, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(k_rep_build_batch, dim3(nb), dim3(256), lds, ctx->stream, d_mzcode, B, S.pool.p, S.pool_off.p, S.rep_read.p, S.R + t0, S.d_count.p);
+        hipLaunchKernelGGL(k_rep_build_batch, dim3(nb), dim3(256), lds, ctx->stream, d_mzcode, B, S.pool.p, S.pool_off.p, S.rep_read.p, S.R + t0, S.d_count.p,
+                           in_lds ? (uint64_t*)nullptr : S.sortbuf.p, P2);
         HIPCHK(ctx, hipGetLastError());
     }
     return NGSID_OK;
