@@ -68,6 +68,7 @@ CHIMERA_FIELDS = ("one_pair", "one_cost", "two_cost", "pair_a", "pair_b", "bp_lo
 CHIMERA_NFIELD, CHIMERA_ROWS, CHIMERA_LDS_QUERY = 7, 12, 2048                      # NGSID_CHIMERA_NFIELD, _ROWS (R of k_chimera_profile), _LDS_QUERY
 CHIMERA_STRIP = 64 * CHIMERA_ROWS                                                   # NGSID_CHIMERA_STRIP: parent rows per pass of a wave
 MAX_CONSENSUS_LEN = 16384                                                           # include/ngsid.h NGSID_MAX_CONSENSUS_LEN
+NEAR_MAX_DIST, NEAR_BOTH_STRANDS = 31, 1                                            # include/ngsid_near.h NGSID_NEAR_MAX_DIST, NGSID_NEAR_BOTH_STRANDS
 
 
 def chimera_profile_offsets(query_lens, pair_off):
@@ -765,6 +766,43 @@ class Api:
         rc = self._call("chimera_model", C.byref(qs.c), C.byref(ps.c), _p(po), _p(pp if len(pp) else np.zeros(1, np.uint32)), _p(pg if pg is None or len(pg) else np.zeros(1, np.int32)), _p(fields if qs.n else np.zeros(CHIMERA_NFIELD, np.int32)), _p(prof))
         if rc: self._err(rc)
         return (fields, prof[:int(prof_off[-1])], prof_off) if profiles else fields
+
+    # ---- include/ngsid_near.h
+    def ed_within(self, queries, targets, q_idx, t_idx, max_dist, both_strands=True):
+        """ngsid_ed_within_batch: for the listed pairs the unit-cost edit distance of queries[q_idx[p]] and targets[t_idx[p]], over both strands with both_strands
+        (the smaller one; a tie goes to forward) -> (dist int32 [n], strand uint8 [n]): dist = -1 and strand = 0 where the distance exceeds max_dist (0 .. NEAR_MAX_DIST).
+        queries / targets: lists of strings or read sets.  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_near.h", "ed_within_batch", "near_pairs")
+        qs, ts = _as_reads(queries), _as_reads(targets)
+        qi = np.ascontiguousarray(q_idx, dtype=np.uint32); ti = np.ascontiguousarray(t_idx, dtype=np.uint32)
+        if len(qi) != len(ti): raise ValueError("ed_within: q_idx and t_idx hold one entry per pair")
+        n = len(qi)
+        dist = np.full(max(n, 1), -1, dtype=np.int32); strand = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = self._call("ed_within_batch", C.byref(qs.c), C.byref(ts.c), _p(qi if n else np.zeros(1, np.uint32)), _p(ti if n else np.zeros(1, np.uint32)), C.c_uint64(n),
+                        C.c_int32(int(max_dist)), C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0), _p(dist), _p(strand))
+        if rc: self._err(rc)
+        return dist[:n], strand[:n]
+
+    def near_pairs(self, seqs, max_dist, both_strands=True, cap=None):
+        """ngsid_near_pairs: every pair i < j of seqs within max_dist edits (0 .. NEAR_MAX_DIST; both strands with both_strands) -> (pair_i uint32, pair_j uint32,
+        dist uint8, strand uint8), in ascending (i, j) order.  The count call (cap = 0), then the fill call; cap: one call with room for that many pairs
+        (NgsidError NGSID_ERR_CAPACITY with .needed when there are more).  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_near.h", "ed_within_batch", "near_pairs")
+        rs = _as_reads(seqs)
+        flags = C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0)
+        found, needed = C.c_uint64(0), C.c_uint64(0)
+        if cap is None:
+            rc = self._call("near_pairs", C.byref(rs.c), C.c_int32(int(max_dist)), flags, None, None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
+            if rc and rc != -4: self._err(rc)
+            cap = int(needed.value)
+        pi = np.zeros(max(cap, 1), dtype=np.uint32); pj = np.zeros(max(cap, 1), dtype=np.uint32); dist = np.zeros(max(cap, 1), dtype=np.uint8); strand = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = self._call("near_pairs", C.byref(rs.c), C.c_int32(int(max_dist)), flags, _p(pi), _p(pj), _p(dist), _p(strand), C.c_uint64(cap), C.byref(found), C.byref(needed))
+        if rc:
+            try: self._err(rc)
+            except NgsidError as e:
+                e.needed = int(needed.value); raise
+        n = int(found.value)
+        return pi[:n], pj[:n], dist[:n], strand[:n]
 
 
 class RefDb:

@@ -48,7 +48,7 @@ DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are h
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
-                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample",
+                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample; `variants --fasta A B ... --outfolder O` (first argument `variants`) writes the files of --variants with every FASTA taken as one sample",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--version', action='version', version='%(prog)s 0.3.1-mi355x')
     p.add_argument('--debug', action='store_true')
@@ -97,6 +97,9 @@ def build_parser():
     from . import chimera as _chimera
     p.add_argument('--chimeras', action='store_true', help='extension: flag PCR chimeras among the final consensuses. Every consensus is modelled on the GPU as the head of one and the tail of another more abundant consensus of the same sample (both strands, unit-cost edit distance, every breakpoint); writes <outfolder>/chimeras.tsv (id n_reads length chimeric best_parent best_strand best_ed parent_a strand_a parent_b strand_b model_ed gain bp_lo bp_hi; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/chimeras_all.tsv). No other output changes. Needs --consensus')
     _chimera.add_flags(p)
+    from . import variants as _variants
+    p.add_argument('--variants', action='store_true', help='extension: the study-wide variant table of a multi-sample run. The final consensuses of all samples are compared with each other on the GPU (banded unit-cost edit distance, both strands) and joined by abundance into variants; writes <outfolder>/variants.fasta (the centroid sequences, variant_{v};size={reads};samples={n}), variant_table.tsv (variants x samples, read counts) and variant_members.tsv (sample, consensus id, reads, variant, dist, strand). No other output changes. Needs --consensus and --fastq_dir or --demux_sheet')
+    _variants.add_flags(p)
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -138,6 +141,23 @@ def _chimeras_subparser(cf):
     return cf
 
 
+def _variants_subparser(cf):
+    """the `variants` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import variants as _variants
+    cf.add_argument('--fasta', type=str, nargs='+', required=True, help='one FASTA per sample (the sample is named by the file name without its extension); read counts are taken from names of this tool\'s consensuses (..._total_supporting_reads_N), else 1')
+    cf.add_argument('--outfolder', type=str, required=True, help='where variants.fasta, variant_table.tsv and variant_members.tsv go')
+    _variants.add_flags(cf)
+    cf.set_defaults(which='variants')
+    return cf
+
+
+def _check_variants(args):
+    from . import variants as _variants
+    err = _variants.check_args(args)
+    if err:
+        logging.error(err); sys.exit(1)
+
+
 def _check_chimeras(args):
     from . import chimera as _chimera
     err = _chimera.check_args(args)
@@ -160,6 +180,8 @@ def cli(argv=None):
         args = _classify_subparser(argparse.ArgumentParser(prog='classify', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'chimeras':
         args = _chimeras_subparser(argparse.ArgumentParser(prog='chimeras', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'variants':
+        args = _variants_subparser(argparse.ArgumentParser(prog='variants', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
         args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if getattr(args, 'debug', False) else logging.INFO, format='%(message)s')
@@ -180,6 +202,15 @@ def cli(argv=None):
         from . import chimera as _chimera
         rows = _chimera.chimeras_fasta(args)
         logging.info("Wrote %d rows to %s." % (len(rows), args.outfile))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'variants':
+        _check_variants(args)
+        for f in args.fasta:
+            if not os.path.isfile(f):
+                logging.error("--fasta %s is not a file." % f); sys.exit(1)
+        from . import variants as _variants
+        tab = _variants.variants_fasta(args)
+        logging.info("Wrote %d variants of %d sequences to %s." % (len(tab["variants"]), len(tab["members"]), args.outfolder))
         sys.exit(0)
     if args.ont and args.isoseq:
         logging.error("Arguments mutually exclusive, specify either --isoseq or --ont. "); sys.exit()
@@ -222,6 +253,12 @@ def cli(argv=None):
         if not args.consensus:
             logging.error("--chimeras models consensus sequences: it needs --consensus."); sys.exit(1)
         _check_chimeras(args)
+    if getattr(args, "variants", False):
+        if not args.consensus:
+            logging.error("--variants joins consensus sequences: it needs --consensus."); sys.exit(1)
+        if not (getattr(args, "fastq_dir", None) or getattr(args, "demux_sheet", None)):
+            logging.error("--variants joins the consensuses of several samples: it needs --fastq_dir or --demux_sheet."); sys.exit(1)
+        _check_variants(args)
     if args.medaka:
         logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
     if args.k > 32 or args.k < 1:

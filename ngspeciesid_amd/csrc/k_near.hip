@@ -1,0 +1,306 @@
+// k_near.hip - ngsid_ed_within_batch / ngsid_near_pairs (include/ngsid_near.h): the unit-cost edit distance of pairs that are at most 31 edits apart, on both strands,
+// for listed pairs and for all pairs of a set.
+//
+// One pair per lane, one band word per lane: the diagonal-band form of Myers' bit-vector recurrence (Hyyro 2003).  In column c (1-based) of the DP matrix of a pattern
+// (rows) against a text (columns), bit r of a 64-bit word is row c - 31 + r, so a diagonal keeps its bit from column to column and the cell (m, n) sits at bit
+// 31 - (n - m).  VP / VN hold the vertical deltas of the column before, already aligned to the rows of the column that is computed: the band slides one row per column
+// by the one shift D0 >> 1.  Row c + 32 was outside the band one column earlier; its delta is taken as +1 (bit 63 of VP), which can only raise a value.  Rows <= 0 are
+// virtual rows that match nothing and hold D[i][c] = c (VP = VN = 0 there), rows behind the pattern's end match nothing.  Every band value is the cost of a real
+// alignment, so it is >= the full DP's, and equal to it where that is <= 31: a path of cost <= 31 stays within 31 diagonals of the main one.
+// The value on the diagonal of (m, n) is tracked from column 0 on (start max(m - n, 0), + 1 wherever D0 has a zero there).  Values never decrease along a diagonal, so
+// a lane leaves the loop as soon as the tracked value exceeds its bound: pairs with |n - m| above it never enter, unrelated pairs leave after a few dozen columns, a wave
+// stops when its last lane has.  The reverse strand runs after the forward one with the bound forward - 1 (a tie goes to forward), not at all behind a forward 0.
+//
+// No LDS and no traceback.  k_near_pack turns every sequence into three bit planes of its letters' codes (A C G T N = 0 .. 4, 7 outside the sequence: equals nothing),
+// in three variants: PATTERN (base p at bit p + 31: the window of column c + 1 starts at bit c), TEXT (base p at bit p) and TEXT_RC (the complement of base
+// len - 1 - p at bit p: rc(b) is never materialised).  A lane loads three pattern words and three text words per 32 columns; per column the three 64-bit pattern windows
+// are funnel shifts of register pairs, the text letter is three 0 / -1 masks, and Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2)): N by the planes, not by a branch.
+// tests/variants_band_model.py runs the same loop on Python ints, word for word.
+//
+// k_near_within: lane = listed pair (pattern = query, text = target).
+// k_near_tiles: the set sorted by length on the host; wave = tile = sequence x (sorted position) against 64 of the sequences behind it; the tiles of x end at hi[x],
+//   the last sequence at most max_dist bases longer: the length bound removes whole tiles, and the lanes of a wave see lengths within max_dist of each other.  The text is
+//   x, the shorter one, the same for every lane: its words and masks are wave-uniform, and every lane has the same number of columns.  A lane that finds a pair appends
+//   (min, max of the caller's indices | distance, strand) through one counter; the host sorts what came back.
+#include "ngsid_host.h"
+#include "../../include/ngsid_near.h"
+#include <numeric>
+
+typedef uint64_t u64;
+
+static_assert(NGSID_NEAR_MAX_DIST == 31, "the band of near_band_ed is rows c - 31 .. c + 32");
+
+namespace {
+
+#define NEAR_PATTERN 0
+#define NEAR_TEXT 1
+#define NEAR_TEXT_RC 2
+
+// words per plane of a sequence of len bases: its bits, the 31 leading pad bits of the pattern variant, and the two words a window reads ahead
+__host__ __device__ __forceinline__ int near_nw(int len) { return ((len + 31) >> 5) + 3; }
+
+__device__ __forceinline__ int near_code(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
+
+// planes of sequence s: woff[s] * 9 words in, variant v plane k at ((v * 3 + k) * nw)
+__global__ __launch_bounds__(64)
+void k_near_pack(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, u64 s0, uint32_t* __restrict__ planes)
+{
+    const u64 s = s0 + blockIdx.x;
+    const u64 a = off[s];
+    const int L = (int)(off[s + 1] - a), nw = near_nw(L);
+    uint32_t* base = planes + woff[s] * 9;
+    for (int w = threadIdx.x; w < nw; w += 64) {
+        for (int v = 0; v < 3; ++v) {
+            uint32_t b0 = 0, b1 = 0, b2 = 0;
+            for (int t = 0; t < 32; ++t) {
+                const int u = 32 * w + t, p = v == NEAR_PATTERN ? u - 31 : u;
+                int c = 7;
+                if (p >= 0 && p < L) {
+                    c = near_code(seq[a + (v == NEAR_TEXT_RC ? L - 1 - p : p)]);
+                    if (v == NEAR_TEXT_RC && c < 4) c = 3 - c;
+                }
+                b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
+            }
+            base[(size_t)(v * 3 + 0) * nw + w] = b0; base[(size_t)(v * 3 + 1) * nw + w] = b1; base[(size_t)(v * 3 + 2) * nw + w] = b2;
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t near_funnel(uint32_t hi, uint32_t lo, int s) { return (uint32_t)((((u64)hi << 32) | lo) >> s); }      // s = 0 .. 31 (one v_lshrrev_b64 of the register pair)
+
+// pat: the PATTERN variant of a sequence of m bases (plane k at pat + k * nwp), txt: a TEXT or TEXT_RC variant of one of n bases -> their edit distance if it is <= K, else -1.
+// Reads pattern words up to ((n - 1) >> 5) + 2 < near_nw(m) (n <= m + 31 behind the length test) and text words up to (n - 1) >> 5 < near_nw(n).
+__device__ __forceinline__ int near_band_ed(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt, int nwt, int m, int n, int K)
+{
+    const int d = n - m;
+    int val = d < 0 ? -d : 0;
+    if (val > K || d > K) return -1;
+    const int sb = 31 - d;
+    u64 VP = ~0ull << 31, VN = 0;
+    for (int c0 = 0; c0 < n; c0 += 32) {
+        const int w = c0 >> 5;
+        const uint32_t a0 = pat[w], a1 = pat[w + 1], a2 = pat[w + 2];
+        const uint32_t b0 = pat[nwp + w], b1 = pat[nwp + w + 1], b2 = pat[nwp + w + 2];
+        const uint32_t c_0 = pat[2 * nwp + w], c_1 = pat[2 * nwp + w + 1], c_2 = pat[2 * nwp + w + 2];
+        const uint32_t t0 = txt[w], t1 = txt[nwt + w], t2 = txt[2 * nwt + w];
+        const int ce = min(32, n - c0);
+        for (int s = 0; s < ce; ++s) {
+            const u64 W0 = ((u64)near_funnel(a2, a1, s) << 32) | near_funnel(a1, a0, s);
+            const u64 W1 = ((u64)near_funnel(b2, b1, s) << 32) | near_funnel(b1, b0, s);
+            const u64 W2 = ((u64)near_funnel(c_2, c_1, s) << 32) | near_funnel(c_1, c_0, s);
+            const u64 T0 = (u64)0 - ((t0 >> s) & 1u), T1 = (u64)0 - ((t1 >> s) & 1u), T2 = (u64)0 - ((t2 >> s) & 1u);
+            const u64 Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2));
+            const u64 D0 = (((Eq & VP) + VP) ^ VP) | Eq | VN;
+            const u64 HP = VN | ~(D0 | VP);
+            const u64 HN = D0 & VP;
+            const u64 D0s = D0 >> 1;
+            VP = HN | ~(D0s | HP) | (1ull << 63);
+            VN = D0s & HP;
+            val += 1 - (int)((D0 >> sb) & 1u);
+            if (val > K) return -1;
+        }
+    }
+    return val;
+}
+
+// forward, then the reverse strand below the forward result -> the distance or -1; *strand = 1 iff the reverse strand is strictly closer
+__device__ __forceinline__ int near_both(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt3, int nwt, int m, int n, int K, bool both, int* strand)
+{
+    int best = near_band_ed(pat, nwp, txt3 + (size_t)(NEAR_TEXT * 3) * nwt, nwt, m, n, K);
+    *strand = 0;
+    if (both && best != 0) {
+        const int r = near_band_ed(pat, nwp, txt3 + (size_t)(NEAR_TEXT_RC * 3) * nwt, nwt, m, n, best < 0 ? K : best - 1);
+        if (r >= 0) { best = r; *strand = 1; }
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(256)
+void k_near_within(const uint64_t* __restrict__ qoff, const uint64_t* __restrict__ qwoff, const uint32_t* __restrict__ qpl, const uint64_t* __restrict__ toff, const uint64_t* __restrict__ twoff,
+                   const uint32_t* __restrict__ tpl, const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ tidx, u64 p0, u64 p1, int K, int both,
+                   int32_t* __restrict__ dist, uint8_t* __restrict__ strand)
+{
+    const u64 p = p0 + (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= p1) return;
+    const uint32_t q = qidx[p], t = tidx[p];
+    const int m = (int)(qoff[q + 1] - qoff[q]), n = (int)(toff[t + 1] - toff[t]);
+    const int nwp = near_nw(m), nwt = near_nw(n);
+    int st = 0;
+    const int best = near_both(qpl + qwoff[q] * 9, nwp, tpl + twoff[t] * 9, nwt, m, n, K, both != 0, &st);
+    dist[p] = best;
+    strand[p] = (uint8_t)st;
+}
+
+// rows x = xa .. xa + nrows - 1 (sorted positions); tile T of the launch belongs to the row r with toff[r] <= T < toff[r + 1] and covers y = x + 1 + 64 (T - toff[r]) + lane
+__global__ __launch_bounds__(256)
+void k_near_tiles(const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, const uint32_t* __restrict__ pl, const uint32_t* __restrict__ order, const uint32_t* __restrict__ hi,
+                  const uint64_t* __restrict__ toff, uint32_t xa, uint32_t nrows, u64 ntiles, int K, int both,
+                  u64* __restrict__ key, uint8_t* __restrict__ ds, u64 limit, unsigned long long* counter)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 Tl = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const u64 T = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(Tl >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)Tl);
+    if (T >= ntiles) return;
+    uint32_t lo = 0, up = nrows;                                   // the last r with toff[r] <= T
+    while (up - lo > 1) { const uint32_t mid = lo + (up - lo) / 2; if (toff[mid] <= T) lo = mid; else up = mid; }
+    const uint32_t x = xa + lo;
+    const u64 y64 = (u64)x + 1 + (T - toff[lo]) * 64 + lane;
+    if (y64 > hi[x]) return;
+    const uint32_t y = (uint32_t)y64, ox = order[x], oy = order[y];
+    const int n = (int)(off[ox + 1] - off[ox]), m = (int)(off[oy + 1] - off[oy]);
+    int st = 0;
+    const int best = near_both(pl + woff[oy] * 9, near_nw(m), pl + woff[ox] * 9, near_nw(n), m, n, K, both != 0, &st);
+    if (best < 0) return;
+    const unsigned long long slot = atomicAdd(counter, 1ull);
+    if (slot < limit) {
+        key[slot] = ((u64)min(ox, oy) << 32) | max(ox, oy);
+        ds[slot] = (uint8_t)(best | (st << 7));
+    }
+}
+
+// the planes of every sequence of R in `buf` (grow-only), the word offsets on the device
+int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
+{
+    PinVec<uint64_t> woff(R.n + 1);
+    woff[0] = 0;
+    for (uint64_t s = 0; s < R.n; ++s) woff[s + 1] = woff[s] + (uint64_t)near_nw((int)(R.h_off[s + 1] - R.h_off[s]));
+    HIPCHK(ctx, buf.reserve(woff[R.n] * 9));
+    NGSID_TRY(dev_put(ctx, d_woff, woff.data(), R.n + 1));
+    ProfScope ps_(ctx, "k_near_pack");
+    for (uint64_t s0 = 0; s0 < R.n; s0 += 1u << 30) {
+        hipLaunchKernelGGL(k_near_pack, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, buf.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // (woff is a host vector of this scope)
+    return NGSID_OK;
+}
+
+// the checks both entry points share: max_dist, the length bound, the alphabet
+int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, const DevReads* A, const DevReads* B)
+{
+    if (max_dist < 0 || max_dist > NGSID_NEAR_MAX_DIST) NGSID_FAIL(ctx, NGSID_ERR_ARG, "max_dist %d outside 0 .. NGSID_NEAR_MAX_DIST=%d", max_dist, NGSID_NEAR_MAX_DIST);
+    const uint32_t maxlen = std::max(A->maxlen, B ? B->maxlen : 0u);
+    if (maxlen > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a sequence of %u bases exceeds NGSID_MAX_CONSENSUS_LEN=%d", maxlen, NGSID_MAX_CONSENSUS_LEN);
+    if (A->n >= 0x100000000ull || (B && B->n >= 0x100000000ull)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "a set is limited to 2^32 - 1 sequences");
+    DevBuf<uint32_t> bad; HIPCHK(ctx, bad.alloc(1));
+    HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), ctx->stream));
+    NGSID_TRY(ngsid_alphabet_scan(ctx, *A, bad.p, "k_near_check")); if (B) NGSID_TRY(ngsid_alphabet_scan(ctx, *B, bad.p, "k_near_check"));
+    uint32_t h_bad = 0;
+    NGSID_TRY(dev_get(ctx, &h_bad, bad.p, 1));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a sequence holds a base outside upper-case ACGTN");
+    return NGSID_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t ngsid_ed_within_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
+                                         int32_t max_dist, uint32_t flags, int32_t* dist, uint8_t* strand)
+{
+    ApiClock api_clock_(ctx, "ed_within_batch");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (n_pairs && !dist) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null output");
+    PairBatch B;
+    NGSID_TRY(ngsid_pair_batch(ctx, queries, targets, q_idx, t_idx, n_pairs, B));
+    NGSID_TRY(near_check(ctx, max_dist, &B.Q, &B.T));
+    if (n_pairs == 0) return NGSID_OK;
+    DevBuf<uint64_t> d_qw, d_tw; DevBuf<int32_t> d_dist; DevBuf<uint8_t> d_strand;
+    NGSID_TRY(near_pack(ctx, B.Q, ctx->near_pl[0], d_qw)); NGSID_TRY(near_pack(ctx, B.T, ctx->near_pl[1], d_tw));
+    HIPCHK(ctx, d_dist.alloc(n_pairs)); HIPCHK(ctx, d_strand.alloc(n_pairs));
+    const long long opt = ngsid_opt(ctx, "near_chunk_pairs", 0);
+    const uint64_t chunk = opt > 0 ? (uint64_t)opt : (uint64_t)1 << 30;
+    for (uint64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
+        const uint64_t p1 = std::min(n_pairs, p0 + chunk);
+        ProfScope ps_(ctx, "k_near_within");
+        hipLaunchKernelGGL(k_near_within, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_pl[0].p, B.T.off, d_tw.p, ctx->near_pl[1].p,
+                           B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), d_dist.p, d_strand.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    NGSID_TRY(dev_get(ctx, dist, d_dist.p, n_pairs));
+    if (strand) NGSID_TRY(dev_get(ctx, strand, d_strand.p, n_pairs));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return NGSID_OK;
+}
+
+extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
+                                    uint64_t cap, uint64_t* n_found, uint64_t* needed)
+{
+    ApiClock api_clock_(ctx, "near_pairs");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (!seqs || !n_found || !needed || (cap && (!pair_i || !pair_j || !dist || !strand))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
+    *n_found = 0; *needed = 0;
+    DevReads R;
+    NGSID_TRY(ngsid_upload_reads(ctx, seqs, &R, false));
+    NGSID_TRY(near_check(ctx, max_dist, &R, nullptr));
+    const uint64_t N = R.n;
+    if (N < 2) return NGSID_OK;
+    // ---- sorted by (length, index); hi[x] = the last sorted position whose sequence is at most max_dist bases longer than x's; 64 candidates per tile
+    auto len = [&](uint32_t s) { return (uint32_t)(R.h_off[(size_t)s + 1] - R.h_off[s]); };
+    PinVec<uint32_t> order(N), hi(N);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return len(a) < len(b); });
+    std::vector<uint64_t> tiles(N + 1, 0);
+    for (uint64_t x = 0, y = 0; x < N; ++x) {
+        if (y < x) y = x;
+        while (y + 1 < N && len(order[y + 1]) - len(order[x]) <= (uint32_t)max_dist) ++y;
+        hi[x] = (uint32_t)y;
+        tiles[x + 1] = tiles[x] + (y - x + 63) / 64;
+    }
+    DevBuf<uint64_t> d_woff, d_toff; DevBuf<uint32_t> d_order, d_hi; DevBuf<unsigned long long> d_ctr;
+    NGSID_TRY(near_pack(ctx, R, ctx->near_pl[0], d_woff));
+    NGSID_TRY(dev_put(ctx, d_order, order.data(), N)); NGSID_TRY(dev_put(ctx, d_hi, hi.data(), N));
+    HIPCHK(ctx, d_ctr.alloc(1));
+    // ---- the found buffer: cap entries, or what a share of the free device memory holds; rows in chunks
+    const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / 9);
+    if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F)); }
+    const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0);
+    const uint64_t max_tiles = (uint64_t)1 << 30;                     // per launch: four tiles per workgroup
+    bool fill = cap > 0;
+    std::vector<uint64_t> keys; std::vector<uint8_t> dss;
+    uint64_t total = 0, rows_now = opt > 0 ? (uint64_t)opt : N;
+    PinVec<uint64_t> h_toff;
+    for (uint64_t xa = 0; xa < N; ) {
+        uint64_t xb = std::min(N, xa + rows_now);
+        while (xb - xa > 1 && tiles[xb] - tiles[xa] > max_tiles) xb = xa + (xb - xa) / 2;
+        const uint64_t nt = tiles[xb] - tiles[xa];
+        if (nt == 0) { xa = xb; continue; }
+        if (nt > 4 * max_tiles) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
+        h_toff.resize(xb - xa + 1);
+        for (uint64_t r = 0; r <= xb - xa; ++r) h_toff[r] = tiles[xa + r] - tiles[xa];
+        NGSID_TRY(dev_put(ctx, d_toff, h_toff.data(), xb - xa + 1));
+        HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long), ctx->stream));
+        const uint64_t limit = fill ? std::min(F, cap - total) : 0;
+        { ProfScope ps_(ctx, "k_near_tiles");
+          hipLaunchKernelGGL(k_near_tiles, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
+                             (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, ctx->near_ds.p, (u64)limit, d_ctr.p); }
+        HIPCHK(ctx, hipGetLastError());
+        unsigned long long c = 0;
+        NGSID_TRY(dev_get(ctx, &c, d_ctr.p, 1));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (fill && c > limit) {
+            if (limit == cap - total) fill = false;                   // more pairs than the caller has room for: count on
+            else if (xb - xa > 1) { rows_now = (xb - xa) / 2; continue; }      // more than the found buffer holds: the same rows in smaller chunks
+            else NGSID_FAIL(ctx, NGSID_ERR_HIP, "one sequence has %llu near neighbours: beyond the found buffer the free device memory allows", c);
+        }
+        if (fill && c) {
+            const size_t at = keys.size();
+            keys.resize(at + c); dss.resize(at + c);
+            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, ctx->near_ds.p, (size_t)c));
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        total += c;
+        xa = xb;
+    }
+    *needed = total;
+    if (total > cap) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "%llu near pairs, room for %llu", (unsigned long long)total, (unsigned long long)cap);
+    // ---- ascending (i, j): the keys are distinct
+    std::vector<uint64_t> perm(total);
+    std::iota(perm.begin(), perm.end(), (uint64_t)0);
+    std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return keys[a] < keys[b]; });
+    for (uint64_t k = 0; k < total; ++k) {
+        const uint64_t key = keys[perm[k]]; const uint8_t v = dss[perm[k]];
+        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = v & 0x7f; strand[k] = v >> 7;
+    }
+    *n_found = total;
+    return NGSID_OK;
+}

@@ -750,6 +750,16 @@ def _chimera_step(args, api, groups, T):
     T["chimeras"] = time() - t0
 
 
+def _variant_step(args, api, groups, T):
+    """--variants: the final consensuses of every (sample, folder, centres) group of a multi-sample run compared with each other in one library call and joined into
+    study-wide variants (variants.run) -> <outfolder>/variants.fasta, variant_table.tsv, variant_members.tsv"""
+    from . import variants
+    t0 = time()
+    named = [(sample, folder, [("consensus_cl_id_{0}_total_supporting_reads_{1}".format(c_id, nr), nr, seq) for nr, c_id, seq, _ in centers]) for sample, folder, centers in groups]
+    variants.run(args, api, named)
+    T["variants"] = time() - t0
+
+
 def sample_files(folder):
     """the samples of --fastq_dir: every *.fastq / *.fq directly under the folder, in sorted name order -> [(sample name = file name without extension, path)]"""
     out = []
@@ -802,6 +812,8 @@ def _main_samples(args, api):
         _classify_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
     if getattr(args, "chimeras", False) and args.consensus:
         _chimera_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
+    if getattr(args, "variants", False) and args.consensus:
+        _variant_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 

@@ -308,14 +308,18 @@ def _bands_alone(rs, so, band):
 def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                         strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None):
+                         strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None,
+                         variants=False, variant_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
     are grouped by the band they would get alone (a sample with a read above POA_BAND64_MAXLEN bases gets 128 columns, the others 64), so at most two consensus
     and two polishing calls.  support=True: the support key of run_hot_path per sample, from one consensus_support call for all samples.  classify=RefDb: the classify
     key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  chimeras=True: the chimeras
-    key of run_hot_path per sample, ALL samples in one model call (parents within a sample only).  strand_aware is not supported here (ValueError)."""
+    key of run_hot_path per sample, ALL samples in one model call (parents within a sample only).  variants=True (extension; variants.py, include/ngsid_near.h):
+    also variants = dict(members = one dict(variant, dist, strand) per centre of the sample, table = the study-wide table of variants.build, the same object in every
+    sample's dict): the final sequences of ALL samples in one near-pairs call, clustered by abundance (variant_kwargs: identity, max_dist, both_strands); every other key
+    is what variants=False returns.  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     T = timings if timings is not None else {}
@@ -329,6 +333,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
         for o in out: o["classify"] = []                                        # what stays for a sample without a centre
     if chimeras:
         for o in out: o["chimeras"] = []
+    if variants:
+        for o in out: o["variants"] = None
     if not do_consensus:
         return out
     t0 = time.perf_counter()
@@ -336,4 +342,14 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
                       do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs)
+    if variants:
+        from . import variants as variants_mod
+        t0 = time.perf_counter()
+        tab = variants_mod.build(api, variants_mod.collect([(s, None, [(c[1], c[0], c[3]) for c in o["centers"]]) for s, o in enumerate(out)]), **(variant_kwargs or {}))
+        at = 0
+        for o in out:
+            n = len(o["centers"])
+            o["variants"] = dict(members=[dict(variant=int(tab["variant_of"][x]), dist=int(tab["dist"][x]), strand=int(tab["strand"][x])) for x in range(at, at + n)], table=tab)
+            at += n
+        T["variants"] = T.get("variants", 0.0) + time.perf_counter() - t0
     return out
