@@ -13,6 +13,7 @@ extern "C" {
 #endif
 
 #define NGSID_NEAR_MAX_DIST 31          /* largest max_dist: the band of k_near is one 64-bit word per lane, rows c - 31 .. c + 32 of column c */
+#define NGSID_NEAR_WIDE_MAX_DIST 255 /* largest max_dist of the wide calls: up to eight band words per lane, a band of W words holds 32 W - 1 edits */
 #define NGSID_NEAR_BOTH_STRANDS 1u      /* flags: also compare against the reverse complement */
 
 /* Definition.  Sequences are upper-case ACGTN; two letters are equal iff the bytes are equal (N equals only N).  ed = unit-cost global edit distance (both sequences
@@ -42,6 +43,16 @@ int32_t ngsid_ed_within_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, cons
  * difference of max_dist do not exist); only the found pairs come back. */
 int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags,
                          uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand /* [cap] each */, uint64_t cap, uint64_t* n_found, uint64_t* needed);
+
+/* The wide calls: the two calls above, word for word - D, the strand and tie rule, N, empty sequences, the ascending (i, j) order, the cap / needed protocol, the options
+ * and the error codes - with the range 0 <= max_dist <= NGSID_NEAR_WIDE_MAX_DIST.  The band is 2, 4 or 8 words per lane, the smallest that holds max_dist (63, 127,
+ * 255 edits); for max_dist <= NGSID_NEAR_MAX_DIST they run the one-word kernels and return exactly what the calls above return.  Scratch: one more pattern variant
+ * per sequence, padded for the widest band.  Profiling lines: k_near_within_wide, k_near_tiles_wide; k_near_check and k_near_pack are shared. */
+int32_t ngsid_ed_within_wide_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets,
+                                   const uint32_t* q_idx /* [n_pairs] */, const uint32_t* t_idx /* [n_pairs] */, uint64_t n_pairs,
+                                   int32_t max_dist, uint32_t flags, int32_t* dist /* [n_pairs] */, uint8_t* strand /* [n_pairs], may be NULL */);
+int32_t ngsid_near_pairs_wide(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags,
+                              uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand /* [cap] each */, uint64_t cap, uint64_t* n_found, uint64_t* needed);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,7 @@ CHIMERA_NFIELD, CHIMERA_ROWS, CHIMERA_LDS_QUERY = 7, 12, 2048                   
 CHIMERA_STRIP = 64 * CHIMERA_ROWS                                                   # NGSID_CHIMERA_STRIP: parent rows per pass of a wave
 MAX_CONSENSUS_LEN = 16384                                                           # include/ngsid.h NGSID_MAX_CONSENSUS_LEN
 NEAR_MAX_DIST, NEAR_BOTH_STRANDS = 31, 1                                            # include/ngsid_near.h NGSID_NEAR_MAX_DIST, NGSID_NEAR_BOTH_STRANDS
+NEAR_WIDE_MAX_DIST = 255                                                            # include/ngsid_near.h NGSID_NEAR_WIDE_MAX_DIST
 
 
 def chimera_profile_offsets(query_lens, pair_off):
@@ -773,12 +774,21 @@ class Api:
         (the smaller one; a tie goes to forward) -> (dist int32 [n], strand uint8 [n]): dist = -1 and strand = 0 where the distance exceeds max_dist (0 .. NEAR_MAX_DIST).
         queries / targets: lists of strings or read sets.  There is no CPU implementation: a library without the entry point is an error."""
         self._need("ngsid_near.h", "ed_within_batch", "near_pairs")
+        return self._ed_within("ed_within_batch", queries, targets, q_idx, t_idx, max_dist, both_strands)
+
+    def ed_within_wide(self, queries, targets, q_idx, t_idx, max_dist, both_strands=True):
+        """ngsid_ed_within_wide_batch: ed_within with max_dist 0 .. NEAR_WIDE_MAX_DIST (a band of 2, 4 or 8 words per lane above NEAR_MAX_DIST, the one-word kernel
+        below); the same arguments, dtypes and shapes.  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_near.h", "ed_within_wide_batch", "near_pairs_wide")
+        return self._ed_within("ed_within_wide_batch", queries, targets, q_idx, t_idx, max_dist, both_strands)
+
+    def _ed_within(self, entry, queries, targets, q_idx, t_idx, max_dist, both_strands):
         qs, ts = _as_reads(queries), _as_reads(targets)
         qi = np.ascontiguousarray(q_idx, dtype=np.uint32); ti = np.ascontiguousarray(t_idx, dtype=np.uint32)
         if len(qi) != len(ti): raise ValueError("ed_within: q_idx and t_idx hold one entry per pair")
         n = len(qi)
         dist = np.full(max(n, 1), -1, dtype=np.int32); strand = np.zeros(max(n, 1), dtype=np.uint8)
-        rc = self._call("ed_within_batch", C.byref(qs.c), C.byref(ts.c), _p(qi if n else np.zeros(1, np.uint32)), _p(ti if n else np.zeros(1, np.uint32)), C.c_uint64(n),
+        rc = self._call(entry, C.byref(qs.c), C.byref(ts.c), _p(qi if n else np.zeros(1, np.uint32)), _p(ti if n else np.zeros(1, np.uint32)), C.c_uint64(n),
                         C.c_int32(int(max_dist)), C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0), _p(dist), _p(strand))
         if rc: self._err(rc)
         return dist[:n], strand[:n]
@@ -788,15 +798,24 @@ class Api:
         dist uint8, strand uint8), in ascending (i, j) order.  The count call (cap = 0), then the fill call; cap: one call with room for that many pairs
         (NgsidError NGSID_ERR_CAPACITY with .needed when there are more).  There is no CPU implementation: a library without the entry point is an error."""
         self._need("ngsid_near.h", "ed_within_batch", "near_pairs")
+        return self._near_pairs("near_pairs", seqs, max_dist, both_strands, cap)
+
+    def near_pairs_wide(self, seqs, max_dist, both_strands=True, cap=None):
+        """ngsid_near_pairs_wide: near_pairs with max_dist 0 .. NEAR_WIDE_MAX_DIST; the same arguments, dtypes (dist stays uint8: 255 fits) and shapes.  There is no
+        CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_near.h", "ed_within_wide_batch", "near_pairs_wide")
+        return self._near_pairs("near_pairs_wide", seqs, max_dist, both_strands, cap)
+
+    def _near_pairs(self, entry, seqs, max_dist, both_strands, cap):
         rs = _as_reads(seqs)
         flags = C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0)
         found, needed = C.c_uint64(0), C.c_uint64(0)
         if cap is None:
-            rc = self._call("near_pairs", C.byref(rs.c), C.c_int32(int(max_dist)), flags, None, None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
+            rc = self._call(entry, C.byref(rs.c), C.c_int32(int(max_dist)), flags, None, None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
             if rc and rc != -4: self._err(rc)
             cap = int(needed.value)
         pi = np.zeros(max(cap, 1), dtype=np.uint32); pj = np.zeros(max(cap, 1), dtype=np.uint32); dist = np.zeros(max(cap, 1), dtype=np.uint8); strand = np.zeros(max(cap, 1), dtype=np.uint8)
-        rc = self._call("near_pairs", C.byref(rs.c), C.c_int32(int(max_dist)), flags, _p(pi), _p(pj), _p(dist), _p(strand), C.c_uint64(cap), C.byref(found), C.byref(needed))
+        rc = self._call(entry, C.byref(rs.c), C.c_int32(int(max_dist)), flags, _p(pi), _p(pj), _p(dist), _p(strand), C.c_uint64(cap), C.byref(found), C.byref(needed))
         if rc:
             try: self._err(rc)
             except NgsidError as e:

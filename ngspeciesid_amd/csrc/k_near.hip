@@ -22,6 +22,16 @@
 //   the last sequence at most max_dist bases longer: the length bound removes whole tiles, and the lanes of a wave see lengths within max_dist of each other.  The text is
 //   x, the shorter one, the same for every lane: its words and masks are wave-uniform, and every lane has the same number of columns.  A lane that finds a pair appends
 //   (min, max of the caller's indices | distance, strand) through one counter; the host sorts what came back.
+//
+// The wide calls (ngsid_ed_within_wide_batch / ngsid_near_pairs_wide, max_dist up to 255) run the same recurrence on W band words per lane, W = 2, 4 or 8, the smallest
+// that holds max_dist: B = 64 W bits, H = B / 2 - 1, bit r of the band in column c is row c - H + r, the cell (m, n) sits at bit H - (n - m), and the band holds
+// K = 32 W - 1 edits by the argument above.  The sum (Eq & VP) + VP carries from word to word, D0 >> 1 takes its top bit from the next word, the +1 of the row that
+// enters the band belongs to the top word, VP starts as ones from bit H up.  The tracked bit lies in word (H - (n - m)) >> 6, which differs from lane to lane: it
+// is picked by a compare / select chain over the W words, never by indexing the register array.  k_near_pack_wide writes one more pattern variant per sequence, padded
+// for the widest band (base p at bit p + 255): the window of column c + 1 of a W-word band starts at bit c + 32 (8 - W), a whole number of words in.  A lane keeps
+// 2 W + 1 words per plane, slides them by one word per 32 columns and loads the word that enters one block ahead.  The text planes are the ones above.  Below 32
+// edits the wide calls run the one-word kernels.  tests/variants_wide_band_model.py is the Python-int model.  The found-pair record of k_near_tiles_wide is 16 bits
+// (distance | strand << 15).
 #include "ngsid_host.h"
 #include "../../include/ngsid_near.h"
 #include <numeric>
@@ -29,6 +39,8 @@
 typedef uint64_t u64;
 
 static_assert(NGSID_NEAR_MAX_DIST == 31, "the band of near_band_ed is rows c - 31 .. c + 32");
+#define NEAR_WMAX 8                     // the widest band in words: the wide pattern planes carry 32 * NEAR_WMAX - 1 pad bits
+static_assert(NGSID_NEAR_WIDE_MAX_DIST == 32 * NEAR_WMAX - 1, "the widest band of near_band_ed_wide holds 32 W - 1 edits");
 
 namespace {
 
@@ -158,6 +170,156 @@ void k_near_tiles(const uint64_t* __restrict__ off, const uint64_t* __restrict__
     }
 }
 
+// ---- the wide band: W words per lane
+// words per wide pattern plane of a sequence of len bases: its bits, the eight pad words in front, and what a lane reads beyond the window's first word for a text up to
+// 32 W - 1 bases longer: 2 W words of the window and the word loaded one block ahead (the farthest read is word ((len + 31) >> 5) + 2 W + 8, see near_band_ed_wide)
+__host__ __device__ __forceinline__ int near_nw_wide(int len) { return ((len + 31) >> 5) + 3 * NEAR_WMAX + 2; }
+
+// wide pattern planes of sequence s: woff[s] * 3 words in, plane k at k * nw; base p at bit p + 32 * NEAR_WMAX - 1
+__global__ __launch_bounds__(64)
+void k_near_pack_wide(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, u64 s0, uint32_t* __restrict__ planes)
+{
+    const u64 s = s0 + blockIdx.x;
+    const u64 a = off[s];
+    const int L = (int)(off[s + 1] - a), nw = near_nw_wide(L);
+    uint32_t* base = planes + woff[s] * 3;
+    for (int w = threadIdx.x; w < nw; w += 64) {
+        uint32_t b0 = 0, b1 = 0, b2 = 0;
+        for (int t = 0; t < 32; ++t) {
+            const int p = 32 * w + t - (32 * NEAR_WMAX - 1);
+            const int c = p >= 0 && p < L ? near_code(seq[a + p]) : 7;
+            b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
+        }
+        base[w] = b0; base[(size_t)nw + w] = b1; base[(size_t)2 * nw + w] = b2;
+    }
+}
+
+// bits s .. s + 31 of hi:lo, s = 0 .. 31, as one v_alignbit_b32: unlike the 64-bit shift of near_funnel it takes any two registers, so a word that is the high half of
+// one window and the low half of the next is not copied into a register pair of its own (W = 8: 151 instead of 241 VGPRs)
+__device__ __forceinline__ uint32_t near_align(uint32_t hi, uint32_t lo, int s) { return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)s); }
+
+// pat: the wide pattern planes of a sequence of m bases (plane k at pat + k * nwp), txt: a TEXT or TEXT_RC variant of one of n bases -> their edit distance if it is
+// <= K <= 32 W - 1, else -1.  Reads pattern words up to (8 - W) + ((n - 1) >> 5) + 2 W + 1 <= ((m + 31) >> 5) + 2 W + 8 < near_nw_wide(m) (n <= m + 32 W - 1 behind
+// the length test) and text words up to ((n - 1) >> 5) + 1 < near_nw(n).  Every array is indexed by unrolled constants only: the band lives in registers.
+template <int W>
+__device__ __forceinline__ int near_band_ed_wide(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt, int nwt, int m, int n, int K)
+{
+    constexpr int H = 32 * W - 1, NA = 2 * W + 1;
+    const int d = n - m;
+    int val = d < 0 ? -d : 0;
+    if (val > K || d > K) return -1;
+    if (n == 0) return val;
+    const int sb = H - d, sw = sb >> 6, sbit = sb & 63;
+    u64 VP[W], VN[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) { VP[j] = j < (H >> 6) ? 0ull : j == (H >> 6) ? ~0ull << (H & 63) : ~0ull; VN[j] = 0; }
+    pat += NEAR_WMAX - W;
+    uint32_t a[3][NA], t[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) a[k][i] = pat[(size_t)k * nwp + i];
+        t[k] = txt[(size_t)k * nwt];
+    }
+    for (int c0 = 0; c0 < n; c0 += 32) {
+        const int w = c0 >> 5;
+        uint32_t nx[3], tn[3];                                       // the words of the next block, loaded one block ahead
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { nx[k] = pat[(size_t)k * nwp + w + NA]; tn[k] = txt[(size_t)k * nwt + w + 1]; }
+        const int ce = min(32, n - c0);
+        for (int s = 0; s < ce; ++s) {
+            const uint32_t T0 = 0u - ((t[0] >> s) & 1u), T1 = 0u - ((t[1] >> s) & 1u), T2 = 0u - ((t[2] >> s) & 1u);
+            u64 D0[W];
+            unsigned long long cy = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const uint32_t nlo = (near_align(a[0][2 * j + 1], a[0][2 * j], s) ^ T0) | (near_align(a[1][2 * j + 1], a[1][2 * j], s) ^ T1) | (near_align(a[2][2 * j + 1], a[2][2 * j], s) ^ T2);
+                const uint32_t nhi = (near_align(a[0][2 * j + 2], a[0][2 * j + 1], s) ^ T0) | (near_align(a[1][2 * j + 2], a[1][2 * j + 1], s) ^ T1) | (near_align(a[2][2 * j + 2], a[2][2 * j + 1], s) ^ T2);
+                const u64 Eq = ~(((u64)nhi << 32) | nlo);
+                const u64 S = __builtin_addcll(Eq & VP[j], VP[j], cy, &cy);      // the carry runs from word j to word j + 1
+                D0[j] = (S ^ VP[j]) | Eq | VN[j];
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const u64 HP = VN[j] | ~(D0[j] | VP[j]);
+                const u64 HN = D0[j] & VP[j];
+                const u64 D0s = j + 1 < W ? (D0[j] >> 1) | (D0[j + 1] << 63) : D0[j] >> 1;
+                VP[j] = HN | ~(D0s | HP) | (j == W - 1 ? 1ull << 63 : 0ull);
+                VN[j] = D0s & HP;
+            }
+            u64 tr = D0[0];
+#pragma unroll
+            for (int j = 1; j < W; ++j) tr = sw == j ? D0[j] : tr;
+            val += 1 - (int)((tr >> sbit) & 1u);
+            if (val > K) return -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int i = 0; i + 1 < NA; ++i) a[k][i] = a[k][i + 1];
+            a[k][NA - 1] = nx[k]; t[k] = tn[k];
+        }
+    }
+    return val;
+}
+
+// pat3w: the wide pattern planes, txt3: the nine one-word planes of the text (its TEXT and TEXT_RC variants are read)
+template <int W>
+__device__ __forceinline__ int near_both_wide(const uint32_t* __restrict__ pat3w, int nwp, const uint32_t* __restrict__ txt3, int nwt, int m, int n, int K, bool both, int* strand)
+{
+    int best = near_band_ed_wide<W>(pat3w, nwp, txt3 + (size_t)(NEAR_TEXT * 3) * nwt, nwt, m, n, K);
+    *strand = 0;
+    if (both && best != 0) {
+        const int r = near_band_ed_wide<W>(pat3w, nwp, txt3 + (size_t)(NEAR_TEXT_RC * 3) * nwt, nwt, m, n, best < 0 ? K : best - 1);
+        if (r >= 0) { best = r; *strand = 1; }
+    }
+    return best;
+}
+
+template <int W>
+__global__ __launch_bounds__(256)
+void k_near_within_wide(const uint64_t* __restrict__ qoff, const uint64_t* __restrict__ qwoff, const uint32_t* __restrict__ qplw, const uint64_t* __restrict__ toff, const uint64_t* __restrict__ twoff,
+                        const uint32_t* __restrict__ tpl, const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ tidx, u64 p0, u64 p1, int K, int both,
+                        int32_t* __restrict__ dist, uint8_t* __restrict__ strand)
+{
+    const u64 p = p0 + (u64)blockIdx.x * 256 + threadIdx.x;
+    if (p >= p1) return;
+    const uint32_t q = qidx[p], t = tidx[p];
+    const int m = (int)(qoff[q + 1] - qoff[q]), n = (int)(toff[t + 1] - toff[t]);
+    int st = 0;
+    const int best = near_both_wide<W>(qplw + qwoff[q] * 3, near_nw_wide(m), tpl + twoff[t] * 9, near_nw(n), m, n, K, both != 0, &st);
+    dist[p] = best;
+    strand[p] = (uint8_t)st;
+}
+
+// k_near_tiles with the wide band: woffw / plw = the wide pattern planes of the same set; a found pair's record is distance | strand << 15
+template <int W>
+__global__ __launch_bounds__(256)
+void k_near_tiles_wide(const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, const uint32_t* __restrict__ pl, const uint64_t* __restrict__ woffw, const uint32_t* __restrict__ plw,
+                       const uint32_t* __restrict__ order, const uint32_t* __restrict__ hi, const uint64_t* __restrict__ toff, uint32_t xa, uint32_t nrows, u64 ntiles, int K, int both,
+                       u64* __restrict__ key, uint16_t* __restrict__ ds, u64 limit, unsigned long long* counter)
+{
+    const int lane = threadIdx.x & 63;
+    const u64 Tl = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const u64 T = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(Tl >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)Tl);
+    if (T >= ntiles) return;
+    uint32_t lo = 0, up = nrows;                                   // the last r with toff[r] <= T
+    while (up - lo > 1) { const uint32_t mid = lo + (up - lo) / 2; if (toff[mid] <= T) lo = mid; else up = mid; }
+    const uint32_t x = xa + lo;
+    const u64 y64 = (u64)x + 1 + (T - toff[lo]) * 64 + lane;
+    if (y64 > hi[x]) return;
+    const uint32_t y = (uint32_t)y64, ox = order[x], oy = order[y];
+    const int n = (int)(off[ox + 1] - off[ox]), m = (int)(off[oy + 1] - off[oy]);
+    int st = 0;
+    const int best = near_both_wide<W>(plw + woffw[oy] * 3, near_nw_wide(m), pl + woff[ox] * 9, near_nw(n), m, n, K, both != 0, &st);
+    if (best < 0) return;
+    const unsigned long long slot = atomicAdd(counter, 1ull);
+    if (slot < limit) {
+        key[slot] = ((u64)min(ox, oy) << 32) | max(ox, oy);
+        ds[slot] = (uint16_t)(best | (st << 15));
+    }
+}
+
 // the planes of every sequence of R in `buf` (grow-only), the word offsets on the device
 int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
 {
@@ -175,10 +337,27 @@ int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevB
     return NGSID_OK;
 }
 
-// the checks both entry points share: max_dist, the length bound, the alphabet
-int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, const DevReads* A, const DevReads* B)
+// the wide pattern planes of every sequence of R in `buf` (grow-only), the word offsets on the device
+int32_t near_pack_wide(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
 {
-    if (max_dist < 0 || max_dist > NGSID_NEAR_MAX_DIST) NGSID_FAIL(ctx, NGSID_ERR_ARG, "max_dist %d outside 0 .. NGSID_NEAR_MAX_DIST=%d", max_dist, NGSID_NEAR_MAX_DIST);
+    PinVec<uint64_t> woff(R.n + 1);
+    woff[0] = 0;
+    for (uint64_t s = 0; s < R.n; ++s) woff[s + 1] = woff[s] + (uint64_t)near_nw_wide((int)(R.h_off[s + 1] - R.h_off[s]));
+    HIPCHK(ctx, buf.reserve(woff[R.n] * 3));
+    NGSID_TRY(dev_put(ctx, d_woff, woff.data(), R.n + 1));
+    ProfScope ps_(ctx, "k_near_pack");
+    for (uint64_t s0 = 0; s0 < R.n; s0 += 1u << 30) {
+        hipLaunchKernelGGL(k_near_pack_wide, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, buf.p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return NGSID_OK;
+}
+
+// the checks the entry points share: max_dist (limit = NGSID_NEAR_MAX_DIST or NGSID_NEAR_WIDE_MAX_DIST), the length bound, the alphabet
+int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, int32_t limit, const DevReads* A, const DevReads* B)
+{
+    if (max_dist < 0 || max_dist > limit) NGSID_FAIL(ctx, NGSID_ERR_ARG, "max_dist %d outside 0 .. %s=%d", max_dist, limit == NGSID_NEAR_MAX_DIST ? "NGSID_NEAR_MAX_DIST" : "NGSID_NEAR_WIDE_MAX_DIST", limit);
     const uint32_t maxlen = std::max(A->maxlen, B ? B->maxlen : 0u);
     if (maxlen > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a sequence of %u bases exceeds NGSID_MAX_CONSENSUS_LEN=%d", maxlen, NGSID_MAX_CONSENSUS_LEN);
     if (A->n >= 0x100000000ull || (B && B->n >= 0x100000000ull)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "a set is limited to 2^32 - 1 sequences");
@@ -192,28 +371,40 @@ int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, const DevReads* A, const De
     return NGSID_OK;
 }
 
-}  // namespace
+// the band words of a wide call: the smallest instance that holds max_dist, 1 = the one-word kernels
+int near_width(int32_t max_dist) { return max_dist <= NGSID_NEAR_MAX_DIST ? 1 : max_dist <= 63 ? 2 : max_dist <= 127 ? 4 : 8; }
 
-extern "C" int32_t ngsid_ed_within_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
-                                         int32_t max_dist, uint32_t flags, int32_t* dist, uint8_t* strand)
+// ngsid_ed_within_batch (limit = NGSID_NEAR_MAX_DIST) and ngsid_ed_within_wide_batch (limit = NGSID_NEAR_WIDE_MAX_DIST) behind their argument checks
+int32_t near_within_run(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
+                        int32_t max_dist, int32_t limit, uint32_t flags, int32_t* dist, uint8_t* strand)
 {
-    ApiClock api_clock_(ctx, "ed_within_batch");
-    if (!ctx) return NGSID_ERR_ARG;
     if (n_pairs && !dist) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null output");
     PairBatch B;
     NGSID_TRY(ngsid_pair_batch(ctx, queries, targets, q_idx, t_idx, n_pairs, B));
-    NGSID_TRY(near_check(ctx, max_dist, &B.Q, &B.T));
+    NGSID_TRY(near_check(ctx, max_dist, limit, &B.Q, &B.T));
     if (n_pairs == 0) return NGSID_OK;
+    const int W = near_width(max_dist);
     DevBuf<uint64_t> d_qw, d_tw; DevBuf<int32_t> d_dist; DevBuf<uint8_t> d_strand;
-    NGSID_TRY(near_pack(ctx, B.Q, ctx->near_pl[0], d_qw)); NGSID_TRY(near_pack(ctx, B.T, ctx->near_pl[1], d_tw));
+    if (W == 1) { NGSID_TRY(near_pack(ctx, B.Q, ctx->near_pl[0], d_qw)); } else { NGSID_TRY(near_pack_wide(ctx, B.Q, ctx->near_plw, d_qw)); }
+    NGSID_TRY(near_pack(ctx, B.T, ctx->near_pl[1], d_tw));
     HIPCHK(ctx, d_dist.alloc(n_pairs)); HIPCHK(ctx, d_strand.alloc(n_pairs));
     const long long opt = ngsid_opt(ctx, "near_chunk_pairs", 0);
     const uint64_t chunk = opt > 0 ? (uint64_t)opt : (uint64_t)1 << 30;
     for (uint64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
         const uint64_t p1 = std::min(n_pairs, p0 + chunk);
-        ProfScope ps_(ctx, "k_near_within");
-        hipLaunchKernelGGL(k_near_within, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_pl[0].p, B.T.off, d_tw.p, ctx->near_pl[1].p,
-                           B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), d_dist.p, d_strand.p);
+        const dim3 grid((unsigned)((p1 - p0 + 255) / 256));
+        const int both = (int)(flags & NGSID_NEAR_BOTH_STRANDS);
+        if (W == 1) {
+            ProfScope ps_(ctx, "k_near_within");
+            hipLaunchKernelGGL(k_near_within, grid, dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_pl[0].p, B.T.off, d_tw.p, ctx->near_pl[1].p,
+                               B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, both, d_dist.p, d_strand.p);
+        } else {
+            ProfScope ps_(ctx, "k_near_within_wide");
+#define NEAR_WITHIN_WIDE(WW) hipLaunchKernelGGL((k_near_within_wide<WW>), grid, dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_plw.p, B.T.off, d_tw.p, ctx->near_pl[1].p, \
+                                                B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, both, d_dist.p, d_strand.p)
+            if (W == 2) NEAR_WITHIN_WIDE(2); else if (W == 4) NEAR_WITHIN_WIDE(4); else NEAR_WITHIN_WIDE(8);
+#undef NEAR_WITHIN_WIDE
+        }
         HIPCHK(ctx, hipGetLastError());
     }
     NGSID_TRY(dev_get(ctx, dist, d_dist.p, n_pairs));
@@ -222,18 +413,22 @@ extern "C" int32_t ngsid_ed_within_batch(ngsid_ctx* ctx, const ngsid_reads_t* qu
     return NGSID_OK;
 }
 
-extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
-                                    uint64_t cap, uint64_t* n_found, uint64_t* needed)
+// ngsid_near_pairs (dist_limit = NGSID_NEAR_MAX_DIST) and ngsid_near_pairs_wide (dist_limit = NGSID_NEAR_WIDE_MAX_DIST) behind the context check.  REC = the found-pair record:
+// uint8_t (distance | strand << 7) with the one-word kernel, uint16_t (distance | strand << 15) with a wide one
+template <typename REC>
+int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, int32_t dist_limit, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
+                       uint64_t cap, uint64_t* n_found, uint64_t* needed)
 {
-    ApiClock api_clock_(ctx, "near_pairs");
-    if (!ctx) return NGSID_ERR_ARG;
+    constexpr bool WIDE = sizeof(REC) == 2;
+    constexpr int SBIT = WIDE ? 15 : 7;
     if (!seqs || !n_found || !needed || (cap && (!pair_i || !pair_j || !dist || !strand))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     *n_found = 0; *needed = 0;
     DevReads R;
     NGSID_TRY(ngsid_upload_reads(ctx, seqs, &R, false));
-    NGSID_TRY(near_check(ctx, max_dist, &R, nullptr));
+    NGSID_TRY(near_check(ctx, max_dist, dist_limit, &R, nullptr));
     const uint64_t N = R.n;
     if (N < 2) return NGSID_OK;
+    const int W = near_width(max_dist);                              // (WIDE: 2, 4 or 8; else 1)
     // ---- sorted by (length, index); hi[x] = the last sorted position whose sequence is at most max_dist bases longer than x's; 64 candidates per tile
     auto len = [&](uint32_t s) { return (uint32_t)(R.h_off[(size_t)s + 1] - R.h_off[s]); };
     PinVec<uint32_t> order(N), hi(N);
@@ -246,17 +441,19 @@ extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, i
         hi[x] = (uint32_t)y;
         tiles[x + 1] = tiles[x] + (y - x + 63) / 64;
     }
-    DevBuf<uint64_t> d_woff, d_toff; DevBuf<uint32_t> d_order, d_hi; DevBuf<unsigned long long> d_ctr;
+    DevBuf<uint64_t> d_woff, d_woffw, d_toff; DevBuf<uint32_t> d_order, d_hi; DevBuf<unsigned long long> d_ctr;
     NGSID_TRY(near_pack(ctx, R, ctx->near_pl[0], d_woff));
+    if (WIDE) { NGSID_TRY(near_pack_wide(ctx, R, ctx->near_plw, d_woffw)); }
     NGSID_TRY(dev_put(ctx, d_order, order.data(), N)); NGSID_TRY(dev_put(ctx, d_hi, hi.data(), N));
     HIPCHK(ctx, d_ctr.alloc(1));
     // ---- the found buffer: cap entries, or what a share of the free device memory holds; rows in chunks
-    const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / 9);
-    if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F)); }
+    const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / (8 + sizeof(REC)));
+    if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F * sizeof(REC))); }
+    REC* const d_ds = reinterpret_cast<REC*>(ctx->near_ds.p);
     const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0);
     const uint64_t max_tiles = (uint64_t)1 << 30;                     // per launch: four tiles per workgroup
     bool fill = cap > 0;
-    std::vector<uint64_t> keys; std::vector<uint8_t> dss;
+    std::vector<uint64_t> keys; std::vector<REC> dss;
     uint64_t total = 0, rows_now = opt > 0 ? (uint64_t)opt : N;
     PinVec<uint64_t> h_toff;
     for (uint64_t xa = 0; xa < N; ) {
@@ -270,9 +467,17 @@ extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, i
         NGSID_TRY(dev_put(ctx, d_toff, h_toff.data(), xb - xa + 1));
         HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long), ctx->stream));
         const uint64_t limit = fill ? std::min(F, cap - total) : 0;
-        { ProfScope ps_(ctx, "k_near_tiles");
-          hipLaunchKernelGGL(k_near_tiles, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
-                             (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, ctx->near_ds.p, (u64)limit, d_ctr.p); }
+        if constexpr (!WIDE) {
+            ProfScope ps_(ctx, "k_near_tiles");
+            hipLaunchKernelGGL(k_near_tiles, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
+                               (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, d_ds, (u64)limit, d_ctr.p);
+        } else {
+            ProfScope ps_(ctx, "k_near_tiles_wide");
+#define NEAR_TILES_WIDE(WW) hipLaunchKernelGGL((k_near_tiles_wide<WW>), dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_woffw.p, ctx->near_plw.p, d_order.p, d_hi.p, \
+                                               d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, d_ds, (u64)limit, d_ctr.p)
+            if (W == 2) NEAR_TILES_WIDE(2); else if (W == 4) NEAR_TILES_WIDE(4); else NEAR_TILES_WIDE(8);
+#undef NEAR_TILES_WIDE
+        }
         HIPCHK(ctx, hipGetLastError());
         unsigned long long c = 0;
         NGSID_TRY(dev_get(ctx, &c, d_ctr.p, 1));
@@ -285,7 +490,7 @@ extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, i
         if (fill && c) {
             const size_t at = keys.size();
             keys.resize(at + c); dss.resize(at + c);
-            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, ctx->near_ds.p, (size_t)c));
+            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, d_ds, (size_t)c));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
         total += c;
@@ -298,9 +503,46 @@ extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, i
     std::iota(perm.begin(), perm.end(), (uint64_t)0);
     std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return keys[a] < keys[b]; });
     for (uint64_t k = 0; k < total; ++k) {
-        const uint64_t key = keys[perm[k]]; const uint8_t v = dss[perm[k]];
-        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = v & 0x7f; strand[k] = v >> 7;
+        const uint64_t key = keys[perm[k]]; const REC v = dss[perm[k]];
+        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = (uint8_t)(v & ((1u << SBIT) - 1)); strand[k] = (uint8_t)(v >> SBIT);
     }
     *n_found = total;
     return NGSID_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t ngsid_ed_within_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
+                                         int32_t max_dist, uint32_t flags, int32_t* dist, uint8_t* strand)
+{
+    ApiClock api_clock_(ctx, "ed_within_batch");
+    if (!ctx) return NGSID_ERR_ARG;
+    return near_within_run(ctx, queries, targets, q_idx, t_idx, n_pairs, max_dist, NGSID_NEAR_MAX_DIST, flags, dist, strand);
+}
+
+extern "C" int32_t ngsid_ed_within_wide_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
+                                              int32_t max_dist, uint32_t flags, int32_t* dist, uint8_t* strand)
+{
+    ApiClock api_clock_(ctx, "ed_within_wide_batch");
+    if (!ctx) return NGSID_ERR_ARG;
+    return near_within_run(ctx, queries, targets, q_idx, t_idx, n_pairs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, dist, strand);
+}
+
+extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
+                                    uint64_t cap, uint64_t* n_found, uint64_t* needed)
+{
+    ApiClock api_clock_(ctx, "near_pairs");
+    if (!ctx) return NGSID_ERR_ARG;
+    return near_pairs_run<uint8_t>(ctx, seqs, max_dist, NGSID_NEAR_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
+}
+
+// (a max_dist the one-word band holds, or one outside the range, goes the one-word way: the same kernels, the same refusal)
+extern "C" int32_t ngsid_near_pairs_wide(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
+                                         uint64_t cap, uint64_t* n_found, uint64_t* needed)
+{
+    ApiClock api_clock_(ctx, "near_pairs_wide");
+    if (!ctx) return NGSID_ERR_ARG;
+    if (max_dist > NGSID_NEAR_MAX_DIST && max_dist <= NGSID_NEAR_WIDE_MAX_DIST)
+        return near_pairs_run<uint16_t>(ctx, seqs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
+    return near_pairs_run<uint8_t>(ctx, seqs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
 }

@@ -318,7 +318,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     key of run_hot_path per sample, the final consensuses of ALL samples in one search and one verification call.  chimeras=True: the chimeras
     key of run_hot_path per sample, ALL samples in one model call (parents within a sample only).  variants=True (extension; variants.py, include/ngsid_near.h):
     also variants = dict(members = one dict(variant, dist, strand) per centre of the sample, table = the study-wide table of variants.build, the same object in every
-    sample's dict): the final sequences of ALL samples in one near-pairs call, clustered by abundance (variant_kwargs: identity, max_dist, both_strands); every other key
+    sample's dict): the final sequences of ALL samples in one near-pairs call, clustered by abundance (variant_kwargs: identity, max_dist, both_strands, wide_max_dist - the last replaces max_dist and takes the wide kernels); every other key
     is what variants=False returns.  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")

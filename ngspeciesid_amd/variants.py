@@ -1,5 +1,5 @@
-"""The study-wide variant table of a multi-sample run (extension; `--variants`, sub-command `variants`): the policy on top of ngsid_near_pairs
-(include/ngsid_near.h, csrc/k_near.hip).
+"""The study-wide variant table of a multi-sample run (extension; `--variants`, sub-command `variants`): the policy on top of ngsid_near_pairs and, with
+`--variant_wide_max_dist`, ngsid_near_pairs_wide (include/ngsid_near.h, csrc/k_near.hip).
 
 The library returns, for the final consensuses of all samples together, every pair that lies within a few edits on either strand, as integers.  What a variant is -
 the admissible distance of a pair, which sequence stands for its neighbours, the tables - is decided here, in Python and numpy, and no device call is made except
@@ -12,9 +12,9 @@ from __future__ import annotations
 import os
 import numpy as np
 from . import classify
-from ._capi import ReadSet, NEAR_MAX_DIST
+from ._capi import ReadSet, NEAR_MAX_DIST, NEAR_WIDE_MAX_DIST
 
-DEFAULTS = dict(identity="0.97", max_dist=NEAR_MAX_DIST)
+DEFAULTS = dict(identity="0.97", max_dist=NEAR_MAX_DIST, wide_max_dist=None)
 MEMBER_COLUMNS = ("sample", "consensus id", "reads", "variant", "dist", "strand")
 _TEXT = ("sample", "consensus id", "variant", "strand")
 
@@ -41,15 +41,23 @@ def _identity_fraction(identity):
     return num, den
 
 
-def thresholds(lengths, identity, max_dist):
+def thresholds(lengths, identity, max_dist, wide_max_dist=None):
     """the admissible distance of every pair: thr(i, j) = min(max_dist, floor((1 - identity) * max(len_i, len_j))).  identity is a decimal STRING ('0.97'); the
     product is formed once, in integer arithmetic, as ((den - num) * length) // den with identity = num / den, so that 0.97 of 600 bases is exactly 18 edits and never
     17 by a float's last bit.  Since the bound grows with the length, thr(i, j) is the larger of the two per-sequence values
     -> (t int64 [n] with thr(i, j) = max(t[i], t[j]), K = the largest of them = the max_dist the device call is made with).  A max_dist above NEAR_MAX_DIST is a
-    ValueError that names the flag: the band of the kernel holds 31 edits, and a silently smaller bound would split variants the user asked to join."""
-    max_dist = int(max_dist)
-    if not 0 <= max_dist <= NEAR_MAX_DIST:
-        raise ValueError("--variant_max_dist must be 0..%d (the device band holds %d edits), not %d" % (NEAR_MAX_DIST, NEAR_MAX_DIST, max_dist))
+    ValueError that names the flag: the one-word band of the kernel holds 31 edits, and a silently smaller bound would split variants the user asked to join.
+    wide_max_dist (--variant_wide_max_dist, 0 .. NEAR_WIDE_MAX_DIST), when given, replaces max_dist as the edit bound (max_dist is then not looked at): the call
+    goes to the wide kernels."""
+    if wide_max_dist is not None:
+        max_dist = int(wide_max_dist)
+        if not 0 <= max_dist <= NEAR_WIDE_MAX_DIST:
+            raise ValueError("--variant_wide_max_dist must be 0..%d (the widest device band holds %d edits), not %d" % (NEAR_WIDE_MAX_DIST, NEAR_WIDE_MAX_DIST, max_dist))
+    else:
+        max_dist = int(max_dist)
+        if not 0 <= max_dist <= NEAR_MAX_DIST:
+            raise ValueError("--variant_max_dist must be 0..%d (the one-word device band holds %d edits; --variant_wide_max_dist goes up to %d), not %d"
+                             % (NEAR_MAX_DIST, NEAR_MAX_DIST, NEAR_WIDE_MAX_DIST, max_dist))
     num, den = _identity_fraction(identity)
     t = np.array([min(max_dist, ((den - num) * int(L)) // den) for L in lengths], dtype=np.int64)
     return t, (int(t.max()) if len(t) else 0)
@@ -119,13 +127,15 @@ def read_table(path):
         return [{c: (v if c in _TEXT else int(v)) for c, v in zip(cols, line.rstrip("\n").split("\t"))} for line in fh if line.strip()]
 
 
-def build(api, col, identity=DEFAULTS["identity"], max_dist=DEFAULTS["max_dist"], both_strands=True):
-    """thresholds + ONE Api.near_pairs call over the sequences of all samples + cluster + table -> the dict of table(), with variant_of / dist / strand [n] beside it"""
+def build(api, col, identity=DEFAULTS["identity"], max_dist=DEFAULTS["max_dist"], both_strands=True, wide_max_dist=DEFAULTS["wide_max_dist"]):
+    """thresholds + ONE Api.near_pairs call (Api.near_pairs_wide when wide_max_dist is given) over the sequences of all samples + cluster + table -> the dict of
+    table(), with variant_of / dist / strand [n] beside it"""
     seqs = col["seqs"]
     lengths = [len(s) for s in seqs]
-    thr, K = thresholds(lengths, identity, max_dist)
+    thr, K = thresholds(lengths, identity, max_dist, wide_max_dist)
     if len(seqs) > 1:
-        pi, pj, dist, strand = api.near_pairs(ReadSet.from_strings(list(seqs)), K, both_strands=both_strands)
+        near = api.near_pairs if wide_max_dist is None else api.near_pairs_wide
+        pi, pj, dist, strand = near(ReadSet.from_strings(list(seqs)), K, both_strands=both_strands)
     else:
         pi = pj = dist = strand = np.zeros(0, dtype=np.int64)
     variant_of, centroids, mdist, mstrand = cluster(col["sizes"], lengths, seqs, (pi, pj), dist, thr, strand)
@@ -137,7 +147,7 @@ def build(api, col, identity=DEFAULTS["identity"], max_dist=DEFAULTS["max_dist"]
 def check_args(args):
     """the range checks of the --variant_* flags -> an error text or None"""
     try:
-        thresholds([], args.variant_identity, args.variant_max_dist)
+        thresholds([], args.variant_identity, args.variant_max_dist, getattr(args, "variant_wide_max_dist", None))
     except ValueError as e:
         return str(e)
     return None
@@ -148,11 +158,12 @@ def add_flags(p):
     d = DEFAULTS
     p.add_argument('--variant_identity', type=str, default=d["identity"], help='extension: two consensuses are one variant when they differ by at most (1 - this) of the longer one\'s length in edits (a decimal fraction; the product is rounded down)')
     p.add_argument('--variant_max_dist', type=int, default=d["max_dist"], help='extension: ... and by at most this many edits (0..%d)' % NEAR_MAX_DIST)
+    p.add_argument('--variant_wide_max_dist', type=int, default=d["wide_max_dist"], help='extension: when given, replaces --variant_max_dist as the edit bound (0..%d) and the comparison runs on the wide band kernels: for long amplicons or a low --variant_identity' % NEAR_WIDE_MAX_DIST)
     p.add_argument('--variant_one_strand', action='store_true', help='extension: compare the consensuses as they are, not also against their reverse complements')
 
 
 def _kwargs(args):
-    return dict(identity=args.variant_identity, max_dist=args.variant_max_dist, both_strands=not args.variant_one_strand)
+    return dict(identity=args.variant_identity, max_dist=args.variant_max_dist, both_strands=not args.variant_one_strand, wide_max_dist=getattr(args, "variant_wide_max_dist", None))
 
 
 def run(args, api, groups):
