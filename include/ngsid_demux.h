@@ -46,6 +46,38 @@ typedef struct {
 int32_t ngsid_demux_locate(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_reads_t* tags, const ngsid_demux_params_t* prm,
                            int32_t* hits, int16_t* ed_all, int16_t* end_all);
 
+typedef struct {
+    int32_t max_ed;    /* >= 0: a position whose last-row score is above min(max_ed, pattern length - 1) belongs to no run */
+    int32_t iupac;     /* != 0: the IUPAC equalities of ngsid_host_infix_locate */
+} ngsid_demux_scan_params_t;
+
+#define NGSID_DEMUX_SCAN_NFIELD 3  /* pattern, end, ed */
+
+/* For every read and every pattern: every place in the WHOLE read where the pattern occurs within max_ed edits.
+ *
+ * Pattern p of m letters against read x of L letters, unit costs, equality as in ngsid_demux_locate (bytes, or the IUPAC rule with iupac != 0):
+ *   D[0][j] = 0 (j = 0 .. L), D[i][0] = i, D[i][j] = min(D[i-1][j-1] + [p[i-1] != x[j-1]], D[i-1][j] + 1, D[i][j-1] + 1);
+ *   s[j] = D[m][j+1] (j = 0 .. L-1): the smallest distance of p to an infix of x that ends at j;  k = min(max_ed, m - 1).
+ * A run is a maximal interval of consecutive positions j with s[j] <= k.  Every run yields exactly one hit: ed = the minimum of s over the run, end = the smallest j
+ * of the run with s[j] == ed.  A run still open at the last base is closed there.  A pattern may have several hits in a read; positions are in the read's own forward
+ * coordinates, and the call knows nothing of strands: reverse complements are patterns of their own.
+ * Where a (read, pattern) pair has a hit, its hit with the smallest (ed, end) has the ed and end of ngsid_host_infix_locate(p, m, x, L, max_ed, iupac, ...).
+ *
+ * reads: upper-case ACGTN (NGSID_ERR_ALPHABET otherwise), host- or device-resident, each up to NGSID_MAX_READ_LEN.  patterns: a host read set (qual ignored) of
+ * 1 .. 2 * NGSID_DEMUX_MAX_TAGS sequences of 1 .. NGSID_DEMUX_MAX_TAG_LEN upper-case letters.
+ *
+ * CSR result: the hits of read r are hit[hit_off[r] .. hit_off[r + 1]), hit[h * 3 + f] (int32): f = 0 pattern, 1 end, 2 ed; within a read in ascending (end, pattern)
+ * order.  hit_off holds n + 1 entries, hit has room for cap hits.  *needed = the number of hits, always.  cap = 0 with hit_off = hit = NULL asks for the count.
+ * More hits than cap: NGSID_ERR_CAPACITY, and neither array is written.
+ * Empty read sets, reads of length 0 and a single pattern are legal.  The reads run in chunks under a share of the free device memory (option
+ * "demux_scan_chunk_reads" fixes the chunk); results never depend on the chunking.
+ *
+ * One 64-bit Myers / Hyyro column per pattern and lane, the read streamed through it (k_demux_scan.hip).  Profiling line (ngsid_profile_read): k_demux_scan.
+ * Errors: NGSID_ERR_ARG (max_ed negative, no pattern, an empty pattern, too many patterns, a missing array), NGSID_ERR_TOO_LONG (a pattern above 64 letters),
+ * NGSID_ERR_ALPHABET, NGSID_ERR_CAPACITY, NGSID_ERR_HIP. */
+int32_t ngsid_demux_scan(ngsid_ctx* ctx, const ngsid_reads_t* reads, const ngsid_reads_t* patterns, const ngsid_demux_scan_params_t* prm,
+                         uint64_t* hit_off, int32_t* hit, uint64_t cap, uint64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

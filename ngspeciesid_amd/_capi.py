@@ -53,6 +53,10 @@ class DemuxParams(C.Structure):
     _fields_ = [("window", C.c_int32), ("max_ed", C.c_int32), ("iupac", C.c_int32)]  # include/ngsid_demux.h ngsid_demux_params_t
 
 
+class DemuxScanParams(C.Structure):
+    _fields_ = [("max_ed", C.c_int32), ("iupac", C.c_int32)]                         # include/ngsid_demux.h ngsid_demux_scan_params_t
+
+
 class RefDbParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("w", C.c_int32)]                                  # include/ngsid_classify.h ngsid_refdb_params_t
 
@@ -83,6 +87,7 @@ def chimera_profile_offsets(query_lens, pair_off):
 
 DEMUX_FIELDS = ("tag", "ed", "start", "end", "ed2")                                # the five integers per (read, side) of Api.demux_locate
 DEMUX_MAX_TAG_LEN, DEMUX_MAX_WINDOW = 64, 256
+DEMUX_SCAN_FIELDS = ("pattern", "end", "ed")                                       # the three integers per hit of Api.demux_scan
 
 
 SUPPORT_COLUMNS = ("depth", "agree", "A", "C", "G", "T", "del", "ins_after")       # the eight counters per base of Api.consensus_support
@@ -719,6 +724,28 @@ class Api:
         rc = self._call("demux_locate", C.byref(rs.c), C.byref(tg.c), C.byref(prm), _p(hits), _p(ed_all), _p(end_all))
         if rc: self._err(rc)
         return (hits, ed_all, end_all) if matrices else hits
+
+    def demux_scan(self, rs: ReadSet, patterns, max_ed=3, iupac=True, cap=None):
+        """ngsid_demux_scan: every place in the whole read where a pattern occurs within max_ed edits, one hit per run of qualifying positions -> (hit_off [n + 1]
+        uint64, hits [H, 3] int32 in DEMUX_SCAN_FIELDS order), within a read in ascending (end, pattern) order.  The count call (cap = 0), then the fill call; cap: one
+        call with room for that many hits (NgsidError NGSID_ERR_CAPACITY with .needed when there are more).  patterns: a list of strings or a host ReadSet; reverse
+        complements are patterns of their own.  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_demux.h", "demux_scan")
+        pt = _as_reads(patterns)
+        if pt.mem != MEM_HOST: raise ValueError("demux_scan takes the patterns as a host read set")
+        prm = DemuxScanParams(int(max_ed), 1 if iupac else 0)
+        needed = C.c_uint64(0)
+        if cap is None:
+            rc = self._call("demux_scan", C.byref(rs.c), C.byref(pt.c), C.byref(prm), None, None, C.c_uint64(0), C.byref(needed))
+            if rc and rc != -4: self._err(rc)
+            cap = int(needed.value)
+        hit_off = np.zeros(rs.n + 1, dtype=np.uint64); hits = np.zeros((max(int(cap), 1), 3), dtype=np.int32)
+        rc = self._call("demux_scan", C.byref(rs.c), C.byref(pt.c), C.byref(prm), _p(hit_off), _p(hits), C.c_uint64(int(cap)), C.byref(needed))
+        if rc:
+            try: self._err(rc)
+            except NgsidError as e:
+                e.needed = int(needed.value); raise
+        return hit_off, hits[:int(needed.value)]
 
     # ---- include/ngsid_classify.h
     def refdb_build(self, refs, k=13, w=20) -> "RefDb":

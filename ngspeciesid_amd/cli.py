@@ -91,6 +91,8 @@ def build_parser():
     p.add_argument('--demux_min_margin', type=int, default=2, help='extension: an end is ambiguous when its second-best tag is closer than this many edits to its best')
     p.add_argument('--demux_keep_tags', action='store_true', help='extension: leave the tags on the demultiplexed reads (default: cut each end behind its tag)')
     p.add_argument('--demux_only', action='store_true', help='extension: stop after the demultiplexing outputs')
+    p.add_argument('--demux_mid_tags', type=str, default='off', choices=['off', 'discard', 'split'], help='extension: search the WHOLE read for the sheet\'s tags on both strands (GPU) and treat a read with a tag inside as a concatemer. discard: it goes whole to demux_unassigned.fastq with status mid_tag. split: it is cut at the tags and every piece is demultiplexed once more (pieces are named <read>/p<k>). Writes <outfolder>/demux_concatemers.tsv and extra lines in demux_summary.tsv (default off)')
+    p.add_argument('--demux_mid_max_ed', type=int, default=None, help='extension: largest edit distance at which a tag counts as found inside a read (default: by tag length, 1 from 13 bases, 2 from 16, 3 from 24, 0 below - profiles/demux.txt)')
     p.add_argument('--reference_db', type=str, default=None, help='extension: FASTA of reference barcodes (BOLD, UNITE, SILVA, ...). Every final consensus (the polished one with --racon, else the draft) is searched in it on the GPU by shared minimizers, both strands, and its best candidates are verified by alignment; writes <outfolder>/classification.tsv (consensus_id n_reads rank reference strand shared identity aln_cols n_match q_cov r_cov called header; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/classification_all.tsv). Needs --consensus')
     from . import classify as _classify
     _classify.add_flags(p)
@@ -245,6 +247,12 @@ def cli(argv=None):
             logging.error("--demux_sheet %s is not a file." % args.demux_sheet); sys.exit(1)
         if not 1 <= args.demux_window <= 256 or args.demux_max_ed < 0 or args.demux_min_margin < 0:
             logging.error("--demux_window must be 1..256, --demux_max_ed and --demux_min_margin must not be negative."); sys.exit(1)
+        if args.demux_mid_max_ed is not None and args.demux_mid_max_ed < 0:
+            logging.error("--demux_mid_max_ed must not be negative."); sys.exit(1)
+        if args.demux_mid_max_ed is not None and args.demux_mid_tags == 'off':
+            logging.error("--demux_mid_max_ed is the edit bound of --demux_mid_tags discard | split."); sys.exit(1)
+    elif getattr(args, "demux_mid_tags", "off") != 'off' or getattr(args, "demux_mid_max_ed", None) is not None:
+        logging.error("--demux_mid_tags and --demux_mid_max_ed need --demux_sheet."); sys.exit(1)
     if getattr(args, "reference_db", None):
         if not args.consensus:
             logging.error("--reference_db classifies consensus sequences: it needs --consensus."); sys.exit(1)

@@ -3,6 +3,9 @@
 The library locates every sample tag in both end windows of every read and returns integers.  Which read goes to which sample - the sheet, the margin
 between the best and the second-best tag, the strand rule, the cuts - is decided here, and the files a demultiplexer leaves are written here:
 <outfolder>/demux/<sample>.fastq, <outfolder>/demux_unassigned.fastq, <outfolder>/demux_summary.tsv.
+
+`--demux_mid_tags discard | split`: the whole read is scanned for the sheet's tags on both strands (ngsid_demux_scan, csrc/k_demux_scan.hip); a read with a tag inside
+is a concatemer and is discarded or cut into pieces that are demultiplexed once more (+ <outfolder>/demux_concatemers.tsv).
 """
 from __future__ import annotations
 import ctypes as C
@@ -170,6 +173,151 @@ def write_outputs(outfolder, sheet: Sheet, names, rs: ReadSet, hits, result, kee
     return folder
 
 
+# ---- tags inside reads (`--demux_mid_tags`): the policy on top of ngsid_demux_scan (include/ngsid_demux.h, csrc/k_demux_scan.hip)
+ST_MID_TAG = 5
+MID_STATUS_NAME = "mid_tag"
+MID_MODES = ("off", "discard", "split")
+_TAG_COMPLEMENT = dict(zip("ACGTMKRYBVDHWSNX", "TGCAKMYRVBHDWSNX"))
+
+
+def revcomp_tag(tag: str) -> str:
+    """reverse complement over the tag alphabet: M-K, R-Y, B-V, D-H; W, S, N and X are their own complements"""
+    return "".join(_TAG_COMPLEMENT[c] for c in reversed(tag))
+
+
+def scan_patterns(sheet: Sheet):
+    """the patterns of the scan: pattern t = tag t, pattern T + t = its reverse complement"""
+    return list(sheet.tags) + [revcomp_tag(t) for t in sheet.tags]
+
+
+def default_mid_max_ed(m: int) -> int:
+    """the edit bound of an interior hit of a tag of m letters when --demux_mid_max_ed is not given.  The sweep of tools/demux_scan_sweep.py (profiles/demux.txt) settled
+    1 at 13, 2 at 16 and 3 at 24 bases: per tag length the bound with the highest recall on planted concatemers among those at which no clean read had an interior hit.
+    A length between two of the sweep takes the bound of the shorter one, a tag below 13 bases counts only as an exact copy."""
+    return 3 if m >= 24 else 2 if m >= 16 else 1 if m >= 13 else 0
+
+
+def interior_hits(hit_off, hits, pattern_len, lens, cut0, cut1, mid_max_ed):
+    """the hits of Api.demux_scan that lie inside the read, away from its own end tags -> bool [H].
+
+    A hit (pattern, end e, ed d) of a pattern of m letters in a read of L letters whose end tags were cut at cut0 / cut1 (assign() on the whole read; 0 where an end
+    carries no tag) is interior iff d <= mid_max_ed, e - m - d + 1 >= cut0 and e < L - cut1.  mid_max_ed: one bound, or one per pattern."""
+    hit_off = np.asarray(hit_off, dtype=np.int64); h = np.asarray(hits, dtype=np.int64).reshape(-1, 3)
+    read = np.repeat(np.arange(len(hit_off) - 1), np.diff(hit_off))
+    m = np.asarray(pattern_len, dtype=np.int64)[h[:, 0]]
+    bound = np.broadcast_to(np.asarray(mid_max_ed, dtype=np.int64), (len(pattern_len),))[h[:, 0]] if np.ndim(mid_max_ed) else int(mid_max_ed)
+    L = np.asarray(lens, dtype=np.int64)[read]; c0 = np.asarray(cut0, dtype=np.int64)[read]; c1 = np.asarray(cut1, dtype=np.int64)[read]
+    e, d = h[:, 1], h[:, 2]
+    return (d <= bound) & (e - m - d + 1 >= c0) & (e < L - c1)
+
+
+def hit_cuts(hits, pattern_len, n_tags):
+    """the cuts of interior hits [k, 3], sorted and distinct: a forward pattern (index < n_tags) starts an amplicon to its right - cut before it, at max(e - m - d + 1, 0),
+    never behind its true start; a reverse-complement pattern ends an amplicon to its left - cut behind it, at e + 1"""
+    h = np.asarray(hits, dtype=np.int64).reshape(-1, 3)
+    m = np.asarray(pattern_len, dtype=np.int64)[h[:, 0]]
+    return np.unique(np.where(h[:, 0] < int(n_tags), np.maximum(h[:, 1] - m - h[:, 2] + 1, 0), h[:, 1] + 1))
+
+
+def pieces_of(cuts, L):
+    """[(a, b)]: the non-empty intervals of [0, L) between the sorted distinct cuts"""
+    edges = np.unique(np.concatenate(([0, int(L)], np.clip(np.asarray(cuts, dtype=np.int64), 0, int(L)))))
+    return [(int(a), int(b)) for a, b in zip(edges[:-1], edges[1:])]
+
+
+def piece_name(header: str, k: int) -> str:
+    """the header of piece k (1-based, left to right): /p<k> behind the first word"""
+    for i, c in enumerate(header):
+        if c in " \t":
+            return "%s/p%d%s" % (header[:i], k, header[i:])
+    return "%s/p%d" % (header, k)
+
+
+def find_concatemers(api, work: ReadSet, sheet: Sheet, result, mid_max_ed=None):
+    """scan the whole reads for the sheet's tags on both strands -> dict(reads [c] (indices of the reads with an interior hit, ascending), hits (list of [k, 3] arrays,
+    the interior hits of each), pattern_len, patterns)"""
+    pats = scan_patterns(sheet)
+    plen = np.array([len(p) for p in pats], dtype=np.int64)
+    bound = np.array([default_mid_max_ed(m) for m in plen], dtype=np.int64) if mid_max_ed is None else np.full(len(pats), int(mid_max_ed), dtype=np.int64)
+    hit_off, hits = api.demux_scan(work, pats, max_ed=int(bound.max()), iupac=True)
+    lens = np.diff(work.off.astype(np.int64))
+    inner = interior_hits(hit_off, hits, plen, lens, result[3], result[4], bound)
+    read = np.repeat(np.arange(work.n), np.diff(hit_off.astype(np.int64)))[inner]                  # ascending: the hits are grouped by read
+    reads, first = np.unique(read, return_index=True)
+    return dict(reads=reads, hits=np.split(hits[inner], first[1:]) if len(reads) else [], pattern_len=plen, patterns=pats)
+
+
+def cut_pieces(names, rs: ReadSet, work: ReadSet, conc, n_tags):
+    """the pieces of the reads conc["reads"] -> (piece names (list), piece read set with the original letters and qualities, the same with the searched letters,
+    owner [p] = position of the piece's read in conc["reads"])"""
+    off = rs.off.astype(np.int64)
+    pn, seq, wseq, qual, owner = [], [], [], [], []
+    for c, (r, h) in enumerate(zip(conc["reads"].tolist(), conc["hits"])):
+        a0, L = int(off[r]), int(off[r + 1] - off[r])
+        for k, (a, b) in enumerate(pieces_of(hit_cuts(h, conc["pattern_len"], n_tags), L), 1):
+            pn.append(piece_name(names.get(r), k)); owner.append(c)
+            seq.append(rs.seq[a0 + a:a0 + b]); wseq.append(work.seq[a0 + a:a0 + b])
+            qual.append(rs.qual[a0 + a:a0 + b] if rs.qual is not None else np.full(b - a, ord("I"), dtype=np.uint8))
+    poff = np.zeros(len(seq) + 1, dtype=np.uint64)
+    if seq:
+        poff[1:] = np.cumsum([len(s) for s in seq])
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs)) if xs else np.zeros(0, dtype=np.uint8)
+    q = cat(qual)
+    return pn, ReadSet(cat(seq), q, poff), ReadSet(cat(wseq), q, poff), np.array(owner, dtype=np.int64)
+
+
+def write_outputs_mid(outfolder, sheet: Sheet, names, rs: ReadSet, hits, result, mode, conc, pieces=None, keep_tags=False):
+    """the outputs of write_outputs with `--demux_mid_tags discard | split`: reads with an interior hit get status 5 (mid_tag).  discard: they go whole to
+    demux_unassigned.fastq.  split: they are written nowhere; their pieces (pieces = (piece names, piece read set, hits and assign() result of the pieces, owner)) join
+    their sample's file behind the whole reads, in input order, or demux_unassigned.fastq.  + demux_concatemers.tsv and the concatemer lines of demux_summary.tsv.
+    -> (folder of the sample files, dict of the concatemer counts)"""
+    sample, strand, status, cut0, cut1 = [np.array(x) for x in result]
+    cr = conc["reads"]
+    sample[cr] = -1; strand[cr] = -1; status[cr] = ST_MID_TAG
+    folder = write_outputs(outfolder, sheet, names, rs, hits, (sample, strand, status, cut0, cut1), keep_tags=keep_tags)
+    psample = np.zeros(0, dtype=np.int32); owner = np.zeros(0, dtype=np.int64)
+    if mode == "split":
+        pnames, prs, phits, presult, owner = pieces
+        psample = presult[0]
+        # the unassigned file holds the whole reads without a sample, the concatemers left out, then the pieces without one
+        fastio.write_fastq(os.path.join(outfolder, "demux_unassigned.fastq"), np.flatnonzero((sample < 0) & (status != ST_MID_TAG)), names, rs)
+        if len(pnames):
+            pn = fastio.Names.from_list(pnames)
+            out = prs if keep_tags else _trimmed(prs, presult[3], presult[4], psample >= 0)
+            for s, name in enumerate(sheet.samples):
+                idx = np.flatnonzero(psample == s)
+                if len(idx):
+                    fastio.write_fastq(os.path.join(folder, name + ".fastq"), idx, pn, out, append=True)
+            fastio.write_fastq(os.path.join(outfolder, "demux_unassigned.fastq"), np.flatnonzero(psample < 0), pn, out, append=True)
+    lens = np.diff(rs.off.astype(np.int64))
+    T = len(sheet.tags)
+    pat_name = lambda p: sheet.tags[p] if p < T else sheet.tags[p - T] + "/rc"
+    first_word = lambda h: h.split()[0] if h.split() else h
+    piece_at = np.searchsorted(owner, np.arange(len(cr) + 1))                                        # owner is ascending: the pieces of concatemer c are piece_at[c] .. piece_at[c + 1]
+    one = many = 0
+    with open(os.path.join(outfolder, "demux_concatemers.tsv"), "w") as fh:
+        fh.write("#read\tlength\tpieces\thits\tpiece_samples\n")
+        for c, (r, h) in enumerate(zip(cr.tolist(), conc["hits"])):
+            mine = psample[piece_at[c]:piece_at[c + 1]]
+            npieces = len(mine) if mode == "split" else len(pieces_of(hit_cuts(h, conc["pattern_len"], T), int(lens[r])))
+            got = np.unique(mine[mine >= 0])
+            one += len(got) == 1; many += len(got) > 1
+            fh.write("%s\t%d\t%d\t%s\t%s\n" % (first_word(names.get(r)), int(lens[r]), npieces,
+                                               ",".join("%s:%d:%d" % (pat_name(int(p)), int(e), int(d)) for p, e, d in h.tolist()),
+                                               ",".join(sheet.samples[s] if s >= 0 else "-" for s in mine.tolist()) if mode == "split" else "-"))
+    counts = dict(concatemers=int(len(cr)), pieces=int(len(psample)), pieces_assigned=int((psample >= 0).sum()), one_sample=int(one), several_samples=int(many))
+    with open(os.path.join(outfolder, "demux_summary.tsv"), "a") as fh:
+        if len(cr):
+            fh.write("status=%d\t%s\t%d\n" % (ST_MID_TAG, MID_STATUS_NAME, len(cr)))
+        fh.write("#mid_tags\tmeaning\tcount\n")
+        fh.write("mid_tags=%s\treads_with_interior_hits\t%d\n" % (mode, counts["concatemers"]))
+        fh.write("mid_tags=%s\tpieces_made\t%d\n" % (mode, counts["pieces"]))
+        fh.write("mid_tags=%s\tpieces_assigned\t%d\n" % (mode, counts["pieces_assigned"]))
+        fh.write("mid_tags=%s\tconcatemers_with_pieces_of_one_sample\t%d\n" % (mode, counts["one_sample"]))
+        fh.write("mid_tags=%s\tconcatemers_with_pieces_of_several_samples\t%d\n" % (mode, counts["several_samples"]))
+    return folder, counts
+
+
 def run(args, api):
     """the `--demux_sheet` step of the command line: ingest the pooled file once, locate, assign, write -> (folder of the sample files, summary dict)"""
     from time import time
@@ -187,8 +335,28 @@ def run(args, api):
     hits = api.demux_locate(work, sheet.tags, window=args.demux_window, max_ed=args.demux_max_ed, iupac=True) if rs.n else np.zeros((0, 2, 5), np.int32)
     T["demux_locate"] = time() - t0; t0 = time()
     result = assign(hits, sheet, args.demux_min_margin, lens=np.diff(rs.off.astype(np.int64)))
-    folder = write_outputs(args.outfolder, sheet, names, rs, hits, result, keep_tags=bool(getattr(args, "demux_keep_tags", False)))
+    keep_tags = bool(getattr(args, "demux_keep_tags", False))
+    mode = getattr(args, "demux_mid_tags", None) or "off"
+    if mode == "off":
+        folder = write_outputs(args.outfolder, sheet, names, rs, hits, result, keep_tags=keep_tags)
+        T["demux_write"] = time() - t0
+        n_assigned = int((result[0] >= 0).sum())
+        logging.info("Demultiplexed %d reads: %d assigned to %d of %d samples" % (rs.n, n_assigned, len(np.unique(result[0][result[0] >= 0])), len(sheet.samples)))
+        return folder, dict(reads=int(rs.n), assigned=n_assigned, timings=T)
+    # ---- tags inside the reads: scan, then discard the reads that carry one or split them and send the pieces through locate + assign once more (pieces are not scanned again)
+    empty = dict(reads=np.zeros(0, dtype=np.int64), hits=[], pattern_len=np.array([len(p) for p in scan_patterns(sheet)], dtype=np.int64), patterns=scan_patterns(sheet))
+    conc = find_concatemers(api, work, sheet, result, getattr(args, "demux_mid_max_ed", None)) if rs.n else empty
+    T["demux_scan"] = time() - t0; t0 = time()
+    pieces = None
+    if mode == "split":
+        pnames, prs, pwork, owner = cut_pieces(names, rs, work, conc, len(sheet.tags))
+        phits = api.demux_locate(pwork, sheet.tags, window=args.demux_window, max_ed=args.demux_max_ed, iupac=True) if prs.n else np.zeros((0, 2, 5), np.int32)
+        pieces = (pnames, prs, phits, assign(phits, sheet, args.demux_min_margin, lens=np.diff(prs.off.astype(np.int64))), owner)
+        T["demux_locate_pieces"] = time() - t0; t0 = time()
+    folder, counts = write_outputs_mid(args.outfolder, sheet, names, rs, hits, result, mode, conc, pieces, keep_tags=keep_tags)
     T["demux_write"] = time() - t0
-    n_assigned = int((result[0] >= 0).sum())
-    logging.info("Demultiplexed %d reads: %d assigned to %d of %d samples" % (rs.n, n_assigned, len(np.unique(result[0][result[0] >= 0])), len(sheet.samples)))
-    return folder, dict(reads=int(rs.n), assigned=n_assigned, timings=T)
+    whole = np.array(result[0]); whole[conc["reads"]] = -1
+    n_assigned = int((whole >= 0).sum())
+    logging.info("Demultiplexed %d reads: %d assigned to %d of %d samples; %d reads with a tag inside (%s): %d pieces, %d assigned"
+                 % (rs.n, n_assigned, len(np.unique(whole[whole >= 0])), len(sheet.samples), counts["concatemers"], mode, counts["pieces"], counts["pieces_assigned"]))
+    return folder, dict(reads=int(rs.n), assigned=n_assigned, mid_tags=counts, timings=T)

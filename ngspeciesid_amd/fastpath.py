@@ -820,7 +820,8 @@ def _main_samples(args, api):
 
 def _main_demux(args, api):
     """--demux_sheet: the pooled file is split by sample tag (demux.py over ngsid_demux_locate; the pooled reads are neither scored nor sorted), then the sample files
-    run through the --fastq_dir path as they are: <outfolder>/<sample>/ per sample.  --demux_only stops after the demultiplexer's own outputs."""
+    run through the --fastq_dir path as they are: <outfolder>/<sample>/ per sample.  --demux_only stops after the demultiplexer's own outputs.
+    --demux_mid_tags / --demux_mid_max_ed travel with args: demux.run scans the whole reads and discards or splits the concatemers before the sample files are written."""
     import copy
     from . import demux
     os.makedirs(args.outfolder, exist_ok=True)
