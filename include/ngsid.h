@@ -227,6 +227,25 @@ typedef struct {
  * layers only: tile consensuses of the upper levels and the draft consensus are unchanged.  Off by default; without the flag every call is what it was. */
 #define NGSID_ALN_SUBGRAPH 16
 
+/* THE RULES OF ONE POLISHING ITERATION (aln_mode 1 / 2 / 3; tests/polish_reference.py restates them in plain Python), per group:
+ *   strand    once per call, against the INITIAL backbone: the HPC minimizers of the read (ngsid_hpc_minimizers with k' = min(k, 21), w' = max(w, k'); every emitted
+ *             minimizer counts, repeated k-mers each time) found among the minimizers of the backbone = a, among those of its reverse complement (A<->T, C<->G, else N) = b.
+ *             a == b == 0: the read is used in no iteration (record -1 x 6); b > a: minus strand, the read is reverse-complemented (qualities reversed); else plus.
+ *   alignment the oriented read against the CURRENT backbone (ngsid_ed_align_batch rules); aln_mode 3 keeps the columns from the first to the last run of >= 15 equal columns.
+ *             The PAF record covers the first to the last kept match / mismatch column and is written whether or not the filters below drop the read.
+ *   windows   n = 1 for a backbone of at most `window` bases, else ceil(length / window), minus one when the last would be shorter than window / 10 (integer division):
+ *             that tail joins the window before it.  Window w < n - 1 has `window` bases, the last one the rest.  A column at backbone position t belongs to window min(t / window, n - 1).
+ *   filters   with qs / ts = read / backbone span of the kept columns, mn / mx the smaller / larger: the read is dropped when 1.0 - (double)mn / mx > error_threshold.
+ *             Layer of (read, window) = read bases from the first to the last kept match / mismatch column of the window; dropped when its length < 0.02 * window, or, with
+ *             qualities, when sum(q - 33) / length < quality_threshold.
+ *   mode      begin / end = backbone position of the layer's first / last column relative to the window, offset = (int)(0.01 * window length): NGSID_POA_GLOBAL when
+ *             begin < offset && end > window length - offset, else NGSID_POA_SEMI (or the sub-graph rule above).
+ *   graph     a window with fewer than two layers keeps its backbone slice.  Else: the backbone slice first (every base weight 0, counted in no coverage), then the layers in
+ *             ascending `begin`, equal ones in listed read order; base weights q - 33, or 1 without qualities; result = heaviest bundle.
+ *   trim      (one graph per window) n = layers of the window; trim 2 always, trim 1 / 3 when the mean length of the group's LISTED reads > 1000.0, trim 0 never: keep [b, e],
+ *             b / e the first / last base with coverage >= n / 2 (integer division), when b < e; else keep everything.
+ *   result    the concatenation of the window results is the next backbone; n_used = reads with at least one layer. */
+
 /* (a16,a17) replaces run_racon's (minimap2 -> racon) x racon_iter chain (consensus.py:107-126).
  * backbones: one sequence per group (qual ignored); reads grouped like ngsid_poa_consensus; a read may be listed under ONE group only
  * (NGSID_ERR_ARG otherwise: orientation and window layers are kept per read).

@@ -36,6 +36,10 @@ one - from the graph and the scores alone, before any other implementation's out
               an ancestor nor a descendant of the node being completed it is the order that says whether it is scored again.  The completion is run
               with none and with all of those nodes scored again; two different consensus paths = undecided.
 After the first undecided event the rest of the group is computed along the first traceback found (the result is not used for comparisons).
+
+Hooks for polish_reference.py (a polishing window is such a graph with the backbone in front), all off by default: add_sequence(counted=False) - a first sequence
+that no coverage counts; align(within=nodes) with subgraph_nodes() - an alignment that sees a node set only (global to racon's sub-graph of a layer);
+heaviest_bundle(chain_ties=True) - a maximum repeated along one simple chain is no tie.
 """
 from collections import deque
 import numpy as np
@@ -84,8 +88,9 @@ class Graph:
             if self.letter[u] == c: return u
         return ("new", min(self.sib[v]))
 
-    def add_sequence(self, s, w, outcome):
-        """s: bytes, w: per-base weights, outcome: {position: label} of the aligned bases"""
+    def add_sequence(self, s, w, outcome, counted=True):
+        """s: bytes, w: per-base weights, outcome: {position: label} of the aligned bases; counted=False: a sequence that no coverage counts (the zero-weight
+        backbone of a polishing window, polish_reference.py)"""
         prev = None
         for i, c in enumerate(s):
             lab = outcome.get(i)
@@ -93,12 +98,12 @@ class Graph:
             elif isinstance(lab, tuple): y = self.new_node(c, sibling_of=lab[1])
             else:
                 y = lab; assert self.letter[y] == c
-            self.count[y] += 1
+            if counted: self.count[y] += 1
             if prev is not None: self.add_edge(prev, y, int(w[i - 1]) + int(w[i]))
             prev = y
 
 
-def score_matrix(G, s, mode, m, n, g, order):
+def score_matrix(G, s, mode, m, n, g, order, within=None):
     V, L = len(G.letter), len(s)
     sv = np.frombuffer(s, dtype=np.uint8)
     H = np.full((V, L + 1), NEG, dtype=np.int64)
@@ -106,10 +111,11 @@ def score_matrix(G, s, mode, m, n, g, order):
     sc_of = {}
     a = np.empty(L + 1, dtype=np.int64)
     for v in order:
+        if within is not None and v not in within: continue
         c = G.letter[v]
         if c not in sc_of: sc_of[c] = np.where(sv == c, m, n).astype(np.int64)
         sc = sc_of[c]
-        preds = list(G.inn[v])
+        preds = [u for u in G.inn[v] if within is None or u in within]
         pm = None
         if len(preds) == 1: pm = H[preds[0]]
         elif preds: pm = H[preds].max(axis=0)
@@ -130,17 +136,31 @@ def score_matrix(G, s, mode, m, n, g, order):
     return H
 
 
-def align(G, s, mode, m, n, g, enumerate_all=True):
-    """-> (outcome {position: label}, decided)"""
+def subgraph_nodes(G, a0, a1):
+    """racon's sub-graph of a layer that spans the backbone positions [a0, a1] of a window graph whose FIRST sequence is the backbone (backbone position = node id):
+    every node reached backwards - through in-edges and aligned siblings - from backbone node a1 without entering a backbone node below a0"""
+    inside, stack = set(), [a1]
+    while stack:
+        v = stack.pop()
+        if v in inside or v < a0: continue
+        inside.add(v)
+        stack.extend(G.inn[v]); stack.extend(G.sib[v])
+    return inside
+
+
+def align(G, s, mode, m, n, g, enumerate_all=True, within=None):
+    """-> (outcome {position: label}, decided).  within (a set of nodes, polish_reference.py): the alignment sees those nodes only - edges from and to other
+    nodes do not exist for it, so nodes without a predecessor / successor INSIDE are its sources / ends (GLOBAL to a sub-graph)"""
     V, L = len(G.letter), len(s)
     order = G.topo()
-    H = score_matrix(G, s, mode, m, n, g, order)
+    H = score_matrix(G, s, mode, m, n, g, order, within)
     if mode == LOCAL:
         best = int(H.max())
         if best <= 0: return {}, True
         ends = [(int(v), int(j)) for v, j in np.argwhere(H == best)]
     else:
-        cand = [v for v in range(V) if not G.out[v]] if mode == GLOBAL else list(range(V))
+        inside = range(V) if within is None else sorted(within)
+        cand = [v for v in inside if not any(within is None or x in within for x in G.out[v])] if mode == GLOBAL else list(inside)
         col = H[cand, L]; best = int(col.max())
         assert best > NEG // 2
         ends = [(cand[int(k)], L) for k in np.nonzero(col == best)[0]]
@@ -161,7 +181,7 @@ def align(G, s, mode, m, n, g, enumerate_all=True):
         h = int(H[v, j])
         if mode == LOCAL and h == 0:
             finals.append(oid); continue
-        preds = G.inn[v]
+        preds = G.inn[v] if within is None else [u for u in G.inn[v] if u in within]
         nxt = []; fin = []
         if j >= 1:
             scv = m if G.letter[v] == s[j - 1] else n
@@ -188,7 +208,7 @@ def align(G, s, mode, m, n, g, enumerate_all=True):
         branches += max(0, new + len(fin) - 1)
         if branches > PATH_CAP:
             over = True; break
-    if over: return align(G, s, mode, m, n, g, enumerate_all=False)[0], False
+    if over: return align(G, s, mode, m, n, g, enumerate_all=False, within=within)[0], False
     outs = set(finals)
     oid = finals[0]; outcome = {}
     while oid:
@@ -210,8 +230,17 @@ def _relatives(G, start):
     return anc, desc
 
 
-def heaviest_bundle(G, info=None):
-    """-> (list of consensus nodes, decided); info (a dict) receives the number of branch completions"""
+def _one_chain(G, nodes):
+    """nodes (in topological order) form a simple chain: each one's only out-edge leads to the next, whose only in-edge it is"""
+    return all(G.out[a] == [b] and list(G.inn[b]) == [a] for a, b in zip(nodes, nodes[1:]))
+
+
+def heaviest_bundle(G, info=None, chain_ties=False):
+    """-> (list of consensus nodes, decided); info (a dict) receives the number of branch completions.
+    chain_ties (polish_reference.py; off = the behaviour of every other caller): a maximum score attained by several nodes is no tie when those nodes form one
+    simple chain.  Zero-weight edges make that the rule in a polishing window whose layers stop short of the backbone's end: every backbone node behind the
+    last supported one repeats its score.  Whichever of them takes over, the completion loop goes on from it to the same sink along the same edges - and a
+    completion at a node whose successor has no other predecessor invalidates nothing and scores every node behind it as before - so the consensus is the same."""
     order = G.topo()
     V = len(order); score = [-1] * V; pred = [-1] * V
     decided = True
@@ -244,12 +273,14 @@ def heaviest_bundle(G, info=None):
             if v == start or v in anc or (v not in desc and not rescore_others): continue
             tie |= take(v, sc, pr, True); cand.append(v)
         top = max(sc[v] for v in cand)
-        tie |= sum(1 for v in cand if sc[v] == top) > 1
+        tied = [v for v in cand if sc[v] == top]
+        tie |= len(tied) > 1 and not (chain_ties and _one_chain(G, tied))
         return sc, pr, next(v for v in cand if sc[v] == top), tie
 
     for v in order: decided &= not take(v, score, pred, False)
     top = max(score)
-    if sum(1 for x in score if x == top) > 1: decided = False
+    tied = [v for v in order if score[v] == top]
+    if len(tied) > 1 and not (chain_ties and _one_chain(G, tied)): decided = False
     mx = next(v for v in order if score[v] == top)
     while G.out[mx]:
         anc, desc = _relatives(G, mx)
