@@ -24,8 +24,9 @@ extern "C" {
  * Legal: empty sets, one sequence, sequences of length 0 (ed("", x) = |x|), identical sequences (distance 0), a sequence equal to its own reverse complement (strand 0).
  * Bounds: every sequence has at most NGSID_MAX_CONSENSUS_LEN bases; fewer than 2^32 sequences per set; 0 <= max_dist <= NGSID_NEAR_MAX_DIST.
  * Read sets are host- or device-resident (qual ignored); every other array is a host array.
- * Scratch (grow-only, in the context; returned by option "release_scratch"): the letter planes of the sequences (nine bits per base and a few words per sequence) and
- * the found pairs.  Work runs in chunks: option "near_chunk_pairs" fixes the listed pairs per launch of ngsid_ed_within_batch, option "near_chunk_seqs" the sequences
+ * Scratch (grow-only, in the context; returned by option "release_scratch"): the letter planes a call reads - pattern planes of the queries (three bits per base and
+ * 78 words per sequence, padded for the widest band of the wide calls) and text planes of the targets (six bits per base: both strands), both kinds for the set of
+ * ngsid_near_pairs - and the found pairs (ten bytes each).  Work runs in chunks: option "near_chunk_pairs" fixes the listed pairs per launch of ngsid_ed_within_batch, option "near_chunk_seqs" the sequences
  * (rows of the pair triangle) per launch of ngsid_near_pairs; by default the chunks are sized from the launch limits and from a share of the free device memory.
  * Results never depend on it.
  * Profiling lines (ngsid_profile_read): k_near_check, k_near_pack, k_near_within, k_near_tiles.
@@ -46,8 +47,8 @@ int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_
 
 /* The wide calls: the two calls above, word for word - D, the strand and tie rule, N, empty sequences, the ascending (i, j) order, the cap / needed protocol, the options
  * and the error codes - with the range 0 <= max_dist <= NGSID_NEAR_WIDE_MAX_DIST.  The band is 2, 4 or 8 words per lane, the smallest that holds max_dist (63, 127,
- * 255 edits); for max_dist <= NGSID_NEAR_MAX_DIST they run the one-word kernels and return exactly what the calls above return.  Scratch: one more pattern variant
- * per sequence, padded for the widest band.  Profiling lines: k_near_within_wide, k_near_tiles_wide; k_near_check and k_near_pack are shared. */
+ * 255 edits); for max_dist <= NGSID_NEAR_MAX_DIST they run the one-word instance, as the calls above do, and return exactly what those return.  Scratch: the
+ * same planes and records.  Profiling lines above NGSID_NEAR_MAX_DIST: k_near_within_wide, k_near_tiles_wide; k_near_check and k_near_pack are shared. */
 int32_t ngsid_ed_within_wide_batch(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets,
                                    const uint32_t* q_idx /* [n_pairs] */, const uint32_t* t_idx /* [n_pairs] */, uint64_t n_pairs,
                                    int32_t max_dist, uint32_t flags, int32_t* dist /* [n_pairs] */, uint8_t* strand /* [n_pairs], may be NULL */);

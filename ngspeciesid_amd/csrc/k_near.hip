@@ -1,231 +1,158 @@
-// k_near.hip - ngsid_ed_within_batch / ngsid_near_pairs (include/ngsid_near.h): the unit-cost edit distance of pairs that are at most 31 edits apart, on both strands,
-// for listed pairs and for all pairs of a set.
+// k_near.hip - ngsid_ed_within_batch / ngsid_near_pairs and their wide twins (include/ngsid_near.h): the unit-cost edit distance of pairs that are at most max_dist edits
+// apart, on both strands, for listed pairs and for all pairs of a set.  max_dist <= 31 with the plain calls, <= 255 with the wide ones.
 //
-// One pair per lane, one band word per lane: the diagonal-band form of Myers' bit-vector recurrence (Hyyro 2003).  In column c (1-based) of the DP matrix of a pattern
-// (rows) against a text (columns), bit r of a 64-bit word is row c - 31 + r, so a diagonal keeps its bit from column to column and the cell (m, n) sits at bit
-// 31 - (n - m).  VP / VN hold the vertical deltas of the column before, already aligned to the rows of the column that is computed: the band slides one row per column
-// by the one shift D0 >> 1.  Row c + 32 was outside the band one column earlier; its delta is taken as +1 (bit 63 of VP), which can only raise a value.  Rows <= 0 are
-// virtual rows that match nothing and hold D[i][c] = c (VP = VN = 0 there), rows behind the pattern's end match nothing.  Every band value is the cost of a real
-// alignment, so it is >= the full DP's, and equal to it where that is <= 31: a path of cost <= 31 stays within 31 diagonals of the main one.
-// The value on the diagonal of (m, n) is tracked from column 0 on (start max(m - n, 0), + 1 wherever D0 has a zero there).  Values never decrease along a diagonal, so
-// a lane leaves the loop as soon as the tracked value exceeds its bound: pairs with |n - m| above it never enter, unrelated pairs leave after a few dozen columns, a wave
-// stops when its last lane has.  The reverse strand runs after the forward one with the bound forward - 1 (a tie goes to forward), not at all behind a forward 0.
+// One pair per lane, W band words per lane, W = 1, 2, 4 or 8, the smallest that holds max_dist: the diagonal-band form of Myers' bit-vector recurrence (Hyyro 2003) on a
+// band of B = 64 W bits, H = B / 2 - 1 = 32 W - 1.  In column c (1-based) of the DP matrix of a pattern (rows) against a text (columns), bit r of the band is row
+// c - H + r (word j holds bits 64 j .. 64 j + 63), so a diagonal keeps its bit from column to column and the cell (m, n) sits at bit H - (n - m).  VP / VN hold the
+// vertical deltas of the column before, already aligned to the rows of the column that is computed: the band slides one row per column by the one shift D0 >> 1, which
+// takes its top bit from the next word.  Row c + H + 1 was outside the band one column earlier; its delta is taken as +1 (the top bit of VP's top word), which can only
+// raise a value.  Rows <= 0 are virtual rows that match nothing and hold D[i][c] = c (VP = VN = 0 there: VP starts as ones from bit H up), rows behind the pattern's end
+// match nothing.  The sum (Eq & VP) + VP carries from word to word.  Every band value is the cost of a real alignment, so it is >= the full DP's, and equal to it where
+// that is <= H: a path of cost <= H stays within H diagonals of the main one.  That is why a band of W words is exact up to 32 W - 1 edits (31, 63, 127, 255).
+// The value on the diagonal of (m, n) is tracked from column 0 on (start max(m - n, 0), + 1 wherever D0 has a zero there).  Its bit lies in word (H - (n - m)) >> 6,
+// which differs from lane to lane: the word is picked by a compare / select chain over the W words, never by indexing the register array (that would send the band to
+// scratch); at W = 1 the chain is empty.  Values never decrease along a diagonal, so a lane leaves the loop as soon as the tracked value exceeds its bound: pairs with
+// |n - m| above it never enter, unrelated pairs leave after a few dozen columns, a wave stops when its last lane has.  The reverse strand runs after the forward one with
+// the bound forward - 1 (a tie goes to forward), not at all behind a forward 0.
 //
-// No LDS and no traceback.  k_near_pack turns every sequence into three bit planes of its letters' codes (A C G T N = 0 .. 4, 7 outside the sequence: equals nothing),
-// in three variants: PATTERN (base p at bit p + 31: the window of column c + 1 starts at bit c), TEXT (base p at bit p) and TEXT_RC (the complement of base
-// len - 1 - p at bit p: rc(b) is never materialised).  A lane loads three pattern words and three text words per 32 columns; per column the three 64-bit pattern windows
-// are funnel shifts of register pairs, the text letter is three 0 / -1 masks, and Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2)): N by the planes, not by a branch.
-// tests/variants_band_model.py runs the same loop on Python ints, word for word.
+// No LDS and no traceback.  k_near_pack turns a sequence into bit planes of its letters' codes (A C G T N = 0 .. 4, 7 outside the sequence: equals nothing), one layout
+// per role.  Pattern planes: three planes, base p at bit p + 255, padded once for the widest band, so that the window of column c + 1 of a W-word band starts at bit
+// c + 32 (8 - W), a whole number of words in, and one layout serves every W.  Text planes: three planes TEXT (base p at bit p) and three TEXT_RC (the complement of base
+// len - 1 - p at bit p: rc(b) is never materialised).  The three planes of a kind are interleaved word by word (word w of plane k at 3 w + k), so what a lane loads
+// for a block of 32 columns is contiguous.  A call packs only what it reads.  A lane keeps 2 W + 1 pattern words per plane in registers, slides them by one word per
+// 32 columns and loads the word that enters, and the next text word, one block ahead.  Per column the windows are v_alignbit_b32 of two neighbouring words: unlike a
+// 64-bit shift it takes any two registers, so a word that is the high half of one window and the low half of the next is not copied into a register pair of its own
+// (W = 8, before the planes were interleaved: 151 instead of 241 VGPRs).  The text letter is three 0 / -1 masks, and Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2)): N by the planes, not by a branch.
+// W = 1 has a column loop of its own inside near_band_ed (the same planes, records and kernels): with the general loop k_near_tiles<1> and k_near_within<1> measured
+// 2 - 3 % slower than with it.  tests/variants_band_model.py runs both loops on Python ints, word for word, for every W.
 //
-// k_near_within: lane = listed pair (pattern = query, text = target).
-// k_near_tiles: the set sorted by length on the host; wave = tile = sequence x (sorted position) against 64 of the sequences behind it; the tiles of x end at hi[x],
+// k_near_within<W>: lane = listed pair (pattern = query, text = target).
+// k_near_tiles<W>: the set sorted by length on the host; wave = tile = sequence x (sorted position) against 64 of the sequences behind it; the tiles of x end at hi[x],
 //   the last sequence at most max_dist bases longer: the length bound removes whole tiles, and the lanes of a wave see lengths within max_dist of each other.  The text is
 //   x, the shorter one, the same for every lane: its words and masks are wave-uniform, and every lane has the same number of columns.  A lane that finds a pair appends
-//   (min, max of the caller's indices | distance, strand) through one counter; the host sorts what came back.
-//
-// The wide calls (ngsid_ed_within_wide_batch / ngsid_near_pairs_wide, max_dist up to 255) run the same recurrence on W band words per lane, W = 2, 4 or 8, the smallest
-// that holds max_dist: B = 64 W bits, H = B / 2 - 1, bit r of the band in column c is row c - H + r, the cell (m, n) sits at bit H - (n - m), and the band holds
-// K = 32 W - 1 edits by the argument above.  The sum (Eq & VP) + VP carries from word to word, D0 >> 1 takes its top bit from the next word, the +1 of the row that
-// enters the band belongs to the top word, VP starts as ones from bit H up.  The tracked bit lies in word (H - (n - m)) >> 6, which differs from lane to lane: it
-// is picked by a compare / select chain over the W words, never by indexing the register array.  k_near_pack_wide writes one more pattern variant per sequence, padded
-// for the widest band (base p at bit p + 255): the window of column c + 1 of a W-word band starts at bit c + 32 (8 - W), a whole number of words in.  A lane keeps
-// 2 W + 1 words per plane, slides them by one word per 32 columns and loads the word that enters one block ahead.  The text planes are the ones above.  Below 32
-// edits the wide calls run the one-word kernels.  tests/variants_wide_band_model.py is the Python-int model.  The found-pair record of k_near_tiles_wide is 16 bits
-// (distance | strand << 15).
+//   (min, max of the caller's indices | a 16-bit record: distance | strand << 15) through one counter; the host sorts what came back.
 #include "ngsid_host.h"
 #include "../../include/ngsid_near.h"
 #include <numeric>
 
 typedef uint64_t u64;
 
-static_assert(NGSID_NEAR_MAX_DIST == 31, "the band of near_band_ed is rows c - 31 .. c + 32");
-#define NEAR_WMAX 8                     // the widest band in words: the wide pattern planes carry 32 * NEAR_WMAX - 1 pad bits
-static_assert(NGSID_NEAR_WIDE_MAX_DIST == 32 * NEAR_WMAX - 1, "the widest band of near_band_ed_wide holds 32 W - 1 edits");
+#define NEAR_WMAX 8                     // the widest band in words: the pattern planes carry 32 * NEAR_WMAX - 1 pad bits
+static_assert(NGSID_NEAR_MAX_DIST == 32 * 1 - 1, "the band of near_band_ed<1> holds 31 edits");
+static_assert(NGSID_NEAR_WIDE_MAX_DIST == 32 * NEAR_WMAX - 1, "the widest band of near_band_ed holds 32 W - 1 edits");
 
 namespace {
 
-#define NEAR_PATTERN 0
+#define NEAR_PATTERN 0                  // the two kinds of planes near_pack writes
 #define NEAR_TEXT 1
-#define NEAR_TEXT_RC 2
 
-// words per plane of a sequence of len bases: its bits, the 31 leading pad bits of the pattern variant, and the two words a window reads ahead
-__host__ __device__ __forceinline__ int near_nw(int len) { return ((len + 31) >> 5) + 3; }
+// words per pattern plane of a sequence of len bases: its bits, the eight pad words in front, and what a lane reads beyond the window's first word for a text up to
+// 32 W - 1 bases longer: 2 W words of the window and the word loaded one block ahead (the farthest read is word ((len + 31) >> 5) + 2 W + 8, see near_band_ed)
+__host__ __device__ __forceinline__ int near_nwp(int len) { return ((len + 31) >> 5) + 3 * NEAR_WMAX + 2; }
+// words per text plane: its bits and the word loaded one block ahead (the farthest read is word ((len - 1) >> 5) + 1 = (len + 31) >> 5; a text of no bases is not read)
+__host__ __device__ __forceinline__ int near_nwt(int len) { return ((len + 31) >> 5) + 1; }
 
 __device__ __forceinline__ int near_code(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
 
-// planes of sequence s: woff[s] * 9 words in, variant v plane k at ((v * 3 + k) * nw)
+// word w of the three planes at base (plane k at base[3 w + k]): bit t holds the code of base p = 32 w + t - shift of seq (L bases), with rc the complement of base L - 1 - p
+__device__ __forceinline__ void near_pack_word(const uint8_t* __restrict__ seq, int L, int w, int shift, bool rc, uint32_t* __restrict__ base)
+{
+    uint32_t b0 = 0, b1 = 0, b2 = 0;
+    for (int t = 0; t < 32; ++t) {
+        const int p = 32 * w + t - shift;
+        int c = 7;
+        if (p >= 0 && p < L) {
+            c = near_code(seq[rc ? L - 1 - p : p]);
+            if (rc && c < 4) c = 3 - c;
+        }
+        b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
+    }
+    base[3 * w] = b0; base[3 * w + 1] = b1; base[3 * w + 2] = b2;
+}
+
+// planes of sequence s, nw words each, the three planes of a kind interleaved word by word.  NEAR_PATTERN: woff[s] * 3 words in.  NEAR_TEXT: woff[s] * 6 words in, TEXT
+// first, TEXT_RC 3 * nw words behind it
 __global__ __launch_bounds__(64)
-void k_near_pack(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, u64 s0, uint32_t* __restrict__ planes)
+void k_near_pack(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, u64 s0, int kind, uint32_t* __restrict__ planes)
 {
     const u64 s = s0 + blockIdx.x;
     const u64 a = off[s];
-    const int L = (int)(off[s + 1] - a), nw = near_nw(L);
-    uint32_t* base = planes + woff[s] * 9;
-    for (int w = threadIdx.x; w < nw; w += 64) {
-        for (int v = 0; v < 3; ++v) {
-            uint32_t b0 = 0, b1 = 0, b2 = 0;
-            for (int t = 0; t < 32; ++t) {
-                const int u = 32 * w + t, p = v == NEAR_PATTERN ? u - 31 : u;
-                int c = 7;
-                if (p >= 0 && p < L) {
-                    c = near_code(seq[a + (v == NEAR_TEXT_RC ? L - 1 - p : p)]);
-                    if (v == NEAR_TEXT_RC && c < 4) c = 3 - c;
-                }
-                b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
-            }
-            base[(size_t)(v * 3 + 0) * nw + w] = b0; base[(size_t)(v * 3 + 1) * nw + w] = b1; base[(size_t)(v * 3 + 2) * nw + w] = b2;
-        }
+    const int L = (int)(off[s + 1] - a);
+    if (kind == NEAR_PATTERN) {
+        const int nw = near_nwp(L);
+        for (int w = threadIdx.x; w < nw; w += 64) near_pack_word(seq + a, L, w, 32 * NEAR_WMAX - 1, false, planes + woff[s] * 3);
+    } else {
+        const int nw = near_nwt(L);
+        uint32_t* base = planes + woff[s] * 6;
+        for (int w = threadIdx.x; w < nw; w += 64) { near_pack_word(seq + a, L, w, 0, false, base); near_pack_word(seq + a, L, w, 0, true, base + (size_t)3 * nw); }
     }
 }
 
-__device__ __forceinline__ uint32_t near_funnel(uint32_t hi, uint32_t lo, int s) { return (uint32_t)((((u64)hi << 32) | lo) >> s); }      // s = 0 .. 31 (one v_lshrrev_b64 of the register pair)
-
-// pat: the PATTERN variant of a sequence of m bases (plane k at pat + k * nwp), txt: a TEXT or TEXT_RC variant of one of n bases -> their edit distance if it is <= K, else -1.
-// Reads pattern words up to ((n - 1) >> 5) + 2 < near_nw(m) (n <= m + 31 behind the length test) and text words up to (n - 1) >> 5 < near_nw(n).
-__device__ __forceinline__ int near_band_ed(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt, int nwt, int m, int n, int K)
-{
-    const int d = n - m;
-    int val = d < 0 ? -d : 0;
-    if (val > K || d > K) return -1;
-    const int sb = 31 - d;
-    u64 VP = ~0ull << 31, VN = 0;
-    for (int c0 = 0; c0 < n; c0 += 32) {
-        const int w = c0 >> 5;
-        const uint32_t a0 = pat[w], a1 = pat[w + 1], a2 = pat[w + 2];
-        const uint32_t b0 = pat[nwp + w], b1 = pat[nwp + w + 1], b2 = pat[nwp + w + 2];
-        const uint32_t c_0 = pat[2 * nwp + w], c_1 = pat[2 * nwp + w + 1], c_2 = pat[2 * nwp + w + 2];
-        const uint32_t t0 = txt[w], t1 = txt[nwt + w], t2 = txt[2 * nwt + w];
-        const int ce = min(32, n - c0);
-        for (int s = 0; s < ce; ++s) {
-            const u64 W0 = ((u64)near_funnel(a2, a1, s) << 32) | near_funnel(a1, a0, s);
-            const u64 W1 = ((u64)near_funnel(b2, b1, s) << 32) | near_funnel(b1, b0, s);
-            const u64 W2 = ((u64)near_funnel(c_2, c_1, s) << 32) | near_funnel(c_1, c_0, s);
-            const u64 T0 = (u64)0 - ((t0 >> s) & 1u), T1 = (u64)0 - ((t1 >> s) & 1u), T2 = (u64)0 - ((t2 >> s) & 1u);
-            const u64 Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2));
-            const u64 D0 = (((Eq & VP) + VP) ^ VP) | Eq | VN;
-            const u64 HP = VN | ~(D0 | VP);
-            const u64 HN = D0 & VP;
-            const u64 D0s = D0 >> 1;
-            VP = HN | ~(D0s | HP) | (1ull << 63);
-            VN = D0s & HP;
-            val += 1 - (int)((D0 >> sb) & 1u);
-            if (val > K) return -1;
-        }
-    }
-    return val;
-}
-
-// forward, then the reverse strand below the forward result -> the distance or -1; *strand = 1 iff the reverse strand is strictly closer
-__device__ __forceinline__ int near_both(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt3, int nwt, int m, int n, int K, bool both, int* strand)
-{
-    int best = near_band_ed(pat, nwp, txt3 + (size_t)(NEAR_TEXT * 3) * nwt, nwt, m, n, K);
-    *strand = 0;
-    if (both && best != 0) {
-        const int r = near_band_ed(pat, nwp, txt3 + (size_t)(NEAR_TEXT_RC * 3) * nwt, nwt, m, n, best < 0 ? K : best - 1);
-        if (r >= 0) { best = r; *strand = 1; }
-    }
-    return best;
-}
-
-__global__ __launch_bounds__(256)
-void k_near_within(const uint64_t* __restrict__ qoff, const uint64_t* __restrict__ qwoff, const uint32_t* __restrict__ qpl, const uint64_t* __restrict__ toff, const uint64_t* __restrict__ twoff,
-                   const uint32_t* __restrict__ tpl, const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ tidx, u64 p0, u64 p1, int K, int both,
-                   int32_t* __restrict__ dist, uint8_t* __restrict__ strand)
-{
-    const u64 p = p0 + (u64)blockIdx.x * 256 + threadIdx.x;
-    if (p >= p1) return;
-    const uint32_t q = qidx[p], t = tidx[p];
-    const int m = (int)(qoff[q + 1] - qoff[q]), n = (int)(toff[t + 1] - toff[t]);
-    const int nwp = near_nw(m), nwt = near_nw(n);
-    int st = 0;
-    const int best = near_both(qpl + qwoff[q] * 9, nwp, tpl + twoff[t] * 9, nwt, m, n, K, both != 0, &st);
-    dist[p] = best;
-    strand[p] = (uint8_t)st;
-}
-
-// rows x = xa .. xa + nrows - 1 (sorted positions); tile T of the launch belongs to the row r with toff[r] <= T < toff[r + 1] and covers y = x + 1 + 64 (T - toff[r]) + lane
-__global__ __launch_bounds__(256)
-void k_near_tiles(const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, const uint32_t* __restrict__ pl, const uint32_t* __restrict__ order, const uint32_t* __restrict__ hi,
-                  const uint64_t* __restrict__ toff, uint32_t xa, uint32_t nrows, u64 ntiles, int K, int both,
-                  u64* __restrict__ key, uint8_t* __restrict__ ds, u64 limit, unsigned long long* counter)
-{
-    const int lane = threadIdx.x & 63;
-    const u64 Tl = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const u64 T = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(Tl >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)Tl);
-    if (T >= ntiles) return;
-    uint32_t lo = 0, up = nrows;                                   // the last r with toff[r] <= T
-    while (up - lo > 1) { const uint32_t mid = lo + (up - lo) / 2; if (toff[mid] <= T) lo = mid; else up = mid; }
-    const uint32_t x = xa + lo;
-    const u64 y64 = (u64)x + 1 + (T - toff[lo]) * 64 + lane;
-    if (y64 > hi[x]) return;
-    const uint32_t y = (uint32_t)y64, ox = order[x], oy = order[y];
-    const int n = (int)(off[ox + 1] - off[ox]), m = (int)(off[oy + 1] - off[oy]);
-    int st = 0;
-    const int best = near_both(pl + woff[oy] * 9, near_nw(m), pl + woff[ox] * 9, near_nw(n), m, n, K, both != 0, &st);
-    if (best < 0) return;
-    const unsigned long long slot = atomicAdd(counter, 1ull);
-    if (slot < limit) {
-        key[slot] = ((u64)min(ox, oy) << 32) | max(ox, oy);
-        ds[slot] = (uint8_t)(best | (st << 7));
-    }
-}
-
-// ---- the wide band: W words per lane
-// words per wide pattern plane of a sequence of len bases: its bits, the eight pad words in front, and what a lane reads beyond the window's first word for a text up to
-// 32 W - 1 bases longer: 2 W words of the window and the word loaded one block ahead (the farthest read is word ((len + 31) >> 5) + 2 W + 8, see near_band_ed_wide)
-__host__ __device__ __forceinline__ int near_nw_wide(int len) { return ((len + 31) >> 5) + 3 * NEAR_WMAX + 2; }
-
-// wide pattern planes of sequence s: woff[s] * 3 words in, plane k at k * nw; base p at bit p + 32 * NEAR_WMAX - 1
-__global__ __launch_bounds__(64)
-void k_near_pack_wide(const uint8_t* __restrict__ seq, const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, u64 s0, uint32_t* __restrict__ planes)
-{
-    const u64 s = s0 + blockIdx.x;
-    const u64 a = off[s];
-    const int L = (int)(off[s + 1] - a), nw = near_nw_wide(L);
-    uint32_t* base = planes + woff[s] * 3;
-    for (int w = threadIdx.x; w < nw; w += 64) {
-        uint32_t b0 = 0, b1 = 0, b2 = 0;
-        for (int t = 0; t < 32; ++t) {
-            const int p = 32 * w + t - (32 * NEAR_WMAX - 1);
-            const int c = p >= 0 && p < L ? near_code(seq[a + p]) : 7;
-            b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
-        }
-        base[w] = b0; base[(size_t)nw + w] = b1; base[(size_t)2 * nw + w] = b2;
-    }
-}
-
-// bits s .. s + 31 of hi:lo, s = 0 .. 31, as one v_alignbit_b32: unlike the 64-bit shift of near_funnel it takes any two registers, so a word that is the high half of
-// one window and the low half of the next is not copied into a register pair of its own (W = 8: 151 instead of 241 VGPRs)
+// bits s .. s + 31 of hi:lo, s = 0 .. 31: as one v_lshrrev_b64 of the register pair (near_funnel), as one v_alignbit_b32 of any two registers (near_align)
+__device__ __forceinline__ uint32_t near_funnel(uint32_t hi, uint32_t lo, int s) { return (uint32_t)((((u64)hi << 32) | lo) >> s); }
 __device__ __forceinline__ uint32_t near_align(uint32_t hi, uint32_t lo, int s) { return __builtin_amdgcn_alignbit(hi, lo, (uint32_t)s); }
 
-// pat: the wide pattern planes of a sequence of m bases (plane k at pat + k * nwp), txt: a TEXT or TEXT_RC variant of one of n bases -> their edit distance if it is
-// <= K <= 32 W - 1, else -1.  Reads pattern words up to (8 - W) + ((n - 1) >> 5) + 2 W + 1 <= ((m + 31) >> 5) + 2 W + 8 < near_nw_wide(m) (n <= m + 32 W - 1 behind
-// the length test) and text words up to ((n - 1) >> 5) + 1 < near_nw(n).  Every array is indexed by unrolled constants only: the band lives in registers.
+// pat: the pattern planes of a sequence of m bases (word i of plane k at pat[3 i + k]), txt: the TEXT or the TEXT_RC planes of one of n bases -> their edit distance if it is
+// <= K <= 32 W - 1, else -1.  Reads pattern words up to (8 - W) + ((n - 1) >> 5) + 2 W + 1 <= ((m + 31) >> 5) + 2 W + 8 < near_nwp(m) (n <= m + 32 W - 1 behind
+// the length test) and text words up to ((n - 1) >> 5) + 1 < near_nwt(n); W = 1 one word less of each.  Every array is indexed by unrolled constants only: the band
+// lives in registers.
 template <int W>
-__device__ __forceinline__ int near_band_ed_wide(const uint32_t* __restrict__ pat, int nwp, const uint32_t* __restrict__ txt, int nwt, int m, int n, int K)
+__device__ __forceinline__ int near_band_ed(const uint32_t* __restrict__ pat, const uint32_t* __restrict__ txt, int m, int n, int K)
 {
     constexpr int H = 32 * W - 1, NA = 2 * W + 1;
     const int d = n - m;
     int val = d < 0 ? -d : 0;
     if (val > K || d > K) return -1;
     if (n == 0) return val;
+    if constexpr (W == 1) {
+        // one word: the same recurrence without the carry, the shift across words and the select chain.  The three pattern words and the text word of a block are
+        // loaded at its start, nothing ahead: most pairs are dead within two blocks.  The windows are 64-bit shifts of register pairs; with three words per plane
+        // there is nothing for v_alignbit_b32 to save.  On the same planes the loop below, instantiated for W = 1, ran 2 % (k_near_tiles) and 3 % (k_near_within) slower
+        const int sb = H - d;
+        u64 VP = ~0ull << H, VN = 0;
+        pat += 3 * (NEAR_WMAX - 1);
+        for (int c0 = 0; c0 < n; c0 += 32) {
+            const int w = c0 >> 5;
+            const uint32_t a0 = pat[3 * w], a1 = pat[3 * w + 3], a2 = pat[3 * w + 6];
+            const uint32_t b0 = pat[3 * w + 1], b1 = pat[3 * w + 4], b2 = pat[3 * w + 7];
+            const uint32_t c_0 = pat[3 * w + 2], c_1 = pat[3 * w + 5], c_2 = pat[3 * w + 8];
+            const uint32_t t0 = txt[3 * w], t1 = txt[3 * w + 1], t2 = txt[3 * w + 2];
+            const int ce = min(32, n - c0);
+            for (int s = 0; s < ce; ++s) {
+                const u64 W0 = ((u64)near_funnel(a2, a1, s) << 32) | near_funnel(a1, a0, s);
+                const u64 W1 = ((u64)near_funnel(b2, b1, s) << 32) | near_funnel(b1, b0, s);
+                const u64 W2 = ((u64)near_funnel(c_2, c_1, s) << 32) | near_funnel(c_1, c_0, s);
+                const u64 T0 = (u64)0 - ((t0 >> s) & 1u), T1 = (u64)0 - ((t1 >> s) & 1u), T2 = (u64)0 - ((t2 >> s) & 1u);
+                const u64 Eq = ~((W0 ^ T0) | (W1 ^ T1) | (W2 ^ T2));
+                const u64 D0 = (((Eq & VP) + VP) ^ VP) | Eq | VN;
+                const u64 HP = VN | ~(D0 | VP);
+                const u64 HN = D0 & VP;
+                const u64 D0s = D0 >> 1;
+                VP = HN | ~(D0s | HP) | (1ull << 63);
+                VN = D0s & HP;
+                val += 1 - (int)((D0 >> sb) & 1u);
+                if (val > K) return -1;
+            }
+        }
+        return val;
+    }
     const int sb = H - d, sw = sb >> 6, sbit = sb & 63;
     u64 VP[W], VN[W];
 #pragma unroll
     for (int j = 0; j < W; ++j) { VP[j] = j < (H >> 6) ? 0ull : j == (H >> 6) ? ~0ull << (H & 63) : ~0ull; VN[j] = 0; }
-    pat += NEAR_WMAX - W;
+    pat += 3 * (NEAR_WMAX - W);
     uint32_t a[3][NA], t[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
 #pragma unroll
-        for (int i = 0; i < NA; ++i) a[k][i] = pat[(size_t)k * nwp + i];
-        t[k] = txt[(size_t)k * nwt];
+        for (int i = 0; i < NA; ++i) a[k][i] = pat[3 * i + k];
+        t[k] = txt[k];
     }
     for (int c0 = 0; c0 < n; c0 += 32) {
         const int w = c0 >> 5;
         uint32_t nx[3], tn[3];                                       // the words of the next block, loaded one block ahead
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { nx[k] = pat[(size_t)k * nwp + w + NA]; tn[k] = txt[(size_t)k * nwt + w + 1]; }
+        for (int k = 0; k < 3; ++k) { nx[k] = pat[3 * (w + NA) + k]; tn[k] = txt[3 * (w + 1) + k]; }
         const int ce = min(32, n - c0);
         for (int s = 0; s < ce; ++s) {
             const uint32_t T0 = 0u - ((t[0] >> s) & 1u), T1 = 0u - ((t[1] >> s) & 1u), T2 = 0u - ((t[2] >> s) & 1u);
@@ -263,41 +190,44 @@ __device__ __forceinline__ int near_band_ed_wide(const uint32_t* __restrict__ pa
     return val;
 }
 
-// pat3w: the wide pattern planes, txt3: the nine one-word planes of the text (its TEXT and TEXT_RC variants are read)
+// pat: the pattern planes, txt6: the six text planes.  Forward, then the reverse strand below the forward result -> the distance or -1; *strand = 1 iff the reverse
+// strand is strictly closer
 template <int W>
-__device__ __forceinline__ int near_both_wide(const uint32_t* __restrict__ pat3w, int nwp, const uint32_t* __restrict__ txt3, int nwt, int m, int n, int K, bool both, int* strand)
+__device__ __forceinline__ int near_both(const uint32_t* __restrict__ pat, const uint32_t* __restrict__ txt6, int nwt, int m, int n, int K, bool both, int* strand)
 {
-    int best = near_band_ed_wide<W>(pat3w, nwp, txt3 + (size_t)(NEAR_TEXT * 3) * nwt, nwt, m, n, K);
+    int best = near_band_ed<W>(pat, txt6, m, n, K);
     *strand = 0;
     if (both && best != 0) {
-        const int r = near_band_ed_wide<W>(pat3w, nwp, txt3 + (size_t)(NEAR_TEXT_RC * 3) * nwt, nwt, m, n, best < 0 ? K : best - 1);
+        const int r = near_band_ed<W>(pat, txt6 + (size_t)3 * nwt, m, n, best < 0 ? K : best - 1);
         if (r >= 0) { best = r; *strand = 1; }
     }
     return best;
 }
 
+// qwoff / qpl: the pattern planes of the queries, twoff / tpl: the text planes of the targets
 template <int W>
 __global__ __launch_bounds__(256)
-void k_near_within_wide(const uint64_t* __restrict__ qoff, const uint64_t* __restrict__ qwoff, const uint32_t* __restrict__ qplw, const uint64_t* __restrict__ toff, const uint64_t* __restrict__ twoff,
-                        const uint32_t* __restrict__ tpl, const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ tidx, u64 p0, u64 p1, int K, int both,
-                        int32_t* __restrict__ dist, uint8_t* __restrict__ strand)
+void k_near_within(const uint64_t* __restrict__ qoff, const uint64_t* __restrict__ qwoff, const uint32_t* __restrict__ qpl, const uint64_t* __restrict__ toff, const uint64_t* __restrict__ twoff,
+                   const uint32_t* __restrict__ tpl, const uint32_t* __restrict__ qidx, const uint32_t* __restrict__ tidx, u64 p0, u64 p1, int K, int both,
+                   int32_t* __restrict__ dist, uint8_t* __restrict__ strand)
 {
     const u64 p = p0 + (u64)blockIdx.x * 256 + threadIdx.x;
     if (p >= p1) return;
     const uint32_t q = qidx[p], t = tidx[p];
     const int m = (int)(qoff[q + 1] - qoff[q]), n = (int)(toff[t + 1] - toff[t]);
     int st = 0;
-    const int best = near_both_wide<W>(qplw + qwoff[q] * 3, near_nw_wide(m), tpl + twoff[t] * 9, near_nw(n), m, n, K, both != 0, &st);
+    const int best = near_both<W>(qpl + qwoff[q] * 3, tpl + twoff[t] * 6, near_nwt(n), m, n, K, both != 0, &st);
     dist[p] = best;
     strand[p] = (uint8_t)st;
 }
 
-// k_near_tiles with the wide band: woffw / plw = the wide pattern planes of the same set; a found pair's record is distance | strand << 15
+// rows x = xa .. xa + nrows - 1 (sorted positions); tile T of the launch belongs to the row r with toff[r] <= T < toff[r + 1] and covers y = x + 1 + 64 (T - toff[r]) + lane.
+// pwoff / ppl: the pattern planes of the set, twoff / tpl: its text planes; a found pair's record is distance | strand << 15
 template <int W>
 __global__ __launch_bounds__(256)
-void k_near_tiles_wide(const uint64_t* __restrict__ off, const uint64_t* __restrict__ woff, const uint32_t* __restrict__ pl, const uint64_t* __restrict__ woffw, const uint32_t* __restrict__ plw,
-                       const uint32_t* __restrict__ order, const uint32_t* __restrict__ hi, const uint64_t* __restrict__ toff, uint32_t xa, uint32_t nrows, u64 ntiles, int K, int both,
-                       u64* __restrict__ key, uint16_t* __restrict__ ds, u64 limit, unsigned long long* counter)
+void k_near_tiles(const uint64_t* __restrict__ off, const uint64_t* __restrict__ pwoff, const uint32_t* __restrict__ ppl, const uint64_t* __restrict__ twoff, const uint32_t* __restrict__ tpl,
+                  const uint32_t* __restrict__ order, const uint32_t* __restrict__ hi, const uint64_t* __restrict__ toff, uint32_t xa, uint32_t nrows, u64 ntiles, int K, int both,
+                  u64* __restrict__ key, uint16_t* __restrict__ ds, u64 limit, unsigned long long* counter)
 {
     const int lane = threadIdx.x & 63;
     const u64 Tl = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -311,7 +241,7 @@ void k_near_tiles_wide(const uint64_t* __restrict__ off, const uint64_t* __restr
     const uint32_t y = (uint32_t)y64, ox = order[x], oy = order[y];
     const int n = (int)(off[ox + 1] - off[ox]), m = (int)(off[oy + 1] - off[oy]);
     int st = 0;
-    const int best = near_both_wide<W>(plw + woffw[oy] * 3, near_nw_wide(m), pl + woff[ox] * 9, near_nw(n), m, n, K, both != 0, &st);
+    const int best = near_both<W>(ppl + pwoff[oy] * 3, tpl + twoff[ox] * 6, near_nwt(n), m, n, K, both != 0, &st);
     if (best < 0) return;
     const unsigned long long slot = atomicAdd(counter, 1ull);
     if (slot < limit) {
@@ -320,37 +250,20 @@ void k_near_tiles_wide(const uint64_t* __restrict__ off, const uint64_t* __restr
     }
 }
 
-// the planes of every sequence of R in `buf` (grow-only), the word offsets on the device
-int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
+// the planes of one kind (NEAR_PATTERN or NEAR_TEXT) of every sequence of R in `buf` (grow-only), the word offsets on the device
+int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, int kind, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
 {
     PinVec<uint64_t> woff(R.n + 1);
     woff[0] = 0;
-    for (uint64_t s = 0; s < R.n; ++s) woff[s + 1] = woff[s] + (uint64_t)near_nw((int)(R.h_off[s + 1] - R.h_off[s]));
-    HIPCHK(ctx, buf.reserve(woff[R.n] * 9));
+    for (uint64_t s = 0; s < R.n; ++s) { const int len = (int)(R.h_off[s + 1] - R.h_off[s]); woff[s + 1] = woff[s] + (uint64_t)(kind == NEAR_PATTERN ? near_nwp(len) : near_nwt(len)); }
+    HIPCHK(ctx, buf.reserve(woff[R.n] * (kind == NEAR_PATTERN ? 3 : 6)));
     NGSID_TRY(dev_put(ctx, d_woff, woff.data(), R.n + 1));
     ProfScope ps_(ctx, "k_near_pack");
     for (uint64_t s0 = 0; s0 < R.n; s0 += 1u << 30) {
-        hipLaunchKernelGGL(k_near_pack, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, buf.p);
+        hipLaunchKernelGGL(k_near_pack, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, kind, buf.p);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // (woff is a host vector of this scope)
-    return NGSID_OK;
-}
-
-// the wide pattern planes of every sequence of R in `buf` (grow-only), the word offsets on the device
-int32_t near_pack_wide(ngsid_ctx* ctx, const DevReads& R, DevBuf<uint32_t>& buf, DevBuf<uint64_t>& d_woff)
-{
-    PinVec<uint64_t> woff(R.n + 1);
-    woff[0] = 0;
-    for (uint64_t s = 0; s < R.n; ++s) woff[s + 1] = woff[s] + (uint64_t)near_nw_wide((int)(R.h_off[s + 1] - R.h_off[s]));
-    HIPCHK(ctx, buf.reserve(woff[R.n] * 3));
-    NGSID_TRY(dev_put(ctx, d_woff, woff.data(), R.n + 1));
-    ProfScope ps_(ctx, "k_near_pack");
-    for (uint64_t s0 = 0; s0 < R.n; s0 += 1u << 30) {
-        hipLaunchKernelGGL(k_near_pack_wide, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, buf.p);
-        HIPCHK(ctx, hipGetLastError());
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NGSID_OK;
 }
 
@@ -371,8 +284,17 @@ int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, int32_t limit, const DevRea
     return NGSID_OK;
 }
 
-// the band words of a wide call: the smallest instance that holds max_dist, 1 = the one-word kernels
+// the band words of a call: the smallest instance that holds max_dist
 int near_width(int32_t max_dist) { return max_dist <= NGSID_NEAR_MAX_DIST ? 1 : max_dist <= 63 ? 2 : max_dist <= 127 ? 4 : 8; }
+
+// launches the instance KERN<W> of k_near_within or k_near_tiles, W = near_width(max_dist), under the profiling line KERN (W = 1) or KERN_wide
+#define NEAR_LAUNCH(KERN, W, GRID, ...) do { \
+        ProfScope ps_(ctx, (W) == 1 ? #KERN : #KERN "_wide"); \
+        if ((W) == 1) hipLaunchKernelGGL((KERN<1>), GRID, dim3(256), 0, ctx->stream, __VA_ARGS__); \
+        else if ((W) == 2) hipLaunchKernelGGL((KERN<2>), GRID, dim3(256), 0, ctx->stream, __VA_ARGS__); \
+        else if ((W) == 4) hipLaunchKernelGGL((KERN<4>), GRID, dim3(256), 0, ctx->stream, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERN<8>), GRID, dim3(256), 0, ctx->stream, __VA_ARGS__); \
+    } while (0)
 
 // ngsid_ed_within_batch (limit = NGSID_NEAR_MAX_DIST) and ngsid_ed_within_wide_batch (limit = NGSID_NEAR_WIDE_MAX_DIST) behind their argument checks
 int32_t near_within_run(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsid_reads_t* targets, const uint32_t* q_idx, const uint32_t* t_idx, uint64_t n_pairs,
@@ -385,26 +307,15 @@ int32_t near_within_run(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsi
     if (n_pairs == 0) return NGSID_OK;
     const int W = near_width(max_dist);
     DevBuf<uint64_t> d_qw, d_tw; DevBuf<int32_t> d_dist; DevBuf<uint8_t> d_strand;
-    if (W == 1) { NGSID_TRY(near_pack(ctx, B.Q, ctx->near_pl[0], d_qw)); } else { NGSID_TRY(near_pack_wide(ctx, B.Q, ctx->near_plw, d_qw)); }
-    NGSID_TRY(near_pack(ctx, B.T, ctx->near_pl[1], d_tw));
+    NGSID_TRY(near_pack(ctx, B.Q, NEAR_PATTERN, ctx->near_pat, d_qw));
+    NGSID_TRY(near_pack(ctx, B.T, NEAR_TEXT, ctx->near_txt, d_tw));
     HIPCHK(ctx, d_dist.alloc(n_pairs)); HIPCHK(ctx, d_strand.alloc(n_pairs));
     const long long opt = ngsid_opt(ctx, "near_chunk_pairs", 0);
     const uint64_t chunk = opt > 0 ? (uint64_t)opt : (uint64_t)1 << 30;
     for (uint64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
         const uint64_t p1 = std::min(n_pairs, p0 + chunk);
-        const dim3 grid((unsigned)((p1 - p0 + 255) / 256));
-        const int both = (int)(flags & NGSID_NEAR_BOTH_STRANDS);
-        if (W == 1) {
-            ProfScope ps_(ctx, "k_near_within");
-            hipLaunchKernelGGL(k_near_within, grid, dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_pl[0].p, B.T.off, d_tw.p, ctx->near_pl[1].p,
-                               B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, both, d_dist.p, d_strand.p);
-        } else {
-            ProfScope ps_(ctx, "k_near_within_wide");
-#define NEAR_WITHIN_WIDE(WW) hipLaunchKernelGGL((k_near_within_wide<WW>), grid, dim3(256), 0, ctx->stream, B.Q.off, d_qw.p, ctx->near_plw.p, B.T.off, d_tw.p, ctx->near_pl[1].p, \
-                                                B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, both, d_dist.p, d_strand.p)
-            if (W == 2) NEAR_WITHIN_WIDE(2); else if (W == 4) NEAR_WITHIN_WIDE(4); else NEAR_WITHIN_WIDE(8);
-#undef NEAR_WITHIN_WIDE
-        }
+        NEAR_LAUNCH(k_near_within, W, dim3((unsigned)((p1 - p0 + 255) / 256)), B.Q.off, d_qw.p, ctx->near_pat.p, B.T.off, d_tw.p, ctx->near_txt.p,
+                    B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), d_dist.p, d_strand.p);
         HIPCHK(ctx, hipGetLastError());
     }
     NGSID_TRY(dev_get(ctx, dist, d_dist.p, n_pairs));
@@ -413,14 +324,10 @@ int32_t near_within_run(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsi
     return NGSID_OK;
 }
 
-// ngsid_near_pairs (dist_limit = NGSID_NEAR_MAX_DIST) and ngsid_near_pairs_wide (dist_limit = NGSID_NEAR_WIDE_MAX_DIST) behind the context check.  REC = the found-pair record:
-// uint8_t (distance | strand << 7) with the one-word kernel, uint16_t (distance | strand << 15) with a wide one
-template <typename REC>
+// ngsid_near_pairs (dist_limit = NGSID_NEAR_MAX_DIST) and ngsid_near_pairs_wide (dist_limit = NGSID_NEAR_WIDE_MAX_DIST) behind the context check
 int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, int32_t dist_limit, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
                        uint64_t cap, uint64_t* n_found, uint64_t* needed)
 {
-    constexpr bool WIDE = sizeof(REC) == 2;
-    constexpr int SBIT = WIDE ? 15 : 7;
     if (!seqs || !n_found || !needed || (cap && (!pair_i || !pair_j || !dist || !strand))) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     *n_found = 0; *needed = 0;
     DevReads R;
@@ -428,7 +335,7 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
     NGSID_TRY(near_check(ctx, max_dist, dist_limit, &R, nullptr));
     const uint64_t N = R.n;
     if (N < 2) return NGSID_OK;
-    const int W = near_width(max_dist);                              // (WIDE: 2, 4 or 8; else 1)
+    const int W = near_width(max_dist);
     // ---- sorted by (length, index); hi[x] = the last sorted position whose sequence is at most max_dist bases longer than x's; 64 candidates per tile
     auto len = [&](uint32_t s) { return (uint32_t)(R.h_off[(size_t)s + 1] - R.h_off[s]); };
     PinVec<uint32_t> order(N), hi(N);
@@ -441,19 +348,18 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
         hi[x] = (uint32_t)y;
         tiles[x + 1] = tiles[x] + (y - x + 63) / 64;
     }
-    DevBuf<uint64_t> d_woff, d_woffw, d_toff; DevBuf<uint32_t> d_order, d_hi; DevBuf<unsigned long long> d_ctr;
-    NGSID_TRY(near_pack(ctx, R, ctx->near_pl[0], d_woff));
-    if (WIDE) { NGSID_TRY(near_pack_wide(ctx, R, ctx->near_plw, d_woffw)); }
+    DevBuf<uint64_t> d_pwoff, d_twoff, d_toff; DevBuf<uint32_t> d_order, d_hi; DevBuf<unsigned long long> d_ctr;
+    NGSID_TRY(near_pack(ctx, R, NEAR_PATTERN, ctx->near_pat, d_pwoff));
+    NGSID_TRY(near_pack(ctx, R, NEAR_TEXT, ctx->near_txt, d_twoff));
     NGSID_TRY(dev_put(ctx, d_order, order.data(), N)); NGSID_TRY(dev_put(ctx, d_hi, hi.data(), N));
     HIPCHK(ctx, d_ctr.alloc(1));
     // ---- the found buffer: cap entries, or what a share of the free device memory holds; rows in chunks
-    const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / (8 + sizeof(REC)));
-    if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F * sizeof(REC))); }
-    REC* const d_ds = reinterpret_cast<REC*>(ctx->near_ds.p);
+    const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / (8 + sizeof(uint16_t)));
+    if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F)); }
     const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0);
     const uint64_t max_tiles = (uint64_t)1 << 30;                     // per launch: four tiles per workgroup
     bool fill = cap > 0;
-    std::vector<uint64_t> keys; std::vector<REC> dss;
+    std::vector<uint64_t> keys; std::vector<uint16_t> dss;
     uint64_t total = 0, rows_now = opt > 0 ? (uint64_t)opt : N;
     PinVec<uint64_t> h_toff;
     for (uint64_t xa = 0; xa < N; ) {
@@ -467,17 +373,8 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
         NGSID_TRY(dev_put(ctx, d_toff, h_toff.data(), xb - xa + 1));
         HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long), ctx->stream));
         const uint64_t limit = fill ? std::min(F, cap - total) : 0;
-        if constexpr (!WIDE) {
-            ProfScope ps_(ctx, "k_near_tiles");
-            hipLaunchKernelGGL(k_near_tiles, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
-                               (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, d_ds, (u64)limit, d_ctr.p);
-        } else {
-            ProfScope ps_(ctx, "k_near_tiles_wide");
-#define NEAR_TILES_WIDE(WW) hipLaunchKernelGGL((k_near_tiles_wide<WW>), dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, ctx->stream, R.off, d_woff.p, ctx->near_pl[0].p, d_woffw.p, ctx->near_plw.p, d_order.p, d_hi.p, \
-                                               d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, d_ds, (u64)limit, d_ctr.p)
-            if (W == 2) NEAR_TILES_WIDE(2); else if (W == 4) NEAR_TILES_WIDE(4); else NEAR_TILES_WIDE(8);
-#undef NEAR_TILES_WIDE
-        }
+        NEAR_LAUNCH(k_near_tiles, W, dim3((unsigned)((nt + 3) / 4)), R.off, d_pwoff.p, ctx->near_pat.p, d_twoff.p, ctx->near_txt.p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
+                    (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, ctx->near_ds.p, (u64)limit, d_ctr.p);
         HIPCHK(ctx, hipGetLastError());
         unsigned long long c = 0;
         NGSID_TRY(dev_get(ctx, &c, d_ctr.p, 1));
@@ -490,7 +387,7 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
         if (fill && c) {
             const size_t at = keys.size();
             keys.resize(at + c); dss.resize(at + c);
-            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, d_ds, (size_t)c));
+            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, ctx->near_ds.p, (size_t)c));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
         total += c;
@@ -503,8 +400,8 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
     std::iota(perm.begin(), perm.end(), (uint64_t)0);
     std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return keys[a] < keys[b]; });
     for (uint64_t k = 0; k < total; ++k) {
-        const uint64_t key = keys[perm[k]]; const REC v = dss[perm[k]];
-        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = (uint8_t)(v & ((1u << SBIT) - 1)); strand[k] = (uint8_t)(v >> SBIT);
+        const uint64_t key = keys[perm[k]]; const uint16_t v = dss[perm[k]];
+        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = (uint8_t)(v & 0x7fffu); strand[k] = (uint8_t)(v >> 15);
     }
     *n_found = total;
     return NGSID_OK;
@@ -533,16 +430,13 @@ extern "C" int32_t ngsid_near_pairs(ngsid_ctx* ctx, const ngsid_reads_t* seqs, i
 {
     ApiClock api_clock_(ctx, "near_pairs");
     if (!ctx) return NGSID_ERR_ARG;
-    return near_pairs_run<uint8_t>(ctx, seqs, max_dist, NGSID_NEAR_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
+    return near_pairs_run(ctx, seqs, max_dist, NGSID_NEAR_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
 }
 
-// (a max_dist the one-word band holds, or one outside the range, goes the one-word way: the same kernels, the same refusal)
 extern "C" int32_t ngsid_near_pairs_wide(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_dist, uint32_t flags, uint32_t* pair_i, uint32_t* pair_j, uint8_t* dist, uint8_t* strand,
                                          uint64_t cap, uint64_t* n_found, uint64_t* needed)
 {
     ApiClock api_clock_(ctx, "near_pairs_wide");
     if (!ctx) return NGSID_ERR_ARG;
-    if (max_dist > NGSID_NEAR_MAX_DIST && max_dist <= NGSID_NEAR_WIDE_MAX_DIST)
-        return near_pairs_run<uint16_t>(ctx, seqs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
-    return near_pairs_run<uint8_t>(ctx, seqs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
+    return near_pairs_run(ctx, seqs, max_dist, NGSID_NEAR_WIDE_MAX_DIST, flags, pair_i, pair_j, dist, strand, cap, n_found, needed);
 }

@@ -579,7 +579,7 @@ extern "C" int32_t ngsid_ctx_option(ngsid_ctx* ctx, const char* name, int64_t va
         for (auto& L : ctx->poa_lv) { L.out.release(); L.seqs.release(); L.job_final.release(); L.out_len.release(); L.out_span.release(); L.job_bb.release(); L.out_cw.release(); L.out_n.release(); L.out_cov.release(); L.job_off.release(); L.seq_idx.release(); L.flags.release(); L.job_list.release(); L.job_unit.release(); L.job_pos.release(); }
         ctx->mzc.valid = false; ctx->mzc_cnt.release(); ctx->mzc_hlen.release(); ctx->mz_off.release(); ctx->mz_scode.release(); ctx->mz_spos.release();
         ctx->pol_mzcode.release(); ctx->pol_mzpos.release(); ctx->pol_oseq.release(); ctx->pol_oqual.release(); ctx->pol_valid.release(); ctx->pol_bp.release(); ctx->pol_lay.release(); ctx->cl_cnt.release(); ctx->cls_cnt.release(); ctx->chm_prof.release(); ctx->chm_bnd.release();
-        ctx->near_pl[0].release(); ctx->near_pl[1].release(); ctx->near_plw.release(); ctx->near_key.release(); ctx->near_ds.release();
+        ctx->near_pat.release(); ctx->near_txt.release(); ctx->near_key.release(); ctx->near_ds.release();
         ngsid_pool_release_all();
         return NGSID_OK;
     }

@@ -121,7 +121,7 @@ struct ngsid_ctx {
     DevBuf<int32_t> poa_h; DevBuf<uint8_t> poa_d; DevBuf<uint8_t> poa_g; DevBuf<uint32_t> poa_cov;   // POA tile scratch (grow-only)
     DevBuf<uint32_t> cls_cnt;                                  // count rows [query][strand][reference] of ngsid_classify_search's current chunk (grow-only; k_classify.hip)
     DevBuf<uint16_t> chm_prof; DevBuf<uint32_t> chm_bnd;       // ngsid_chimera_model (k_chimera.hip): the F / B profiles of the current chunk of queries, the strip boundaries of its waves (grow-only)
-    DevBuf<uint32_t> near_pl[2], near_plw; DevBuf<uint64_t> near_key; DevBuf<uint8_t> near_ds;      // ngsid_ed_within_batch / ngsid_near_pairs and their wide twins (k_near.hip): the letter planes of the two read sets, the wide pattern planes, the found pairs of the current chunk (grow-only)
+    DevBuf<uint32_t> near_pat, near_txt; DevBuf<uint64_t> near_key; DevBuf<uint16_t> near_ds;      // ngsid_ed_within_batch / ngsid_near_pairs and their wide twins (k_near.hip): the pattern planes and the text planes of the call's sequences, the found pairs of the current chunk (grow-only)
     std::vector<struct ngsid_refdb*> refdbs;                   // reference libraries built in this context (ngsid_refdb_build) and not released yet: they go with the context
 };
 void ngsid_refdb_release_all(ngsid_ctx* ctx);                  // k_classify.hip: ngsid_destroy releases the libraries the caller left

@@ -73,6 +73,20 @@ def test_exact_distance_length_difference_and_outermost_diagonal(gpu_api, K):
     _check_within(gpu_api, qs, ts, idx, idx, K, "K=%d both strands" % K)
 
 
+@pytest.mark.parametrize("K", (0, 1, 31))
+def test_carry_chain_of_poly_a(gpu_api, K):
+    """poly-A against poly-A: Eq and VP are all ones inside the sequences, so the sum carries out of the band word in every column; 600 bases, so the words loaded
+    one block ahead are used.  The true distances are 0, 1, K, K + 1, 1, K, K + 1, 1, 1: [0, 1, K, -1, 1, K, -1, 1, 1] for K >= 1, and at K = 0 the 1s are beyond
+    the bound as well"""
+    n = 600
+    qs = ["A" * n] * 4 + ["A" * (n + d) for d in (1, K, K + 1)] + ["A" * n, "A" * 300 + "G" + "A" * 299]
+    ts = ["A" * (n + d) for d in (0, 1, K, K + 1)] + ["A" * n] * 3 + ["A" * 300 + "G" + "A" * 299, "A" * n]
+    idx = np.arange(len(qs))
+    got = _check_within(gpu_api, qs, ts, idx, idx, K, "K=%d poly-A" % K, both=False)
+    assert got[0].tolist() == ([0, 1, K, -1, 1, K, -1, 1, 1] if K >= 1 else [0, -1, 0, -1, -1, 0, -1, -1, -1])
+    _check_within(gpu_api, qs, ts, idx, idx, K, "K=%d poly-A both strands" % K)
+
+
 def test_letters_palindromes_and_the_reverse_strand(gpu_api):
     rng = np.random.default_rng(9)
     pal = "ACGTTAACGT"
