@@ -52,8 +52,6 @@ __host__ __device__ __forceinline__ int near_nwp(int len) { return ((len + 31) >
 // words per text plane: its bits and the word loaded one block ahead (the farthest read is word ((len - 1) >> 5) + 1 = (len + 31) >> 5; a text of no bases is not read)
 __host__ __device__ __forceinline__ int near_nwt(int len) { return ((len + 31) >> 5) + 1; }
 
-__device__ __forceinline__ int near_code(uint8_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
-
 // word w of the three planes at base (plane k at base[3 w + k]): bit t holds the code of base p = 32 w + t - shift of seq (L bases), with rc the complement of base L - 1 - p
 __device__ __forceinline__ void near_pack_word(const uint8_t* __restrict__ seq, int L, int w, int shift, bool rc, uint32_t* __restrict__ base)
 {
@@ -62,7 +60,7 @@ __device__ __forceinline__ void near_pack_word(const uint8_t* __restrict__ seq, 
         const int p = 32 * w + t - shift;
         int c = 7;
         if (p >= 0 && p < L) {
-            c = near_code(seq[rc ? L - 1 - p : p]);
+            c = (int)ngsid_base_code(seq[rc ? L - 1 - p : p]);
             if (rc && c < 4) c = 3 - c;
         }
         b0 |= (uint32_t)(c & 1) << t; b1 |= (uint32_t)((c >> 1) & 1) << t; b2 |= (uint32_t)((c >> 2) & 1) << t;
@@ -358,41 +356,29 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
     if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F)); }
     const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0);
     const uint64_t max_tiles = (uint64_t)1 << 30;                     // per launch: four tiles per workgroup
-    bool fill = cap > 0;
     std::vector<uint64_t> keys; std::vector<uint16_t> dss;
-    uint64_t total = 0, rows_now = opt > 0 ? (uint64_t)opt : N;
     PinVec<uint64_t> h_toff;
-    for (uint64_t xa = 0; xa < N; ) {
-        uint64_t xb = std::min(N, xa + rows_now);
+    const auto launch = [&](uint64_t xa, uint64_t& xb, uint64_t limit, bool& launched) -> int32_t {
         while (xb - xa > 1 && tiles[xb] - tiles[xa] > max_tiles) xb = xa + (xb - xa) / 2;
         const uint64_t nt = tiles[xb] - tiles[xa];
-        if (nt == 0) { xa = xb; continue; }
+        if (nt == 0) { launched = false; return NGSID_OK; }
         if (nt > 4 * max_tiles) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
         h_toff.resize(xb - xa + 1);
         for (uint64_t r = 0; r <= xb - xa; ++r) h_toff[r] = tiles[xa + r] - tiles[xa];
         NGSID_TRY(dev_put(ctx, d_toff, h_toff.data(), xb - xa + 1));
         HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long), ctx->stream));
-        const uint64_t limit = fill ? std::min(F, cap - total) : 0;
         NEAR_LAUNCH(k_near_tiles, W, dim3((unsigned)((nt + 3) / 4)), R.off, d_pwoff.p, ctx->near_pat.p, d_twoff.p, ctx->near_txt.p, d_order.p, d_hi.p, d_toff.p, (uint32_t)xa, (uint32_t)(xb - xa), (u64)nt,
                     (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), ctx->near_key.p, ctx->near_ds.p, (u64)limit, d_ctr.p);
-        HIPCHK(ctx, hipGetLastError());
-        unsigned long long c = 0;
-        NGSID_TRY(dev_get(ctx, &c, d_ctr.p, 1));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (fill && c > limit) {
-            if (limit == cap - total) fill = false;                   // more pairs than the caller has room for: count on
-            else if (xb - xa > 1) { rows_now = (xb - xa) / 2; continue; }      // more than the found buffer holds: the same rows in smaller chunks
-            else NGSID_FAIL(ctx, NGSID_ERR_HIP, "one sequence has %llu near neighbours: beyond the found buffer the free device memory allows", c);
-        }
-        if (fill && c) {
-            const size_t at = keys.size();
-            keys.resize(at + c); dss.resize(at + c);
-            NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, (size_t)c)); NGSID_TRY(dev_get(ctx, dss.data() + at, ctx->near_ds.p, (size_t)c));
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        total += c;
-        xa = xb;
-    }
+        return NGSID_OK;
+    };
+    const auto fetch = [&](uint64_t, size_t c) -> int32_t {
+        const size_t at = keys.size();
+        keys.resize(at + c); dss.resize(at + c);
+        NGSID_TRY(dev_get(ctx, keys.data() + at, ctx->near_key.p, c));
+        return dev_get(ctx, dss.data() + at, ctx->near_ds.p, c);
+    };
+    uint64_t total = 0;
+    NGSID_TRY(ngsid_found_loop(ctx, N, opt > 0 ? (uint64_t)opt : N, F, cap, d_ctr.p, launch, fetch, "sequence", "near neighbours", &total));
     *needed = total;
     if (total > cap) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "%llu near pairs, room for %llu", (unsigned long long)total, (unsigned long long)cap);
     // ---- ascending (i, j): the keys are distinct

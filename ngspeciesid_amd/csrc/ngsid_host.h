@@ -1,4 +1,5 @@
-// ngsid_host.h - host-side plumbing the entry points share: transfers, the memory budget, list checks, the grouped-reads front end, pair batches, sketch scratch, the alphabet scan
+// ngsid_host.h - host-side plumbing the entry points share: transfers, the memory budget, list checks, the grouped-reads front end, pair batches, sketch scratch, the alphabet scan,
+// the IUPAC equality and the letter code (k_demux_common.h, k_near.hip), the found-buffer loop (k_demux_scan.hip, k_near.hip)
 #pragma once
 #include "ngsid_internal.h"
 #include <algorithm>
@@ -81,3 +82,39 @@ static inline int32_t ngsid_sketch(ngsid_ctx* ctx, const DevReads& R, int k, int
 
 // ---- k_demux.hip: enqueues the scan of R's bases; *d_flag (cleared by the caller) becomes non-zero when one is outside upper-case ACGTN.  The caller reads the flag.
 int32_t ngsid_alphabet_scan(ngsid_ctx* ctx, const DevReads& R, uint32_t* d_flag, const char* prof_name = nullptr);
+bool ngsid_iupac_eq(uint8_t a, uint8_t b, int iupac);      // host_io.hip: the equality rule of ngsid_host_infix_locate
+// the letter code of the demultiplexer and near-pairs kernels: A C G T -> 0 .. 3, anything else (N) -> 4
+__device__ __forceinline__ uint32_t ngsid_base_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+
+// ---- the found-buffer loop of ngsid_demux_scan and ngsid_near_pairs*: rows [0, N) in chunks of rows_first, every launch appending its records to a found buffer of F
+// records through ONE counter (*d_ctr) that runs on past the launch's `limit`, so a launch always yields its count.  launch(a, b, limit, launched) clears the counter and
+// enqueues rows [a, b) (it may lower b, or clear `launched` when the rows hold nothing to launch); fetch(a, c) enqueues the copy of the c records of the launch that began at row a.
+// -> *total: the records of all rows.  Filling stops (and counting goes on) exactly when total exceeds cap.
+template <typename Launch, typename Fetch>
+static inline int32_t ngsid_found_loop(ngsid_ctx* ctx, uint64_t N, uint64_t rows_first, uint64_t F, uint64_t cap, unsigned long long* d_ctr, Launch launch, Fetch fetch,
+                                       const char* row_noun, const char* record_noun, uint64_t* total_out)
+{
+    bool fill = cap > 0;
+    uint64_t total = 0, rows_now = rows_first;
+    for (uint64_t a = 0; a < N; ) {
+        uint64_t b = std::min(N, a + rows_now);
+        const uint64_t limit = fill ? std::min(F, cap - total) : 0;
+        bool launched = true;
+        NGSID_TRY(launch(a, b, limit, launched));
+        if (!launched) { a = b; continue; }
+        HIPCHK(ctx, hipGetLastError());
+        unsigned long long c = 0;
+        NGSID_TRY(dev_get(ctx, &c, d_ctr, 1));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (fill && c > limit) {
+            if (limit == cap - total) fill = false;                     // more records than the caller has room for: count on
+            else if (b - a > 1) { rows_now = (b - a) / 2; continue; }   // more than the found buffer holds: the same rows in smaller chunks
+            else NGSID_FAIL(ctx, NGSID_ERR_HIP, "one %s has %llu %s: beyond the found buffer the free device memory allows", row_noun, c, record_noun);
+        }
+        if (fill && c) { NGSID_TRY(fetch(a, (size_t)c)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
+        total += c;
+        a = b;
+    }
+    *total_out = total;
+    return NGSID_OK;
+}

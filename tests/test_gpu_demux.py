@@ -88,6 +88,23 @@ def test_tag_list_passes(gpu_api, T):
     _check(gpu_api, reads, tags, W, 40, what="T=%d, every tag hits" % T)
 
 
+@pytest.mark.parametrize("W", [129, 256])
+@pytest.mark.parametrize("T", [1, 2])
+def test_lanes_outside_every_group(gpu_api, T, W):
+    """windows above 128 bases cap a wave at 32 read-sides: with one tag lanes 32 .. 63 of every wave belong to no group, with two every lane does"""
+    rng = np.random.default_rng(500 + 10 * T + W)
+    tags = [_rand(rng, m) for m in (30, 64)[:T]]
+    reads = []
+    for i in range(150):
+        r = _rand(rng, int(rng.integers(0, 2 * W + 41)), "ACGTN" if i % 7 == 0 else "ACGT")
+        if i % 3 == 0:
+            p = int(rng.integers(0, len(r) + 1)); t = tags[int(rng.integers(0, T))]
+            r = r[:p] + (t if i % 2 else ref.revcomp(t)) + r[p:]
+        reads.append(r)
+    want = _check(gpu_api, reads, tags, W, 3, what="T=%d" % T)
+    assert (want[0][0::3, :, 0] >= 0).any(axis=1).mean() > 0.5                           # most planted tags lie inside a window
+
+
 CODES = {"R": "AG", "Y": "CT", "N": "ACGT", "X": "ACGT", "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "M": "AC", "K": "GT", "S": "CG", "W": "AT"}
 
 
