@@ -79,7 +79,7 @@ uint32_t    ngsid_abi_version(void);
 
 /* (f1) replaces get_sorted_fastq_for_cluster.calc_score_new / fastq_single_core :23-33,124-155.
  * score[i] = expected number of error-free k-mers, err_rate[i] = mean 10^-(q/10) (no clamp),
- * keep[i] = 0 when len<2k, HPC len<k or 10*-log10(err)<=q_threshold.  Limits: k <= 64 (NGSID_ERR_ARG), reads <= 65535 bases (NGSID_ERR_TOO_LONG). */
+ * keep[i] = 0 when len<2k, HPC len<k or 10*-log10(err)<=q_threshold.  Limits: k <= 64 (NGSID_ERR_ARG).  No limit on the read length here: reads above NGSID_MAX_READ_LEN are scored too (32-bit quality histogram), they are only not clustered. */
 int32_t ngsid_score_reads(ngsid_ctx* ctx, const ngsid_reads_t* reads, int32_t k, double q_threshold,
                           double* score, double* err_rate, uint8_t* keep);
 
@@ -89,7 +89,7 @@ int32_t ngsid_score_reads(ngsid_ctx* ctx, const ngsid_reads_t* reads, int32_t k,
  * codes are 3-bit-per-base order-preserving k-mer codes for k <= 21; for 22 <= k <= 32 they are the dense ranks of the k-mers among all
  * minimizers of THIS call (order preserving, equal k-mers equal code; not comparable between calls); pos are positions in the HPC string.
  * hpc_len[i] = HPC length, hpc_err[i] = error rate (sum over quality characters in ascending
- * character code), reads with hpc_len<k get 0 minimizers.
+ * character code), reads with hpc_len<k get 0 minimizers.  A base outside ACGTN in ANY read of the call, one with hpc_len<k included, is NGSID_ERR_ALPHABET.
  * codes/pos/mz_off follow reads->mem (device outputs for device inputs); hpc_len/hpc_err are host. */
 int32_t ngsid_hpc_minimizers(ngsid_ctx* ctx, const ngsid_reads_t* reads, int32_t k, int32_t w,
                              uint64_t* mz_off, uint64_t* codes, uint32_t* pos, uint64_t cap, uint64_t* needed,

@@ -10,7 +10,7 @@
 //   4. window minima through a sparse table of argmin positions (log2(w-k+1) doubling passes instead of a scan of w-k+1 codes per window),
 //      emission on position change by ballot-ordered compaction, (code, pos) pairs written at the read's own base offset in HBM
 //      (a read of n bases has at most n-k+1 minimizers: no allocation pass, no atomics, deterministic layout).
-// k <= 21 fits one 64-bit code.  22 <= k <= 42 (KW = 2) keeps (hi, lo) pairs - lo = the last 21 letters - and a rename pass afterwards
+// k <= 21 fits one 64-bit code.  22 <= k <= 32 = NGSID_MAX_K (KW = 2) keeps (hi, lo) pairs - lo = the last 21 letters - and a rename pass afterwards
 // replaces them by their dense rank over the whole launch (order preserving, equal k-mers equal code), so everything downstream still
 // sees 64-bit order-preserving codes.  HBM traffic per read: 2L in, 12 B per minimizer out.
 #include "ngsid_internal.h"

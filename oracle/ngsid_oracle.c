@@ -58,6 +58,10 @@ static inline int enc3(uint8_t c) {
     switch (c) { case 'A': return 1; case 'C': return 2; case 'G': return 3; case 'N': return 4; case 'T': return 5; default: return -1; }
 }
 
+/* a letter the encoder has no code for, anywhere in an HPC string: NGSID_ERR_ALPHABET for the whole call, whether or not the read is long enough to have a k-mer (the library
+ * encodes every HPC letter of every read before it looks at the length) */
+static int has_foreign(const uint8_t* hs, int hl) { for (int i = 0; i < hl; ++i) if (enc3(hs[i]) < 0) return 1; return 0; }
+
 /* (a2) get_kmer_minimizers(seq,k,w)                                                    cluster.py:16-39
  * = leftmost minimum of every window of w-k+1 consecutive k-mers, emitted when its position changes.
  * For len < w the first (only) window holds end-truncated / empty slices (cluster.py:19): codes are
@@ -356,6 +360,7 @@ int32_t ongsid_hpc_minimizers(const ngsid_reads_t* reads, int32_t k, int32_t w,
         int n = (int)(reads->off[r + 1] - reads->off[r]);
         uint8_t* hs = (uint8_t*)malloc((size_t)n + 1), *hq = (uint8_t*)malloc((size_t)n + 1);
         int hl = hpc_compress(s, q, n, hs, hq);
+        if (has_foreign(hs, hl)) { free(hs); free(hq); free(wide); FAIL(NGSID_ERR_ALPHABET, "read %llu: base outside ACGTN", (unsigned long long)r); }
         if (hpc_len) hpc_len[r] = (uint32_t)hl;
         if (hpc_err) hpc_err[r] = (q && hl > 0) ? mean_err(hq, hl, NGSID_PHRED_P) : NAN;
         int cnt = 0;
@@ -479,6 +484,7 @@ int32_t ongsid_cluster_greedy(const ngsid_reads_t* reads, const ngsid_cluster_pa
         int hl = hpc_compress(s, q, n, hs, hq);
         double e = (known_err && !isnan(known_err[i])) ? known_err[i] : (hl > 0 ? mean_err(hq, hl, NGSID_PHRED_P) : NAN);
         herr[i] = e; if (hpc_err_out) hpc_err_out[i] = e;
+        if (has_foreign(hs, hl)) { rc = NGSID_ERR_ALPHABET; snprintf(g_err, sizeof g_err, "read %llu: base outside ACGTN", (unsigned long long)i); goto done; }
         if (hl < k) continue;
         int cnt = minimizers(hs, hl, k, w, mc, mp);
         if (cnt < 0) { rc = NGSID_ERR_ALPHABET; snprintf(g_err, sizeof g_err, "read %llu: base outside ACGTN", (unsigned long long)i); goto done; }
@@ -491,6 +497,7 @@ int32_t ongsid_cluster_greedy(const ngsid_reads_t* reads, const ngsid_cluster_pa
         const uint8_t* s = reads->seq + reads->off[i]; const uint8_t* q = reads->qual + reads->off[i]; int n = (int)(reads->off[i + 1] - reads->off[i]);
         int hl = hpc_compress(s, q, n, hs, hq);
         if (g_tr_best && i < g_tr_n) { g_tr_best[i] = -2; g_tr_ns[i] = 0; g_tr_ratio[i] = 0.0; }
+        if (has_foreign(hs, hl)) { rc = NGSID_ERR_ALPHABET; snprintf(g_err, sizeof g_err, "read %llu: base outside ACGTN", (unsigned long long)i); goto done; }
         if (hl < k) { if (status_out) status_out[i] = NGSID_ST_SHORT; continue; }    /* cluster.py:266-268 */
         int M = minimizers(hs, hl, k, w, mc, mp);                                     /* cluster.py:269 */
         if (M < 0) { rc = NGSID_ERR_ALPHABET; snprintf(g_err, sizeof g_err, "read %llu: base outside ACGTN", (unsigned long long)i); goto done; }
