@@ -105,6 +105,9 @@ def phase_offsets(grp_off, site_off):
     return geno_off, tab_off
 
 
+HP_NBUCKET, HP_OTHER = 17, 16                                                      # include/ngsid_hp.h: buckets 0 - 14 exact run lengths, 15 = 15 or more, 16 = spanned, no length
+
+
 def cluster_params(k=13, w=20, min_shared=5, min_fraction=0.8, mapped_threshold=0.7, aligned_threshold=0.4,
                    min_prob_no_hits=0.1, symmetric=False, p_shared=None):
     p = ClusterParams()
@@ -657,6 +660,25 @@ class Api:
         rc = self._call("consensus_support", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(counts), _p(used), _p(strand))
         if rc: self._err(rc)
         return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
+
+    # ---- include/ngsid_hp.h
+    def hp_runs(self, centres: ReadSet, rs: ReadSet, grp_off, run_off, run_start, read_order=None, k=13, w=20, clip=False):
+        """ngsid_hp_runs: how long the runs run_start[run_off[g]:run_off[g + 1]] (ascending first positions of maximal runs of equal bytes of centre g) are in the reads
+        of the group -> (hist [n_runs, 2, HP_NBUCKET] uint32, strand [n_listed] int8).  hist[run_off[g] + r, s, l]: reads of strand s whose run, between two '=' flanks, has
+        l bases of the run's letter and nothing else (l = 15: 15 or more); bucket HP_OTHER: reads that span the run without giving a length.  Grouping, strands and counted
+        columns as in consensus_support().  There is no CPU implementation: a library without the entry point is an error."""
+        if centres.mem != MEM_HOST: raise ValueError("hp_runs takes the centres as a host read set")
+        self._need("ngsid_hp.h", "hp_runs")
+        grp_off, ro, ng = _groups(grp_off, read_order); run_off = np.ascontiguousarray(run_off, dtype=np.uint64)
+        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
+        if len(run_off) != ng + 1 or len(run_start) != int(run_off[-1]): raise ValueError("hp_runs: run_off has one entry per group + 1 and run_start run_off[-1] entries")
+        nr = int(run_off[-1])
+        hist = np.zeros((max(nr, 1), 2, HP_NBUCKET), dtype=np.uint32); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
+        rp = run_start if nr else np.zeros(1, dtype=np.uint32)
+        prm = SupportParams(int(k), int(w), 1 if clip else 0)
+        rc = self._call("hp_runs", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(run_off), _p(rp), _p(hist), _p(strand))
+        if rc: self._err(rc)
+        return hist[:nr], strand[:int(grp_off[-1])]
 
     # ---- include/ngsid_phase.h
     def phase_genotypes(self, centres: ReadSet, rs: ReadSet, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):

@@ -102,6 +102,13 @@ def build_parser():
     from . import variants as _variants
     p.add_argument('--variants', action='store_true', help='extension: the study-wide variant table of a multi-sample run. The final consensuses of all samples are compared with each other on the GPU (banded unit-cost edit distance, both strands) and joined by abundance into variants; writes <outfolder>/variants.fasta (the centroid sequences, variant_{v};size={reads};samples={n}), variant_table.tsv (variants x samples, read counts) and variant_members.tsv (sample, consensus id, reads, variant, dist, strand). No other output changes. Needs --consensus and --fastq_dir or --demux_sheet')
     _variants.add_flags(p)
+    from . import hp as _hp
+    p.add_argument('--hp_polish', action='store_true', help='extension: homopolymer finishing pass, a run-length vote and NOT medaka (--medaka stays refused: no neural polisher). For every homopolymer run of every final consensus (the polished one with --racon, else the draft) the GPU counts, per strand, how long that run is in every read that spans it between two matching flanks; a run is rewritten to the length most reads carry when the thresholds below are met. Letters never change and no run is removed. The consensus files carry the corrected sequence; writes <outfolder>/hp_polish.tsv (cluster_id pos letter old_len new_len round hist_plus hist_minus; with --fastq_dir / --demux_sheet one table per sample folder and <outfolder>/hp_polish_all.tsv). Support, classification, chimeras and haplotypes see the corrected sequences. Needs --consensus')
+    p.add_argument('--hp_rounds', type=int, default=2, help='extension: rounds of --hp_polish; a further round runs only on the consensuses the round before changed')
+    p.add_argument('--hp_min_depth', type=int, default=_hp.DEFAULTS["min_depth"], help='extension: --hp_polish calls a length only when at least this many reads give one (both strands)')
+    p.add_argument('--hp_min_share', type=float, default=_hp.DEFAULTS["min_share"], help='extension: the called length holds at least this share of those reads')
+    p.add_argument('--hp_min_margin', type=float, default=_hp.DEFAULTS["min_margin"], help="extension: and leads the consensus's own length by at least this share of them")
+    p.add_argument('--hp_min_strand_depth', type=int, default=_hp.DEFAULTS["min_strand_depth"], help="extension: a strand with at least this many reads of its own that does not prefer the called length to the consensus's vetoes the call")
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -267,8 +274,13 @@ def cli(argv=None):
         if not (getattr(args, "fastq_dir", None) or getattr(args, "demux_sheet", None)):
             logging.error("--variants joins the consensuses of several samples: it needs --fastq_dir or --demux_sheet."); sys.exit(1)
         _check_variants(args)
+    if getattr(args, "hp_polish", False):
+        if not args.consensus:
+            logging.error("--hp_polish corrects consensus sequences: it needs --consensus."); sys.exit(1)
+        if args.hp_rounds < 1 or args.hp_min_depth < 1 or not (0.0 <= args.hp_min_share <= 1.0) or not (0.0 <= args.hp_min_margin <= 1.0) or args.hp_min_strand_depth < 1:
+            logging.error("--hp_rounds, --hp_min_depth and --hp_min_strand_depth are at least 1, --hp_min_share and --hp_min_margin lie in [0, 1]."); sys.exit(1)
     if args.medaka:
-        logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon."); sys.exit(1)
+        logging.error("--medaka (neural polisher) is outside the accelerated hot path (see DESIGN.md); use --racon, and --hp_polish for a run-length vote on the homopolymers."); sys.exit(1)
     if args.k > 32 or args.k < 1:
         logging.error('k = %d is outside what the minimizer encoder of this build handles (1..32; the shared-minimizer table has rows for k = 10..30).' % args.k); sys.exit(1)
     if 100 < args.w or args.w < args.k:

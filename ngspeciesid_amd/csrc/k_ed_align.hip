@@ -23,12 +23,14 @@ typedef unsigned long long u64;
 #define CLIP_RUN 15
 // REC (ngsid_consensus_support): the traceback also RECORDS its path - one nibble per target position into the pair's row of `rec` (layout and codes: ngsid_internal.h), packed in a
 // register and stored as a dword per 8 positions.  The instances without REC are unchanged; only ngsid_launch_ed_align_rec launches the ones with it.
+// `pos` (REC only, optional - ngsid_hp_runs): the query index of every '=' / 'X' column as a uint16 per target position, row p at pos + p * rec_stride * 8.  The 64 lanes of the
+// traceback sit on 64 rows, so the indices are packed like the nibbles: four to a 64-bit register, one 8-byte store per 4 positions.  Null: the REC instances write what they did.
 template <int BMAX, bool WIN, bool CLIP = false, bool REC = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
 void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-byte units */, uint32_t mstride, uint32_t* __restrict__ work_ctr, int32_t* __restrict__ dist_out,
                 int8_t* __restrict__ hcar /* per wave mstride x 64: horizontal delta below the last block of a block group */,
                 int bandK /* > 0: Ukkonen band for distances <= bandK (single block group only) */, uint32_t* __restrict__ fail_list, uint32_t* __restrict__ fail_count,
-                uint32_t* __restrict__ rec /* REC only */, uint32_t rec_stride)
+                uint32_t* __restrict__ rec /* REC only */, uint32_t rec_stride, uint16_t* __restrict__ pos /* REC only, may be null */)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
@@ -188,6 +190,9 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
         int c_run = 0, c_x0q = -1, c_x0t = -1; bool c_started = false;       // CLIP state (unused otherwise)
         uint32_t r_acc = 0; int r_w = -1;                                    // REC state (unused otherwise): the dword being packed and its index in the row
         uint32_t* myrec = (REC && have) ? rec + p * (u64)rec_stride : nullptr;
+        u64 p_acc = 0; int p_w = -1;                                         // REC with positions: the four positions being packed and their index in the row
+        u64* mypos = (REC && have && pos) ? (u64*)(pos + p * (u64)rec_stride * 8) : nullptr;
+        auto pos_put = [&](int ti, int qi) { const int w_ = ti >> 2; if (w_ != p_w) { if (p_w >= 0) mypos[p_w] = p_acc; p_acc = 0; p_w = w_; } p_acc |= (u64)(uint32_t)qi << ((ti & 3) * 16); };
         auto rec_put = [&](int ti, uint32_t nib) { const int w_ = ti >> 3; if (w_ != r_w) { if (r_w >= 0) myrec[r_w] = r_acc; r_acc = 0; r_w = w_; } r_acc |= nib << ((ti & 7) * 4); };
         int wsn = j > 0 ? (j - 1) / W : 0, ws = wsn * W;       // window of the current target position, tracked without divisions
         // The lanes walk their paths IN LOCKSTEP OVER THE TARGET COLUMNS (round 3): in round jj every lane whose path stands in column jj handles that column (any
@@ -253,6 +258,7 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
                         if constexpr (REC) {
                             const int cq = ngsid_bcode(q[qi0]), ct = ngsid_bcode(t[ti0]);
                             rec_put(ti0, (cq < 4 ? (cq == ct ? (uint32_t)NGSID_REC_EQ : (uint32_t)NGSID_REC_SUB + cq) : (uint32_t)NGSID_REC_OTHER) | r_ins);
+                            if (mypos) pos_put(ti0, qi0);
                         }
                         --i; --j; break;
                     }
@@ -266,7 +272,7 @@ void k_ed_align(AlignJob J, ngsid_v4u* __restrict__ tb, u64 tb_per_wave /* 16-by
             }
         }
         i = 0;
-        if constexpr (REC) { if (r_w >= 0) myrec[r_w] = r_acc; }
+        if constexpr (REC) { if (r_w >= 0) myrec[r_w] = r_acc; if (p_w >= 0) mypos[p_w] = p_acc; }
         if (bpp && ok && cw >= 0 && cw < J.bp_windows) { bpp[cw * 4 + 0] = w_qf; bpp[cw * 4 + 1] = w_ql; bpp[cw * 4 + 2] = w_tf; bpp[cw * 4 + 3] = w_tl; }
         if constexpr (CLIP) {
             if (have && ok && c_started) {      // head side: everything in front of the first run of CLIP_RUN equal columns goes
@@ -297,7 +303,7 @@ static int32_t ed_reserve(ngsid_ctx* ctx, u64& want, u64 per_wave)
     }
 }
 
-struct EdRec { uint32_t* p = nullptr; uint32_t stride = 0; };       // REC instances: the path matrix
+struct EdRec { uint32_t* p = nullptr; uint32_t stride = 0; uint16_t* pos = nullptr; };       // REC instances: the path matrix, and the optional read positions
 template <int BMAX, bool WIN = false, bool CLIP = false, bool REC = false>
 static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, int32_t* dist_out, uint32_t ctr_slot = 14, int bandK = 0, uint32_t fail_slot = 15, uint32_t* fail_list = nullptr, EdRec rec = EdRec())
 {
@@ -317,7 +323,7 @@ static int32_t launch_ed(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen,
     if (ctx->aln_ctr.n < 16) HIPCHK(ctx, ctx->aln_ctr.alloc(16));
     HIPCHK(ctx, hipMemsetAsync(ctx->aln_ctr.p + ctr_slot, 0, sizeof(uint32_t), ctx->stream));
     { ProfScope ps_(ctx, REC ? "k_ed_align_rec" : "k_ed_align"); hipLaunchKernelGGL((k_ed_align<BMAX, WIN, CLIP, REC>), dim3((unsigned)want), dim3(64), lds, ctx->stream, job, ctx->ed_tb.p, per_wave, mstride, ctx->aln_ctr.p + ctr_slot, dist_out, ctx->ed_h.p,
-                                                            bandK, fail_list ? fail_list : ctx->ed_fail.p, ctx->aln_ctr.p + fail_slot, rec.p, rec.stride); }
+                                                            bandK, fail_list ? fail_list : ctx->ed_fail.p, ctx->aln_ctr.p + fail_slot, rec.p, rec.stride, rec.pos); }
     HIPCHK(ctx, hipGetLastError());
     return NGSID_OK;
 }
@@ -408,9 +414,9 @@ int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
     return ed_align_route<false>(ctx, job, max_qlen, max_tlen, dist_out, EdRec());
 }
 
-int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride)
+int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride, uint16_t* pos)
 {
     if (!rec || !job.span || (uint64_t)stride * 8 < max_tlen) NGSID_FAIL(ctx, NGSID_ERR_ARG, "internal: path matrix of the edit-distance aligner missing or too narrow");
-    EdRec r; r.p = rec; r.stride = stride;
+    EdRec r; r.p = rec; r.stride = stride; r.pos = pos;
     return ed_align_route<true>(ctx, job, max_qlen, max_tlen, nullptr, r);
 }

@@ -56,13 +56,13 @@ void k_support_sum(const uint32_t* __restrict__ rec, uint32_t stride, const int3
 // at least one pair (everything else of P is set: device allocations of the consumer); `chunk` after the store pass of every chunk, followed by a stream synchronisation.
 int32_t ngsid_rec_walk(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups,
                        const ngsid_support_params_t* prm, int8_t* strand, const std::function<int32_t(const RecPlan&)>& init,
-                       const std::function<int32_t(const RecPlan&)>& start, const std::function<int32_t(const RecPlan&, const RecChunk&)>& chunk)
+                       const std::function<int32_t(const RecPlan&)>& start, const std::function<int32_t(const RecPlan&, const RecChunk&)>& chunk, bool want_pos)
 {
     if (!prm) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
     if (prm->clip != 0 && prm->clip != 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_support_params_t.clip must be 0 or 1");
     GroupedReads S; NGSID_TRY(ngsid_groups_open(ctx, centres, reads, read_order, grp_off, n_groups, S));
     const DevReads& RD = S.RD; const uint32_t G = S.G, maxb = S.maxb; const uint64_t total = S.boff[G];
-    RecPlan P; P.G = G; P.boff = S.boff; P.total = total; P.maxb = maxb;
+    RecPlan P; P.G = G; P.boff = S.boff; P.total = total; P.maxb = maxb; P.bseq = S.bseq.data();
     int32_t rc = init(P); if (rc) return rc;
     if (strand) for (uint64_t x = 0; x < S.NL; ++x) strand[x] = -1;
     if (maxb > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "centre longer than %d", NGSID_MAX_CONSENSUS_LEN);
@@ -70,26 +70,28 @@ int32_t ngsid_rec_walk(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid
     NGSID_TRY(ngsid_groups_pairs(ctx, read_order, grp_off, prm->k, prm->w, S, strand));
     const uint64_t NP = S.NP; P.NP = NP; P.gbeg = S.gbeg;
     if (NP == 0 || total == 0) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); return NGSID_OK; }
-    P.pair_x = S.pair_x->data(); P.pair_group = S.pair_group->data();
-    DevBuf<uint32_t> d_pair_read, d_pair_group, d_rec; DevBuf<int32_t> d_span;
+    P.pair_x = S.pair_x->data(); P.pair_group = S.pair_group->data(); P.pair_read = S.pair_read->data(); P.h_orient = S.h_orient->data();
+    DevBuf<uint32_t> d_pair_read, d_pair_group, d_rec; DevBuf<int32_t> d_span; DevBuf<uint16_t> d_pos;
     NGSID_TRY(dev_put(ctx, d_pair_read, S.pair_read->data(), NP)); NGSID_TRY(dev_put(ctx, d_pair_group, S.pair_group->data(), NP));
     ngsid_reads_t br{S.bseq.data(), nullptr, S.boff.data(), G, NGSID_MEM_HOST, 0};
     DevReads BB; rc = ngsid_upload_reads(ctx, &br, &BB, false); if (rc) return rc;
     // ---- chunks of pairs under the byte budget of the path matrix (the share of the free device memory the POA batches take; option "support_budget_mb")
     const uint32_t stride = ((maxb + 63u) & ~63u) / 8;                    // dwords per row
     P.stride = stride; P.d_cen_seq = BB.seq; P.d_cen_off = BB.off; P.d_pair_group = d_pair_group.p;
+    P.d_oseq = ctx->pol_oseq.p; P.d_read_off = RD.off; P.d_pair_read = d_pair_read.p;
     rc = start(P); if (rc) return rc;
     const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
     const size_t budget = mb > 0 ? (size_t)mb << 20 : ngsid_mem_share(3, (size_t)256 << 20, (size_t)16 << 30, (size_t)16 << 30);
-    const uint64_t rows = std::min<uint64_t>(NP, std::max<uint64_t>(64, budget / ((size_t)stride * 4)));
+    const uint64_t rows = std::min<uint64_t>(NP, std::max<uint64_t>(64, budget / ((size_t)stride * (want_pos ? 20 : 4))));      // a row: 4 bits per position, and 2 bytes with the positions
     HIPCHK(ctx, d_rec.alloc(rows * stride)); HIPCHK(ctx, d_span.alloc(rows * 4));
+    if (want_pos) HIPCHK(ctx, d_pos.alloc(rows * stride * 8));
     for (uint64_t c0 = 0; c0 < NP; c0 += rows) {
         const uint64_t c1 = std::min(NP, c0 + rows);
         AlignJob J{};
         J.qseq = ctx->pol_oseq.p; J.qoff = RD.off; J.tseq = BB.seq; J.toff = BB.off; J.qidx = d_pair_read.p + c0; J.tidx = d_pair_group.p + c0; J.npairs = c1 - c0;
         J.span = d_span.p; J.clip = prm->clip;
-        rc = ngsid_launch_ed_align_rec(ctx, J, RD.maxlen, maxb, d_rec.p, stride); if (rc) return rc;
-        rc = chunk(P, RecChunk{d_rec.p, d_span.p, c0, c1}); if (rc) return rc;
+        rc = ngsid_launch_ed_align_rec(ctx, J, RD.maxlen, maxb, d_rec.p, stride, d_pos.p); if (rc) return rc;
+        rc = chunk(P, RecChunk{d_rec.p, d_span.p, c0, c1, d_pos.p}); if (rc) return rc;
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // the consumer's host lists are pageable and refilled by the next chunk
     }
     return NGSID_OK;

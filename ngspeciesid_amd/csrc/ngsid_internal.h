@@ -215,7 +215,9 @@ int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
 // The same alignments with the PATH of every pair recorded (ngsid_consensus_support, k_support.hip): row p of rec ([npairs][stride] dwords, stride >= ceil(max_tlen / 8)) receives one nibble
 // per target position the path of pair p passes, position t in bits 4 * (t & 7) of dword t >> 3: bits 0-2 = the column that consumes t (NGSID_REC_*), bit 3 = query-only columns follow it
 // directly.  Positions the path does not pass are left unwritten: read a row only inside the pair's span (job.span is required).
-int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride);
+// pos (optional, ngsid_hp_runs): row p of pos ([npairs][stride * 8] uint16, 8-byte aligned rows) receives the query index of the column at every target position whose nibble
+// is a match or mismatch column; the cells of the other positions hold nothing meaningful.
+int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride, uint16_t* pos = nullptr);
 enum { NGSID_REC_EQ = 1, NGSID_REC_SUB = 2 /* + code of the read's letter (A C G T) */, NGSID_REC_OTHER = 6 /* mismatch, read letter outside ACGT */, NGSID_REC_DEL = 7, NGSID_REC_INS = 8 };
 // poa_host.hip: first stage of ngsid_polish (strand by shared HPC minimizers + oriented copies of the reads in ctx->pol_oseq / pol_oqual); S keeps its device temporaries alive for the caller
 struct OrientBufs { DevBuf<uint32_t> d_rgroup; DevBuf<double> herr, rawerr; DevBuf<uint8_t> d_orient; };

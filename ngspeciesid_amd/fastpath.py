@@ -606,6 +606,8 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
             merged[x][2] = polished[x]
             if used_out is not None: used_out[c_id] = int(used[x])
         T["polish"] = T.get("polish", 0.0) + time() - t0
+    if getattr(args, "hp_polish", False):
+        _hp_polish(args, api, work, merged, polish_lists, clip, T)
     if getattr(args, "consensus_support", False) and merged:
         # --consensus_support: the read support of every base of the sequences just written, over the reads the polisher takes; clip as in the polisher (primer-trimmed flows)
         t0 = time()
@@ -625,6 +627,27 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
     if getattr(args, "split_haplotypes", False):
         _split_haplotypes(args, api, sr, work, merged, polish_lists, node_cap, clip, counts_of if getattr(args, "consensus_support", False) and merged else None, T)
     return merged
+
+
+def _hp_polish(args, api, work, merged, polish_lists, clip, T):
+    """--hp_polish: the run-length vote of hp.polish over the sequences just written (one Api.hp_runs call per round for all centres of the sample, over the reads the polisher
+    takes, clip as in the polisher) -> hp_polish.tsv; the centres that changed get their consensus file rewritten (racon_cl_id_{id}/consensus.fasta with racon's header tags
+    and the new length, without --racon consensus_reference_{id}.fasta) and carry the corrected sequence into support, haplotypes, classification and chimeras.  The files of
+    the polishing iterations stay what the polisher wrote."""
+    from . import hp
+    t0 = time()
+    racon = getattr(args, "racon", False) and args.racon_iter >= 0
+    seqs, changes = hp.polish(api, [m[2] for m in merged], work, polish_lists, k=args.k, w=args.w, clip=clip, **hp.policy_from_args(args)) if merged else ([], [])
+    for x, (nr, c_id, center, cs) in enumerate(merged):
+        if not changes[x]: continue
+        merged[x][2] = seqs[x]
+        path = os.path.join(args.outfolder, "racon_cl_id_{0}".format(c_id), "consensus.fasta") if racon else os.path.join(args.outfolder, "consensus_reference_{0}.fasta".format(c_id))
+        with open(path) as f: head = f.readline().rstrip("\n")
+        head = " ".join("LN:i:%d" % len(seqs[x]) if t.startswith("LN:i:") else t for t in head.split(" "))
+        with open(path, "w") as f: f.write("{0}\n{1}\n".format(head, seqs[x]))
+    args._hp_rows = hp.table_rows([m[1] for m in merged], changes)
+    hp.write_table(os.path.join(args.outfolder, "hp_polish.tsv"), args._hp_rows)
+    T["hp_polish"] = T.get("hp_polish", 0.0) + time() - t0
 
 
 def _split_haplotypes(args, api, sr, work, merged, polish_lists, node_cap, clip, supports, T):
@@ -814,6 +837,9 @@ def _main_samples(args, api):
         _chimera_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
     if getattr(args, "variants", False) and args.consensus:
         _variant_step(args, api, [(os.path.basename(a.outfolder), a.outfolder, out[os.path.basename(a.outfolder)]["centers"]) for a, _ in subs], T)
+    if getattr(args, "hp_polish", False) and args.consensus:
+        from . import hp
+        hp.write_table(os.path.join(args.outfolder, "hp_polish_all.tsv"), [(os.path.basename(a.outfolder),) + r for a, _ in subs for r in getattr(a, "_hp_rows", [])], ("sample",) + hp.TABLE_HEADER)
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 

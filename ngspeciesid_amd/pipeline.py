@@ -149,12 +149,14 @@ def _support_of(api, rs, seqs, lists, k, w):
 
 
 def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None):
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None, hp_polish=False, hp_kwargs=None):
     """Everything behind the clustering call, once for a list of samples: reads [seg_off[s], seg_off[s+1]) of rs are sample s, out[s] is its result dict (rep_of in read
     indices local to the sample) and bands[s] the band of its draft and polishing calls.  Per sample the cluster table and the selection with the sample's own cut-off, the
     reverse-complement bookkeeping and the pooled read lists; for all samples ONE alignment call, one consensus_support call and one search, and per distinct band one draft
     and one polishing call.  Fills centers (and support / classify, when asked for) into the dicts of the samples that have a centre above their cut-off and leaves the other
-    dicts as they are.  -> None when no sample has one, else (polished, pooled, prms): polished[s] the final sequences and pooled[s] the polisher's read lists (read numbers
+    dicts as they are.  hp_polish (extension, hp.py): the homopolymer run-length vote over the final sequences of ALL samples - one Api.hp_runs call per round - after
+    the polishing (or the draft, without it) and before support, classification and chimeras, which see the corrected sequences; hp_polish of a sample's dict = one change
+    table per centre.  -> None when no sample has one, else (polished, pooled, prms): polished[s] the final sequences and pooled[s] the polisher's read lists (read numbers
     of rs) of every centre of sample s, prms[band] the (draft, polish or None) parameter structs of that band's calls."""
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
     single_below = SINGLE_BELOW if single_below is None else single_below
@@ -207,6 +209,14 @@ def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ra
             pol, _ = api.polish(ReadSet.from_strings([m[2] for s in ss for m in merged[s]]), rs, group_offsets(lists), prms[bnd][1], read_order=np.concatenate(lists))      # (dealt to two contexts when it pays: _capi.Api lanes)
             polished.update(zip(ss, _deal(pol, [len(merged[s]) for s in ss])))
         T["polish"] = T.get("polish", 0.0) + time.perf_counter() - t0
+    if hp_polish:
+        from . import hp as hp_mod
+        t0 = time.perf_counter()
+        sizes = [len(merged[s]) for s in tab]
+        new, changes = hp_mod.polish(api, [q for s in tab for q in polished[s]], rs, [l for s in tab for l in pooled[s]], k=k, w=w, **(hp_kwargs or {}))
+        for s, seqs_, ch in zip(tab, _deal(new, sizes), _deal(changes, sizes)):
+            polished[s] = list(seqs_); out[s]["hp_polish"] = ch
+        T["hp_polish"] = T.get("hp_polish", 0.0) + time.perf_counter() - t0
     for s in tab:
         reps = tab[s][0]
         out[s]["centers"] = [(m[0], m[1], m[2], polished[s][i], [int(reps[ci]) for ci in m[3]]) for i, m in enumerate(merged[s])]
@@ -236,7 +246,8 @@ def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ra
 def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, w=20, abundance_ratio=0.1,
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
-                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None, chimeras=False, chimera_kwargs=None):
+                 strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None, chimeras=False, chimera_kwargs=None,
+                 hp_polish=False, hp_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
@@ -249,7 +260,10 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     is what split_haplotypes=False returns.
     chimeras=True (extension; chimera.py, include/ngsid_chimera.h): also chimeras = one dict per centre (chimera.describe: chimeric, the best single parent, the best
     two-parent model and its breakpoint interval, parents as centre numbers) - every centre's final sequence modelled from the more abundant centres, both strands
-    (chimera_kwargs: min_abskew, min_gain, max_model_frac); every other key is what chimeras=False returns."""
+    (chimera_kwargs: min_abskew, min_gain, max_model_frac); every other key is what chimeras=False returns.
+    hp_polish=True (extension; hp.py, include/ngsid_hp.h): the homopolymer finishing pass - a run-length vote of the pooled reads over every run of every final sequence, not
+    a neural polisher - rewrites centers[..][3] before support, classification, chimeras and haplotypes see it; also hp_polish = one list per centre of
+    dict(round, pos, letter, old, new, hist [2, 17]) for the runs it changed (hp_kwargs: rounds and the thresholds of hp.call)."""
     T = timings if timings is not None else {}
     t0 = time.perf_counter()
     prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
@@ -268,12 +282,13 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     if classify is not None: res["classify"] = []                               # what stays without a centre: nothing to name, nothing to split
     if split_haplotypes: res["haplotypes"] = []
     if chimeras: res["chimeras"] = []
+    if hp_polish: res["hp_polish"] = []
     if not do_consensus:
         return res
     # one sample, reads [0, n); band goes through as it is: for band <= 0 the library applies the POA_BAND64_MAXLEN rule to the reads of the call, which here are the sample's
     # (reading the lengths of a device-resident set here would cost a copy of its offsets to the host in every step)
     stages = _consensus_stages(api, rs, score, [0, n], [res], [band], T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                               do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs)
+                               do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs)
     if split_haplotypes and stages is not None:
         from . import phase
         t0 = time.perf_counter()
@@ -309,7 +324,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
                          strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None,
-                         variants=False, variant_kwargs=None):
+                         variants=False, variant_kwargs=None, hp_polish=False, hp_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
@@ -319,7 +334,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     key of run_hot_path per sample, ALL samples in one model call (parents within a sample only).  variants=True (extension; variants.py, include/ngsid_near.h):
     also variants = dict(members = one dict(variant, dist, strand) per centre of the sample, table = the study-wide table of variants.build, the same object in every
     sample's dict): the final sequences of ALL samples in one near-pairs call, clustered by abundance (variant_kwargs: identity, max_dist, both_strands, wide_max_dist - the last replaces max_dist and takes the wide kernels); every other key
-    is what variants=False returns.  strand_aware is not supported here (ValueError)."""
+    is what variants=False returns.  hp_polish=True: the hp_polish key of run_hot_path per sample, ONE Api.hp_runs call per round for all samples; the variants see the
+    corrected sequences.  strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     T = timings if timings is not None else {}
@@ -335,13 +351,15 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
         for o in out: o["chimeras"] = []
     if variants:
         for o in out: o["variants"] = None
+    if hp_polish:
+        for o in out: o["hp_polish"] = []
     if not do_consensus:
         return out
     t0 = time.perf_counter()
     bands = _bands_alone(rs, so, band)
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs)
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs)
     if variants:
         from . import variants as variants_mod
         t0 = time.perf_counter()
