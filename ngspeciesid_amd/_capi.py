@@ -61,6 +61,10 @@ class RefDbParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("w", C.c_int32)]                                  # include/ngsid_classify.h ngsid_refdb_params_t
 
 
+class UmiParams(C.Structure):
+    _fields_ = [("max_dist", C.c_int32), ("seed_len", C.c_int32)]                    # include/ngsid_umi.h ngsid_umi_params_t
+
+
 class ClassifyParams(C.Structure):
     _fields_ = [("top_k", C.c_int32), ("min_shared", C.c_int32)]                     # include/ngsid_classify.h ngsid_classify_params_t
 
@@ -74,6 +78,7 @@ CHIMERA_STRIP = 64 * CHIMERA_ROWS                                               
 MAX_CONSENSUS_LEN = 16384                                                           # include/ngsid.h NGSID_MAX_CONSENSUS_LEN
 NEAR_MAX_DIST, NEAR_BOTH_STRANDS = 31, 1                                            # include/ngsid_near.h NGSID_NEAR_MAX_DIST, NGSID_NEAR_BOTH_STRANDS
 NEAR_WIDE_MAX_DIST = 255                                                            # include/ngsid_near.h NGSID_NEAR_WIDE_MAX_DIST
+UMI_MAX_LEN, UMI_MAX_DIST = 64, 8                                                   # include/ngsid_umi.h NGSID_UMI_MAX_LEN, NGSID_UMI_MAX_DIST
 
 
 def chimera_profile_offsets(query_lens, pair_off):
@@ -871,6 +876,43 @@ class Api:
                 e.needed = int(needed.value); raise
         n = int(found.value)
         return pi[:n], pj[:n], dist[:n], strand[:n]
+
+    # ---- include/ngsid_umi.h
+    def umi_pairs(self, seqs, max_dist, seed_len, cap=None):
+        """ngsid_umi_pairs: every pair i < j of seqs (at most UMI_MAX_LEN letters each) within max_dist edits (0 .. UMI_MAX_DIST), found by the seeded search ->
+        (pair_i uint32, pair_j uint32, dist uint8), in ascending (i, j) order: what near_pairs(seqs, max_dist, both_strands=False) returns without its strand array,
+        whatever seed_len (4 .. 16) is.  The count call (cap = 0), then the fill call; cap: one call with room for that many pairs (NgsidError NGSID_ERR_CAPACITY with
+        .needed when there are more).  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_umi.h", "umi_pairs", "umi_centroids")
+        rs = _as_reads(seqs)
+        prm = UmiParams(int(max_dist), int(seed_len))
+        found, needed = C.c_uint64(0), C.c_uint64(0)
+        if cap is None:
+            rc = self._call("umi_pairs", C.byref(rs.c), C.byref(prm), None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
+            if rc and rc != -4: self._err(rc)
+            cap = int(needed.value)
+        pi = np.zeros(max(cap, 1), dtype=np.uint32); pj = np.zeros(max(cap, 1), dtype=np.uint32); dist = np.zeros(max(cap, 1), dtype=np.uint8)
+        rc = self._call("umi_pairs", C.byref(rs.c), C.byref(prm), _p(pi), _p(pj), _p(dist), C.c_uint64(cap), C.byref(found), C.byref(needed))
+        if rc:
+            try: self._err(rc)
+            except NgsidError as e:
+                e.needed = int(needed.value); raise
+        n = int(found.value)
+        return pi[:n], pj[:n], dist[:n]
+
+    def umi_centroids(self, pair_i, pair_j, order):
+        """ngsid_umi_centroids (a host function): the nodes 0 .. len(order) - 1 walked in `order`, each joining the earliest-founded centroid it shares a listed pair
+        with or founding a bin -> (bin_of int32 [n], centroid uint32 [n_bins] in founding order)"""
+        self._need("ngsid_umi.h", "umi_pairs", "umi_centroids")
+        pi = np.ascontiguousarray(pair_i, dtype=np.uint32); pj = np.ascontiguousarray(pair_j, dtype=np.uint32); od = np.ascontiguousarray(order, dtype=np.uint32)
+        if len(pi) != len(pj): raise ValueError("umi_centroids: pair_i and pair_j hold one entry per pair")
+        n = len(od)
+        bin_of = np.full(max(n, 1), -1, dtype=np.int32); cent = np.zeros(max(n, 1), dtype=np.uint32); nb = C.c_uint32(0)
+        f = self._fn("umi_centroids")
+        rc = f(_p(pi if len(pi) else np.zeros(1, np.uint32)), _p(pj if len(pj) else np.zeros(1, np.uint32)), C.c_uint64(len(pi)), _p(od if n else np.zeros(1, np.uint32)), C.c_uint32(n),
+               _p(bin_of), _p(cent), C.byref(nb))
+        if rc: raise NgsidError(rc, "umi_centroids: an index out of range, a pair (x, x), or an order that is no permutation")
+        return bin_of[:n], cent[:int(nb.value)].copy()
 
 
 class RefDb:

@@ -48,7 +48,7 @@ DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are h
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
-                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample; `variants --fasta A B ... --outfolder O` (first argument `variants`) writes the files of --variants with every FASTA taken as one sample",
+                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample; `variants --fasta A B ... --outfolder O` (first argument `variants`) writes the files of --variants with every FASTA taken as one sample; `umi --fastq X --outfolder O --umi_fwd PRE,POST --umi_rev PRE,POST` (first argument `umi`; `umi --help`) bins the reads of a UMI protocol by molecule and writes one polished consensus per bin",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--version', action='version', version='%(prog)s 0.3.1-mi355x')
     p.add_argument('--debug', action='store_true')
@@ -160,6 +160,16 @@ def _variants_subparser(cf):
     return cf
 
 
+def _umi_subparser(cf):
+    """the `umi` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import umi as _umi
+    cf.add_argument('--fastq', type=str, required=True, help='reads of a UMI protocol: adapter - flank - UMI - primer - amplicon - primer\' - UMI\' - flank\'')
+    cf.add_argument('--outfolder', type=str, required=True, help='where umi_consensus.fasta, umi_bins.tsv, umi_reads.tsv and umi_summary.tsv go')
+    _umi.add_flags(cf)
+    cf.set_defaults(which='umi')
+    return cf
+
+
 def _check_variants(args):
     from . import variants as _variants
     err = _variants.check_args(args)
@@ -191,6 +201,8 @@ def cli(argv=None):
         args = _chimeras_subparser(argparse.ArgumentParser(prog='chimeras', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'variants':
         args = _variants_subparser(argparse.ArgumentParser(prog='variants', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'umi':
+        args = _umi_subparser(argparse.ArgumentParser(prog='umi', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
         args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.DEBUG if getattr(args, 'debug', False) else logging.INFO, format='%(message)s')
@@ -220,6 +232,16 @@ def cli(argv=None):
         from . import variants as _variants
         tab = _variants.variants_fasta(args)
         logging.info("Wrote %d variants of %d sequences to %s." % (len(tab["variants"]), len(tab["members"]), args.outfolder))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'umi':
+        from . import umi as _umi
+        err = _umi.check_args(args)
+        if err:
+            logging.error(err); sys.exit(1)
+        if not os.path.isfile(args.fastq):
+            logging.error("--fastq %s is not a file." % args.fastq); sys.exit(1)
+        res = _umi.umi_fastq(args)
+        logging.info("Wrote %d UMI consensus sequences of %d bins (%d reads) to %s." % (len(res["kept"]), len(res["bins"]["centroids"]), len(res["status"]), args.outfolder))
         sys.exit(0)
     if args.ont and args.isoseq:
         logging.error("Arguments mutually exclusive, specify either --isoseq or --ont. "); sys.exit()

@@ -565,7 +565,7 @@ extern "C" int32_t ngsid_reads_release(ngsid_ctx* ctx, ngsid_reads_t* dev)
 extern "C" int32_t ngsid_ctx_option(ngsid_ctx* ctx, const char* name, int64_t value)
 {
     if (!ctx || !name) return NGSID_ERR_ARG;
-    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs"};
+    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs", "umi_chunk_seqs"};
     for (const char* k : known) if (!strcmp(k, name)) { ctx->options[name] = (long long)value; return NGSID_OK; }
     if (!strcmp(name, "touch")) {        // one trivial operation on the context's stream (+ wait): a caller that spends milliseconds on the host between two calls keeps the device out of its idle state
         if (ctx->mzc_fp.n < 2) HIPCHK(ctx, ctx->mzc_fp.alloc(2));
@@ -580,6 +580,8 @@ extern "C" int32_t ngsid_ctx_option(ngsid_ctx* ctx, const char* name, int64_t va
         ctx->mzc.valid = false; ctx->mzc_cnt.release(); ctx->mzc_hlen.release(); ctx->mz_off.release(); ctx->mz_scode.release(); ctx->mz_spos.release();
         ctx->pol_mzcode.release(); ctx->pol_mzpos.release(); ctx->pol_oseq.release(); ctx->pol_oqual.release(); ctx->pol_valid.release(); ctx->pol_bp.release(); ctx->pol_lay.release(); ctx->cl_cnt.release(); ctx->cls_cnt.release(); ctx->chm_prof.release(); ctx->chm_bnd.release();
         ctx->near_pat.release(); ctx->near_txt.release(); ctx->near_key.release(); ctx->near_ds.release();
+        ctx->umi_pack.release(); ctx->umi_key.release(); ctx->umi_skey.release(); ctx->umi_tile.release(); ctx->umi_tsum.release(); ctx->umi_found.release(); ctx->umi_sfound.release();
+        ctx->umi_val.release(); ctx->umi_sval.release(); ctx->umi_lo.release(); ctx->umi_cnt.release(); ctx->umi_tidx.release(); ctx->umi_dist.release(); ctx->umi_sdist.release(); ctx->umi_tmp.release();
         ngsid_pool_release_all();
         return NGSID_OK;
     }

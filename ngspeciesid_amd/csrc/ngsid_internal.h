@@ -122,7 +122,10 @@ struct ngsid_ctx {
     DevBuf<uint32_t> cls_cnt;                                  // count rows [query][strand][reference] of ngsid_classify_search's current chunk (grow-only; k_classify.hip)
     DevBuf<uint16_t> chm_prof; DevBuf<uint32_t> chm_bnd;       // ngsid_chimera_model (k_chimera.hip): the F / B profiles of the current chunk of queries, the strip boundaries of its waves (grow-only)
     DevBuf<uint32_t> near_pat, near_txt; DevBuf<uint64_t> near_key; DevBuf<uint16_t> near_ds;      // ngsid_ed_within_batch / ngsid_near_pairs and their wide twins (k_near.hip): the pattern planes and the text planes of the call's sequences, the found pairs of the current chunk (grow-only)
-    std::vector<struct ngsid_refdb*> refdbs;                   // reference libraries built in this context (ngsid_refdb_build) and not released yet: they go with the context
+    // ngsid_umi_pairs (k_umi.hip): the letter planes of the set (four words per sequence), the seed index (keys and sequence numbers, unsorted and sorted), the ranges,
+    // tile sums and tile list of the current chunk of queries, the found pairs (unsorted and sorted) and the radix sorts' temporary storage (all grow-only)
+    DevBuf<uint64_t> umi_pack, umi_key, umi_skey, umi_tile, umi_tsum, umi_found, umi_sfound; DevBuf<uint32_t> umi_val, umi_sval, umi_lo, umi_cnt, umi_tidx; DevBuf<uint8_t> umi_dist, umi_sdist, umi_tmp;
+    std::vector<struct ngsid_refdb*> refdbs;                  // reference libraries built in this context (ngsid_refdb_build) and not released yet: they go with the context
 };
 void ngsid_refdb_release_all(ngsid_ctx* ctx);                  // k_classify.hip: ngsid_destroy releases the libraries the caller left
 
