@@ -200,6 +200,11 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _p0(a):
+    """_p of a list the C-ABI takes no null for: an empty array is passed as one zero element of its dtype"""
+    return None if a is None else _p(a if len(a) else np.zeros(1, a.dtype))
+
+
 def _groups(grp_off, read_order):
     """-> (grp_off uint64, read_order uint32 or None, n_groups) as the C-ABI takes them"""
     grp_off = np.ascontiguousarray(grp_off, dtype=np.uint64)
@@ -448,6 +453,31 @@ class Api:
         if not all(hasattr(self.lib, self.prefix + n) for n in names):
             raise NgsidError(-2, "the bound library does not export %s (include/%s): rebuild it from this tree" % (" / ".join(self.prefix + n for n in names), header))
 
+    def _found_list(self, entry, head, n_out, alloc, cap, tail=()):
+        """the count-then-fill protocol of a call that returns a list of unknown length: entry(*head, *outputs, cap, *tail, &needed).  cap None: the count call (no
+        outputs, cap 0; NGSID_ERR_CAPACITY is its answer whenever something was found), then the fill call with room for what it counted; a cap: that fill call alone.
+        alloc(cap) -> the n_out output arrays.  -> (outputs, needed); a capacity error of the fill call carries .needed"""
+        needed = C.c_uint64(0)
+        if cap is None:
+            rc = self._call(entry, *head, *[None] * n_out, C.c_uint64(0), *tail, C.byref(needed))
+            if rc and rc != -4: self._err(rc)
+            cap = needed.value
+        outs = alloc(int(cap))
+        rc = self._call(entry, *head, *[_p(a) for a in outs], C.c_uint64(int(cap)), *tail, C.byref(needed))
+        if rc:
+            try: self._err(rc)
+            except NgsidError as e:
+                e.needed = int(needed.value); raise
+        return outs, int(needed.value)
+
+    def _support_head(self, what, header, names, centres, grp_off, read_order, k, w, clip):
+        """what consensus_support, hp_runs and phase_genotypes begin with: the centres are a host set, the entry points exist -> (grp_off, read_order, n_groups as the
+        C-ABI takes them, strand [n_listed] int8 filled with -1, SupportParams)"""
+        if centres.mem != MEM_HOST: raise ValueError("%s takes the centres as a host read set" % what)
+        self._need(header, *names)
+        grp_off, ro, ng = _groups(grp_off, read_order)
+        return grp_off, ro, ng, np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8), SupportParams(int(k), int(w), 1 if clip else 0)
+
     # ---- (f1)
     def score_reads(self, rs: ReadSet, k, q_threshold=7.0):
         n = rs.n
@@ -656,12 +686,9 @@ class Api:
         (counts [total, 8] uint32 in SUPPORT_COLUMNS order, cen_off [n_groups + 1], n_used [n_groups], strand [n_listed] int8: 0, 1, -1 = no shared minimizer).
         Rows cen_off[g] .. cen_off[g + 1] of counts are centre g.  Grouping as in polish(); clip=True counts a read between its first and last run of 15 equal
         columns only (the polisher's aln_mode 3).  There is no CPU implementation: a library without the entry point is an error."""
-        if centres.mem != MEM_HOST: raise ValueError("consensus_support takes the centres as a host read set")
-        self._need("ngsid_support.h", "consensus_support")
-        grp_off, ro, ng = _groups(grp_off, read_order)
+        grp_off, ro, ng, strand, prm = self._support_head("consensus_support", "ngsid_support.h", ("consensus_support",), centres, grp_off, read_order, k, w, clip)
         cen_off = centres.off.copy(); total = int(cen_off[-1]) if len(cen_off) else 0
-        counts = np.zeros((total, 8), dtype=np.uint32); used = np.zeros(max(ng, 1), dtype=np.uint64); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
-        prm = SupportParams(int(k), int(w), 1 if clip else 0)
+        counts = np.zeros((total, 8), dtype=np.uint32); used = np.zeros(max(ng, 1), dtype=np.uint64)
         rc = self._call("consensus_support", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(counts), _p(used), _p(strand))
         if rc: self._err(rc)
         return counts, cen_off, used[:ng], strand[:int(grp_off[-1])]
@@ -672,16 +699,12 @@ class Api:
         of the group -> (hist [n_runs, 2, HP_NBUCKET] uint32, strand [n_listed] int8).  hist[run_off[g] + r, s, l]: reads of strand s whose run, between two '=' flanks, has
         l bases of the run's letter and nothing else (l = 15: 15 or more); bucket HP_OTHER: reads that span the run without giving a length.  Grouping, strands and counted
         columns as in consensus_support().  There is no CPU implementation: a library without the entry point is an error."""
-        if centres.mem != MEM_HOST: raise ValueError("hp_runs takes the centres as a host read set")
-        self._need("ngsid_hp.h", "hp_runs")
-        grp_off, ro, ng = _groups(grp_off, read_order); run_off = np.ascontiguousarray(run_off, dtype=np.uint64)
-        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
+        grp_off, ro, ng, strand, prm = self._support_head("hp_runs", "ngsid_hp.h", ("hp_runs",), centres, grp_off, read_order, k, w, clip)
+        run_off = np.ascontiguousarray(run_off, dtype=np.uint64); run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
         if len(run_off) != ng + 1 or len(run_start) != int(run_off[-1]): raise ValueError("hp_runs: run_off has one entry per group + 1 and run_start run_off[-1] entries")
         nr = int(run_off[-1])
-        hist = np.zeros((max(nr, 1), 2, HP_NBUCKET), dtype=np.uint32); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
-        rp = run_start if nr else np.zeros(1, dtype=np.uint32)
-        prm = SupportParams(int(k), int(w), 1 if clip else 0)
-        rc = self._call("hp_runs", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(run_off), _p(rp), _p(hist), _p(strand))
+        hist = np.zeros((max(nr, 1), 2, HP_NBUCKET), dtype=np.uint32)
+        rc = self._call("hp_runs", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(run_off), _p0(run_start), _p(hist), _p(strand))
         if rc: self._err(rc)
         return hist[:nr], strand[:int(grp_off[-1])]
 
@@ -691,16 +714,12 @@ class Api:
         its group -> (geno uint8, geno_off [n_groups + 1], strand [n_listed] int8).  geno[geno_off[g]:geno_off[g + 1]].reshape(R_g, S_g) is group g, [listed read][site]:
         0-3 = A C G T, GENO_DEL, GENO_OTHER (mismatch with a read base outside ACGT), GENO_NONE (not counted).  Grouping, strands and counted columns as in consensus_support().
         There is no CPU implementation: a library without the entry point is an error."""
-        if centres.mem != MEM_HOST: raise ValueError("phase_genotypes takes the centres as a host read set")
-        self._need("ngsid_phase.h", "phase_genotypes", "phase_pair_tables", "phase_assign")
-        grp_off, ro, ng = _groups(grp_off, read_order); site_off = np.ascontiguousarray(site_off, dtype=np.uint64)
-        site_pos = np.ascontiguousarray(site_pos, dtype=np.uint32)
+        grp_off, ro, ng, strand, prm = self._support_head("phase_genotypes", "ngsid_phase.h", ("phase_genotypes", "phase_pair_tables", "phase_assign"), centres, grp_off, read_order, k, w, clip)
+        site_off = np.ascontiguousarray(site_off, dtype=np.uint64); site_pos = np.ascontiguousarray(site_pos, dtype=np.uint32)
         if len(site_off) != ng + 1 or len(site_pos) != int(site_off[-1]): raise ValueError("phase_genotypes: site_off has one entry per group + 1 and site_pos site_off[-1] entries")
         geno_off, _ = phase_offsets(grp_off, site_off)
-        geno = np.full(max(int(geno_off[-1]), 1), GENO_NONE, dtype=np.uint8); strand = np.full(max(int(grp_off[-1]), 1), -1, dtype=np.int8)
-        sp = site_pos if len(site_pos) else np.zeros(1, dtype=np.uint32)
-        prm = SupportParams(int(k), int(w), 1 if clip else 0)
-        rc = self._call("phase_genotypes", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(site_off), _p(sp), _p(geno), _p(strand))
+        geno = np.full(max(int(geno_off[-1]), 1), GENO_NONE, dtype=np.uint8)
+        rc = self._call("phase_genotypes", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(site_off), _p0(site_pos), _p(geno), _p(strand))
         if rc: self._err(rc)
         return geno[:int(geno_off[-1])], geno_off, strand[:int(grp_off[-1])]
 
@@ -713,7 +732,7 @@ class Api:
         geno = np.ascontiguousarray(geno, dtype=np.uint8)
         if len(geno) != int(geno_off[-1]): raise ValueError("phase_pair_tables: geno has %d entries, the offsets ask for %d" % (len(geno), int(geno_off[-1])))
         tables = np.zeros(max(int(tab_off[-1]), 1), dtype=np.uint32)
-        rc = self._call("phase_pair_tables", _p(geno if len(geno) else np.zeros(1, np.uint8)), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(tables))
+        rc = self._call("phase_pair_tables", _p0(geno), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(tables))
         if rc: self._err(rc)
         return tables[:int(tab_off[-1])], tab_off
 
@@ -729,7 +748,7 @@ class Api:
         if len(geno) != int(geno_off[-1]) or len(hal) != need or len(hap_off) != len(grp_off): raise ValueError("phase_assign: geno / hap_alleles do not match the offsets")
         nl = int(grp_off[-1])
         best = np.full(max(nl, 1), -1, dtype=np.int8); dist = np.full(max(nl, 1), 255, dtype=np.uint8); dist2 = np.full(max(nl, 1), 255, dtype=np.uint8)
-        rc = self._call("phase_assign", _p(geno if len(geno) else np.zeros(1, np.uint8)), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(hap_off), _p(hal if len(hal) else np.zeros(1, np.uint8)),
+        rc = self._call("phase_assign", _p0(geno), _p(grp_off), _p(site_off), C.c_uint64(len(grp_off) - 1), _p(hap_off), _p0(hal),
                         _p(best), _p(dist), _p(dist2))
         if rc: self._err(rc)
         return best[:nl], dist[:nl], dist2[:nl]
@@ -761,18 +780,9 @@ class Api:
         pt = _as_reads(patterns)
         if pt.mem != MEM_HOST: raise ValueError("demux_scan takes the patterns as a host read set")
         prm = DemuxScanParams(int(max_ed), 1 if iupac else 0)
-        needed = C.c_uint64(0)
-        if cap is None:
-            rc = self._call("demux_scan", C.byref(rs.c), C.byref(pt.c), C.byref(prm), None, None, C.c_uint64(0), C.byref(needed))
-            if rc and rc != -4: self._err(rc)
-            cap = int(needed.value)
-        hit_off = np.zeros(rs.n + 1, dtype=np.uint64); hits = np.zeros((max(int(cap), 1), 3), dtype=np.int32)
-        rc = self._call("demux_scan", C.byref(rs.c), C.byref(pt.c), C.byref(prm), _p(hit_off), _p(hits), C.c_uint64(int(cap)), C.byref(needed))
-        if rc:
-            try: self._err(rc)
-            except NgsidError as e:
-                e.needed = int(needed.value); raise
-        return hit_off, hits[:int(needed.value)]
+        (hit_off, hits), n = self._found_list("demux_scan", (C.byref(rs.c), C.byref(pt.c), C.byref(prm)), 2,
+                                              lambda c: (np.zeros(rs.n + 1, dtype=np.uint64), np.zeros((max(c, 1), 3), dtype=np.int32)), cap)
+        return hit_off, hits[:n]
 
     # ---- include/ngsid_classify.h
     def refdb_build(self, refs, k=13, w=20) -> "RefDb":
@@ -818,7 +828,7 @@ class Api:
             if qs.mem != MEM_HOST: raise ValueError("chimera_model: profiles=True takes the queries as a host read set (their lengths size the result)")
             prof_off = chimera_profile_offsets(np.diff(qs.off.astype(np.int64)), po)
             prof = np.zeros(max(int(prof_off[-1]), 1), dtype=np.uint16)
-        rc = self._call("chimera_model", C.byref(qs.c), C.byref(ps.c), _p(po), _p(pp if len(pp) else np.zeros(1, np.uint32)), _p(pg if pg is None or len(pg) else np.zeros(1, np.int32)), _p(fields if qs.n else np.zeros(CHIMERA_NFIELD, np.int32)), _p(prof))
+        rc = self._call("chimera_model", C.byref(qs.c), C.byref(ps.c), _p(po), _p0(pp), _p0(pg), _p0(fields), _p(prof))
         if rc: self._err(rc)
         return (fields, prof[:int(prof_off[-1])], prof_off) if profiles else fields
 
@@ -842,7 +852,7 @@ class Api:
         if len(qi) != len(ti): raise ValueError("ed_within: q_idx and t_idx hold one entry per pair")
         n = len(qi)
         dist = np.full(max(n, 1), -1, dtype=np.int32); strand = np.zeros(max(n, 1), dtype=np.uint8)
-        rc = self._call(entry, C.byref(qs.c), C.byref(ts.c), _p(qi if n else np.zeros(1, np.uint32)), _p(ti if n else np.zeros(1, np.uint32)), C.c_uint64(n),
+        rc = self._call(entry, C.byref(qs.c), C.byref(ts.c), _p0(qi), _p0(ti), C.c_uint64(n),
                         C.c_int32(int(max_dist)), C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0), _p(dist), _p(strand))
         if rc: self._err(rc)
         return dist[:n], strand[:n]
@@ -862,20 +872,10 @@ class Api:
 
     def _near_pairs(self, entry, seqs, max_dist, both_strands, cap):
         rs = _as_reads(seqs)
-        flags = C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0)
-        found, needed = C.c_uint64(0), C.c_uint64(0)
-        if cap is None:
-            rc = self._call(entry, C.byref(rs.c), C.c_int32(int(max_dist)), flags, None, None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
-            if rc and rc != -4: self._err(rc)
-            cap = int(needed.value)
-        pi = np.zeros(max(cap, 1), dtype=np.uint32); pj = np.zeros(max(cap, 1), dtype=np.uint32); dist = np.zeros(max(cap, 1), dtype=np.uint8); strand = np.zeros(max(cap, 1), dtype=np.uint8)
-        rc = self._call(entry, C.byref(rs.c), C.c_int32(int(max_dist)), flags, _p(pi), _p(pj), _p(dist), _p(strand), C.c_uint64(cap), C.byref(found), C.byref(needed))
-        if rc:
-            try: self._err(rc)
-            except NgsidError as e:
-                e.needed = int(needed.value); raise
-        n = int(found.value)
-        return pi[:n], pj[:n], dist[:n], strand[:n]
+        found = C.c_uint64(0)
+        outs, _ = self._found_list(entry, (C.byref(rs.c), C.c_int32(int(max_dist)), C.c_uint32(NEAR_BOTH_STRANDS if both_strands else 0)), 4,
+                                   lambda c: tuple(np.zeros(max(c, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8, np.uint8)), cap, tail=(C.byref(found),))
+        return tuple(a[:int(found.value)] for a in outs)
 
     # ---- include/ngsid_umi.h
     def umi_pairs(self, seqs, max_dist, seed_len, cap=None):
@@ -886,19 +886,9 @@ class Api:
         self._need("ngsid_umi.h", "umi_pairs", "umi_centroids")
         rs = _as_reads(seqs)
         prm = UmiParams(int(max_dist), int(seed_len))
-        found, needed = C.c_uint64(0), C.c_uint64(0)
-        if cap is None:
-            rc = self._call("umi_pairs", C.byref(rs.c), C.byref(prm), None, None, None, C.c_uint64(0), C.byref(found), C.byref(needed))
-            if rc and rc != -4: self._err(rc)
-            cap = int(needed.value)
-        pi = np.zeros(max(cap, 1), dtype=np.uint32); pj = np.zeros(max(cap, 1), dtype=np.uint32); dist = np.zeros(max(cap, 1), dtype=np.uint8)
-        rc = self._call("umi_pairs", C.byref(rs.c), C.byref(prm), _p(pi), _p(pj), _p(dist), C.c_uint64(cap), C.byref(found), C.byref(needed))
-        if rc:
-            try: self._err(rc)
-            except NgsidError as e:
-                e.needed = int(needed.value); raise
-        n = int(found.value)
-        return pi[:n], pj[:n], dist[:n]
+        found = C.c_uint64(0)
+        outs, _ = self._found_list("umi_pairs", (C.byref(rs.c), C.byref(prm)), 3, lambda c: tuple(np.zeros(max(c, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8)), cap, tail=(C.byref(found),))
+        return tuple(a[:int(found.value)] for a in outs)
 
     def umi_centroids(self, pair_i, pair_j, order):
         """ngsid_umi_centroids (a host function): the nodes 0 .. len(order) - 1 walked in `order`, each joining the earliest-founded centroid it shares a listed pair
@@ -909,7 +899,7 @@ class Api:
         n = len(od)
         bin_of = np.full(max(n, 1), -1, dtype=np.int32); cent = np.zeros(max(n, 1), dtype=np.uint32); nb = C.c_uint32(0)
         f = self._fn("umi_centroids")
-        rc = f(_p(pi if len(pi) else np.zeros(1, np.uint32)), _p(pj if len(pj) else np.zeros(1, np.uint32)), C.c_uint64(len(pi)), _p(od if n else np.zeros(1, np.uint32)), C.c_uint32(n),
+        rc = f(_p0(pi), _p0(pj), C.c_uint64(len(pi)), _p0(od), C.c_uint32(n),
                _p(bin_of), _p(cent), C.byref(nb))
         if rc: raise NgsidError(rc, "umi_centroids: an index out of range, a pair (x, x), or an order that is no permutation")
         return bin_of[:n], cent[:int(nb.value)].copy()

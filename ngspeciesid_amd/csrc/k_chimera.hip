@@ -217,16 +217,7 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
     for (uint64_t k = 0; k < NP; ++k) if (pair_parent[k] >= Pr.n) NGSID_FAIL(ctx, NGSID_ERR_ARG, "pair %llu: parent %u out of range (%llu parents)", (unsigned long long)k, pair_parent[k], (unsigned long long)Pr.n);
     if (Q.maxlen > NGSID_MAX_CONSENSUS_LEN || Pr.maxlen > NGSID_MAX_CONSENSUS_LEN)
         NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a sequence of %u bases exceeds NGSID_MAX_CONSENSUS_LEN=%d", std::max(Q.maxlen, Pr.maxlen), NGSID_MAX_CONSENSUS_LEN);
-    // ---- the alphabet
-    {
-        DevBuf<uint32_t> bad; HIPCHK(ctx, bad.alloc(1));
-        HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), ctx->stream));
-        NGSID_TRY(ngsid_alphabet_scan(ctx, Q, bad.p, "k_chimera_check")); NGSID_TRY(ngsid_alphabet_scan(ctx, Pr, bad.p, "k_chimera_check"));
-        uint32_t h_bad = 0;
-        NGSID_TRY(dev_get(ctx, &h_bad, bad.p, 1));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (h_bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a query or a parent holds a base outside upper-case ACGTN");
-    }
+    NGSID_TRY(ngsid_alphabet_check(ctx, Q, &Pr, "k_chimera_check", "a query or a parent holds a base outside upper-case ACGTN"));
     if (N == 0) return NGSID_OK;
     if (!fields) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null output");
     // ---- per pair: its query, its gid, where its block starts (in uint16 values, from the first pair of the call)
@@ -272,7 +263,7 @@ extern "C" int32_t ngsid_chimera_model(ngsid_ctx* ctx, const ngsid_reads_t* quer
             HIPCHK(ctx, hipGetLastError());
         }
         { ProfScope ps_(ctx, "k_chimera_reduce");
-          hipLaunchKernelGGL(k_chimera_reduce, dim3((unsigned)(qb - qa)), dim3(64), 0, ctx->stream, Q.off, (u64)qa, d_poff.p, (u64)ka, d_po.p + ka, (u64)v0, d_gid.p + ka, prof, d_fields.p); }
+          hipLaunchKernelGGL(k_chimera_reduce, dim3(NGSID_GRID(ctx, qb - qa, 64, "k_chimera_reduce")), dim3(64), 0, ctx->stream, Q.off, (u64)qa, d_poff.p, (u64)ka, d_po.p + ka, (u64)v0, d_gid.p + ka, prof, d_fields.p); }
         HIPCHK(ctx, hipGetLastError());
         if (profiles) NGSID_TRY(dev_get(ctx, profiles + v0, ctx->chm_prof.p, nv));
         if (c + 2 < cuts.size()) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // the next chunk rewrites the scratch

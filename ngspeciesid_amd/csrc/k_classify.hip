@@ -264,7 +264,7 @@ extern "C" int32_t ngsid_refdb_build(ngsid_ctx* ctx, const ngsid_reads_t* refs, 
         DevBuf<uint64_t> scode; DevBuf<uint32_t> ref, sref, fp, fc, rp, rcs; DevBuf<unsigned char> tmp;
         HIPCHK(ctx, scode.alloc(M)); HIPCHK(ctx, ref.alloc(M)); HIPCHK(ctx, sref.alloc(M));
         { ProfScope ps_(ctx, "k_classify_pairs");
-          hipLaunchKernelGGL(k_classify_pairs, dim3((unsigned)n), dim3(64), 0, ctx->stream, coff.p, (u64)n, ref.p); }
+          hipLaunchKernelGGL(k_classify_pairs, dim3(NGSID_GRID(ctx, n, 64, "k_classify_pairs")), dim3(64), 0, ctx->stream, coff.p, (u64)n, ref.p); }
         HIPCHK(ctx, hipGetLastError());
         size_t tb = 0;
         HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ccode.p, scode.p, ref.p, sref.p, (int)M, 0, 3 * prm->k, ctx->stream));
@@ -343,7 +343,7 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
     D2.h_off[2 * N] = 2 * T;
     HIPCHK(ctx, D2.own_seq.alloc(2 * T + 16)); NGSID_TRY(dev_put(ctx, D2.own_off, D2.h_off.data(), 2 * N + 1));
     { ProfScope ps_(ctx, "k_classify_revcomp");
-      hipLaunchKernelGGL(k_classify_revcomp, dim3((unsigned)N), dim3(256), 0, ctx->stream, RD.seq, RD.off, (u64)N, D2.own_off.p, D2.own_seq.p); }
+      hipLaunchKernelGGL(k_classify_revcomp, dim3(NGSID_GRID(ctx, N, 256, "k_classify_revcomp")), dim3(256), 0, ctx->stream, RD.seq, RD.off, (u64)N, D2.own_off.p, D2.own_seq.p); }
     HIPCHK(ctx, hipGetLastError());
     D2.seq = D2.own_seq.p; D2.off = D2.own_off.p; D2.qual = nullptr;
     // ---- their sketches: sorted distinct codes per (query, strand)
@@ -365,7 +365,7 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // (tmp goes out of scope)
     }
     { ProfScope ps_(ctx, "k_classify_uniq");
-      hipLaunchKernelGGL(k_classify_uniq, dim3((unsigned)S), dim3(64), 0, ctx->stream, scode.p, coff.p, (u64)S, ucode.p, ucnt.p); }
+      hipLaunchKernelGGL(k_classify_uniq, dim3(NGSID_GRID(ctx, S, 64, "k_classify_uniq")), dim3(64), 0, ctx->stream, scode.p, coff.p, (u64)S, ucode.p, ucnt.p); }
     HIPCHK(ctx, hipGetLastError());
     // ---- chunks of queries: two count rows each, under a share of the free device memory
     const uint32_t n_refs = (uint32_t)db->n_refs;
@@ -381,11 +381,11 @@ extern "C" int32_t ngsid_classify_search(ngsid_ctx* ctx, const ngsid_refdb* db, 
         const uint64_t nq = std::min(N, c0 + chunk) - c0;
         HIPCHK(ctx, hipMemsetAsync(ctx->cls_cnt.p, 0, nq * row_bytes, ctx->stream));
         { ProfScope ps_(ctx, "k_classify_count");
-          hipLaunchKernelGGL(k_classify_count, dim3((unsigned)(2 * nq)), dim3(CLS_THREADS), 0, ctx->stream, ucode.p, coff.p, ucnt.p, (u64)(2 * c0),
+          hipLaunchKernelGGL(k_classify_count, dim3(NGSID_GRID(ctx, 2 * nq, CLS_THREADS, "k_classify_count")), dim3(CLS_THREADS), 0, ctx->stream, ucode.p, coff.p, ucnt.p, (u64)(2 * c0),
                              db->codes.p, (uint32_t)db->n_codes, db->post_off.p, db->post.p, n_refs, ctx->cls_cnt.p); }
         HIPCHK(ctx, hipGetLastError());
         { ProfScope ps_(ctx, "k_classify_topk");
-          hipLaunchKernelGGL(k_classify_topk, dim3((unsigned)nq), dim3(CLS_THREADS), 0, ctx->stream, ctx->cls_cnt.p, n_refs, (u64)c0, ucnt.p, top_k, prm->min_shared, d_ref.p, d_sh.p, d_st.p); }
+          hipLaunchKernelGGL(k_classify_topk, dim3(NGSID_GRID(ctx, nq, CLS_THREADS, "k_classify_topk")), dim3(CLS_THREADS), 0, ctx->stream, ctx->cls_cnt.p, n_refs, (u64)c0, ucnt.p, top_k, prm->min_shared, d_ref.p, d_sh.p, d_st.p); }
         HIPCHK(ctx, hipGetLastError());
     }
     NGSID_TRY(dev_get(ctx, cand_ref, d_ref.p, N * top_k)); NGSID_TRY(dev_get(ctx, cand_shared, d_sh.p, N * top_k)); NGSID_TRY(dev_get(ctx, cand_strand, d_st.p, N * top_k));

@@ -16,7 +16,7 @@
 // block only the items whose decision a committed representative can change (rep_can_matter) are decided again.
 // A block that keeps restarting is cut short: the items behind the cut are decided from scratch by the next block.
 // Aligner results are cached per (read, representative) since they do not depend on the database.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_tables.h"
 #include "../../include/ngsid_batch.h"
 #include <math.h>
@@ -715,7 +715,7 @@ struct ClusterRun {
             NGSID_FAIL(ctx, NGSID_ERR_ARG, "%llu segments, but a minimizer code of k = %d leaves %d bits for the segment number", (unsigned long long)n_seg, k, free_bits < 0 ? 0 : free_bits);
         HIPCHK(ctx, d_segof.alloc(N)); HIPCHK(ctx, d_segoff.alloc(n_seg + 1));
         HIPCHK(ctx, hipMemcpyAsync(d_segoff.p, seg_off, 8 * (n_seg + 1), hipMemcpyHostToDevice, ctx->stream));      // (the caller's array: valid for the whole call, so nothing waits for this copy)
-        hipLaunchKernelGGL(k_tag_codes, dim3((unsigned)N), dim3(64), 0, ctx->stream, ctx->pol_mzcode.p, ctx->mz_off.p, d_segoff.p, (uint32_t)n_seg, d_segof.p, N, used);
+        hipLaunchKernelGGL(k_tag_codes, dim3(NGSID_GRID(ctx, N, 64, "k_tag_codes")), dim3(64), 0, ctx->stream, ctx->pol_mzcode.p, ctx->mz_off.p, d_segoff.p, (uint32_t)n_seg, d_segof.p, N, used);
         HIPCHK(ctx, hipGetLastError());
         return NGSID_OK;
     }

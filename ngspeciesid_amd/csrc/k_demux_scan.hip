@@ -22,8 +22,8 @@ __device__ __forceinline__ void dsc_wave_sync() { asm volatile("s_waitcnt lgkmcn
 
 __device__ __forceinline__ void dsc_emit(DscRec* __restrict__ found, u64 limit, unsigned long long* __restrict__ ctr, uint32_t read, int pattern, int end, int ed)
 {
-    const u64 at = atomicAdd(ctr, 1ull);
-    if (at < limit) { DscRec r; r.read = read; r.pattern = pattern; r.end = end; r.ed = ed; found[at] = r; }
+    unsigned long long at;
+    if (ngsid_found_slot(ctr, limit, &at)) { DscRec r; r.read = read; r.pattern = pattern; r.end = end; r.ed = ed; found[at] = r; }
 }
 
 __global__ __launch_bounds__(DMX_THREADS)
@@ -109,14 +109,9 @@ extern "C" int32_t ngsid_demux_scan(ngsid_ctx* ctx, const ngsid_reads_t* reads, 
     const uint64_t N = RD.n;
     if (RD.maxlen > NGSID_MAX_READ_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a read is longer than %d", NGSID_MAX_READ_LEN);
     if (N == 0) { if (hit_off) hit_off[0] = 0; return NGSID_OK; }
-    DevBuf<uint32_t> d_flag; DevBuf<unsigned long long> d_ctr; DevBuf<DscRec> d_found;
-    HIPCHK(ctx, d_flag.alloc(1)); HIPCHK(ctx, d_ctr.alloc(1));
-    HIPCHK(ctx, hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), ctx->stream));
-    NGSID_TRY(ngsid_alphabet_scan(ctx, RD, d_flag.p));
-    uint32_t bad = 0;
-    NGSID_TRY(dev_get(ctx, &bad, d_flag.p, 1));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a read base outside upper-case ACGTN");
+    NGSID_TRY(ngsid_alphabet_check(ctx, RD, nullptr, nullptr, "a read base outside upper-case ACGTN"));
+    DevBuf<unsigned long long> d_ctr; DevBuf<DscRec> d_found;
+    HIPCHK(ctx, d_ctr.alloc(1));
     // ---- lane mapping
     const int G = 64 >> P.logTp;
     const size_t lds = DMX_PEQ_BYTES + (size_t)DMX_WAVES * G * DSC_CHUNK;

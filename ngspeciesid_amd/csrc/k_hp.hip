@@ -114,7 +114,7 @@ extern "C" int32_t ngsid_hp_runs(ngsid_ctx* ctx, const ngsid_reads_t* centres, c
         HIPCHK(ctx, d_items.reserve(items.size()));
         HIPCHK(ctx, hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, ctx->stream));
         { ProfScope ps_(ctx, "k_hp_runs");
-          hipLaunchKernelGGL(k_hp_runs, dim3((unsigned)(items.size() / 3), (unsigned)((max_runs + HP_TILE - 1) / HP_TILE)), dim3(HP_TILE), 0, ctx->stream,
+          hipLaunchKernelGGL(k_hp_runs, dim3(NGSID_GRID(ctx, items.size() / 3, HP_TILE, "k_hp_runs"), (unsigned)((max_runs + HP_TILE - 1) / HP_TILE)), dim3(HP_TILE), 0, ctx->stream,
                              C.rec, P.stride, C.pos, C.span, P.d_pair_read + C.c0, d_pair_strand.p + C.c0, P.d_oseq, P.d_read_off, d_items.p,
                              d_run_off.p, d_run_start.p, d_run_end.p, P.d_cen_seq, P.d_cen_off, d_hist.p); }
         HIPCHK(ctx, hipGetLastError());

@@ -13,7 +13,7 @@
 // k <= 21 fits one 64-bit code.  22 <= k <= 32 = NGSID_MAX_K (KW = 2) keeps (hi, lo) pairs - lo = the last 21 letters - and a rename pass afterwards
 // replaces them by their dense rank over the whole launch (order preserving, equal k-mers equal code), so everything downstream still
 // sees 64-bit order-preserving codes.  HBM traffic per read: 2L in, 12 B per minimizer out.
-#include "ngsid_internal.h"
+#include "ngsid_host.h"
 #include "../../include/ngsid_tables.h"
 #include <hipcub/hipcub.hpp>
 
@@ -429,7 +429,7 @@ int32_t ngsid_minimizers_csr(ngsid_ctx* ctx, const DevReads& R, int k, int w, co
             cap_have = want;
         }
         HIPCHK(ctx, hipMemcpyAsync(o_off.p + done, ho + done, 8 * (nr + 1), hipMemcpyHostToDevice, ctx->stream));      // (pinned: h_mzoff stays valid and unchanged below r1)
-        hipLaunchKernelGGL(k_mz_gather, dim3((unsigned)nr), dim3(64), 0, ctx->stream, R.off + done, d_cnt + done, o_off.p + done, nr, b0,
+        hipLaunchKernelGGL(k_mz_gather, dim3(NGSID_GRID(ctx, nr, 64, "k_mz_gather")), dim3(64), 0, ctx->stream, R.off + done, d_cnt + done, o_off.p + done, nr, b0,
                            ctx->mz_scode.p, wide ? s_hi.p : nullptr, ctx->mz_spos.p, o_code.p, wide ? c_hi.p : nullptr, o_pos.p);
         HIPCHK(ctx, hipGetLastError());
         done = r1;

@@ -241,11 +241,8 @@ void k_near_tiles(const uint64_t* __restrict__ off, const uint64_t* __restrict__
     int st = 0;
     const int best = near_both<W>(ppl + pwoff[oy] * 3, tpl + twoff[ox] * 6, near_nwt(n), m, n, K, both != 0, &st);
     if (best < 0) return;
-    const unsigned long long slot = atomicAdd(counter, 1ull);
-    if (slot < limit) {
-        key[slot] = ((u64)min(ox, oy) << 32) | max(ox, oy);
-        ds[slot] = (uint16_t)(best | (st << 15));
-    }
+    unsigned long long slot;
+    if (ngsid_found_slot(counter, limit, &slot)) { key[slot] = ngsid_pair_key(ox, oy); ds[slot] = (uint16_t)(best | (st << 15)); }
 }
 
 // the planes of one kind (NEAR_PATTERN or NEAR_TEXT) of every sequence of R in `buf` (grow-only), the word offsets on the device
@@ -257,8 +254,8 @@ int32_t near_pack(ngsid_ctx* ctx, const DevReads& R, int kind, DevBuf<uint32_t>&
     HIPCHK(ctx, buf.reserve(woff[R.n] * (kind == NEAR_PATTERN ? 3 : 6)));
     NGSID_TRY(dev_put(ctx, d_woff, woff.data(), R.n + 1));
     ProfScope ps_(ctx, "k_near_pack");
-    for (uint64_t s0 = 0; s0 < R.n; s0 += 1u << 30) {
-        hipLaunchKernelGGL(k_near_pack, dim3((unsigned)std::min<uint64_t>(R.n - s0, 1u << 30)), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, kind, buf.p);
+    for (uint64_t s0 = 0; s0 < R.n; s0 += ngsid_max_blocks(64)) {
+        hipLaunchKernelGGL(k_near_pack, dim3((unsigned)std::min<uint64_t>(R.n - s0, ngsid_max_blocks(64))), dim3(64), 0, ctx->stream, R.seq, R.off, d_woff.p, (u64)s0, kind, buf.p);
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));                  // (woff is a host vector of this scope)
@@ -272,14 +269,7 @@ int32_t near_check(ngsid_ctx* ctx, int32_t max_dist, int32_t limit, const DevRea
     const uint32_t maxlen = std::max(A->maxlen, B ? B->maxlen : 0u);
     if (maxlen > NGSID_MAX_CONSENSUS_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a sequence of %u bases exceeds NGSID_MAX_CONSENSUS_LEN=%d", maxlen, NGSID_MAX_CONSENSUS_LEN);
     if (A->n >= 0x100000000ull || (B && B->n >= 0x100000000ull)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "a set is limited to 2^32 - 1 sequences");
-    DevBuf<uint32_t> bad; HIPCHK(ctx, bad.alloc(1));
-    HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), ctx->stream));
-    NGSID_TRY(ngsid_alphabet_scan(ctx, *A, bad.p, "k_near_check")); if (B) NGSID_TRY(ngsid_alphabet_scan(ctx, *B, bad.p, "k_near_check"));
-    uint32_t h_bad = 0;
-    NGSID_TRY(dev_get(ctx, &h_bad, bad.p, 1));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a sequence holds a base outside upper-case ACGTN");
-    return NGSID_OK;
+    return ngsid_alphabet_check(ctx, *A, B, "k_near_check", "a sequence holds a base outside upper-case ACGTN");
 }
 
 // the band words of a call: the smallest instance that holds max_dist
@@ -312,7 +302,7 @@ int32_t near_within_run(ngsid_ctx* ctx, const ngsid_reads_t* queries, const ngsi
     const uint64_t chunk = opt > 0 ? (uint64_t)opt : (uint64_t)1 << 30;
     for (uint64_t p0 = 0; p0 < n_pairs; p0 += chunk) {
         const uint64_t p1 = std::min(n_pairs, p0 + chunk);
-        NEAR_LAUNCH(k_near_within, W, dim3((unsigned)((p1 - p0 + 255) / 256)), B.Q.off, d_qw.p, ctx->near_pat.p, B.T.off, d_tw.p, ctx->near_txt.p,
+        NEAR_LAUNCH(k_near_within, W, dim3(NGSID_GRID(ctx, (p1 - p0 + 255) / 256, 256, "k_near_within")), B.Q.off, d_qw.p, ctx->near_pat.p, B.T.off, d_tw.p, ctx->near_txt.p,
                     B.dq.p, B.dt.p, (u64)p0, (u64)p1, (int)max_dist, (int)(flags & NGSID_NEAR_BOTH_STRANDS), d_dist.p, d_strand.p);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -354,15 +344,16 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
     // ---- the found buffer: cap entries, or what a share of the free device memory holds; rows in chunks
     const uint64_t F = std::min<uint64_t>(cap, ngsid_mem_share(4, (size_t)64 << 20, (size_t)16 << 30, (size_t)4 << 30, ctx->near_key.abytes + ctx->near_ds.abytes) / (8 + sizeof(uint16_t)));
     if (F) { HIPCHK(ctx, ctx->near_key.reserve(F)); HIPCHK(ctx, ctx->near_ds.reserve(F)); }
-    const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0);
-    const uint64_t max_tiles = (uint64_t)1 << 30;                     // per launch: four tiles per workgroup
+    const long long opt = ngsid_opt(ctx, "near_chunk_seqs", 0), opt_tiles = ngsid_opt(ctx, "near_max_tiles", 0);
+    const uint64_t launch_tiles = 4 * ngsid_max_blocks(256);          // what a launch holds: four tiles per workgroup
+    const uint64_t max_tiles = opt_tiles > 0 ? std::min<uint64_t>((uint64_t)opt_tiles, launch_tiles) : launch_tiles;      // above: the rows are split
     std::vector<uint64_t> keys; std::vector<uint16_t> dss;
     PinVec<uint64_t> h_toff;
     const auto launch = [&](uint64_t xa, uint64_t& xb, uint64_t limit, bool& launched) -> int32_t {
         while (xb - xa > 1 && tiles[xb] - tiles[xa] > max_tiles) xb = xa + (xb - xa) / 2;
         const uint64_t nt = tiles[xb] - tiles[xa];
         if (nt == 0) { launched = false; return NGSID_OK; }
-        if (nt > 4 * max_tiles) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
+        if (nt > launch_tiles) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
         h_toff.resize(xb - xa + 1);
         for (uint64_t r = 0; r <= xb - xa; ++r) h_toff[r] = tiles[xa + r] - tiles[xa];
         NGSID_TRY(dev_put(ctx, d_toff, h_toff.data(), xb - xa + 1));
@@ -386,8 +377,8 @@ int32_t near_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, int32_t max_di
     std::iota(perm.begin(), perm.end(), (uint64_t)0);
     std::sort(perm.begin(), perm.end(), [&](uint64_t a, uint64_t b) { return keys[a] < keys[b]; });
     for (uint64_t k = 0; k < total; ++k) {
-        const uint64_t key = keys[perm[k]]; const uint16_t v = dss[perm[k]];
-        pair_i[k] = (uint32_t)(key >> 32); pair_j[k] = (uint32_t)key; dist[k] = (uint8_t)(v & 0x7fffu); strand[k] = (uint8_t)(v >> 15);
+        const uint16_t v = dss[perm[k]];
+        ngsid_pair_unkey(keys[perm[k]], pair_i + k, pair_j + k); dist[k] = (uint8_t)(v & 0x7fffu); strand[k] = (uint8_t)(v >> 15);
     }
     *n_found = total;
     return NGSID_OK;

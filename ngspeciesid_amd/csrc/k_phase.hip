@@ -171,7 +171,7 @@ extern "C" int32_t ngsid_phase_genotypes(ngsid_ctx* ctx, const ngsid_reads_t* ce
         if (!started) return NGSID_OK;
         const u64 np = C.c1 - C.c0, blocks = ((np << lp_shift) + PHASE_THREADS - 1) / PHASE_THREADS;
         { ProfScope ps_(ctx, "k_phase_gather");
-          hipLaunchKernelGGL(k_phase_gather, dim3((unsigned)blocks), dim3(PHASE_THREADS), 0, ctx->stream, C.rec, P.stride, C.span, P.d_pair_group + C.c0, d_pair_x.p + C.c0, np, lp_shift,
+          hipLaunchKernelGGL(k_phase_gather, dim3(NGSID_GRID(ctx, blocks, PHASE_THREADS, "k_phase_gather")), dim3(PHASE_THREADS), 0, ctx->stream, C.rec, P.stride, C.span, P.d_pair_group + C.c0, d_pair_x.p + C.c0, np, lp_shift,
                              d_site_off.p, d_site_pos.p, d_geno_off.p, P.d_cen_seq, P.d_cen_off, d_geno.p); }
         HIPCHK(ctx, hipGetLastError());
         return NGSID_OK;
@@ -208,7 +208,7 @@ extern "C" int32_t ngsid_phase_pair_tables(ngsid_ctx* ctx, const uint8_t* geno, 
     HIPCHK(ctx, d_tables.alloc(tab_off[G]));
     HIPCHK(ctx, hipMemsetAsync(d_tables.p, 0, sizeof(uint32_t) * tab_off[G], ctx->stream));
     { ProfScope ps_(ctx, "k_phase_pairs");
-      hipLaunchKernelGGL(k_phase_pairs, dim3((unsigned)(items.size() / 4)), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_site_off.p, d_tab_off.p, d_items.p, d_tables.p); }
+      hipLaunchKernelGGL(k_phase_pairs, dim3(NGSID_GRID(ctx, items.size() / 4, PHASE_THREADS, "k_phase_pairs")), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_site_off.p, d_tab_off.p, d_items.p, d_tables.p); }
     HIPCHK(ctx, hipGetLastError());
     NGSID_TRY(dev_get(ctx, tables, d_tables.p, tab_off[G]));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -247,7 +247,7 @@ extern "C" int32_t ngsid_phase_assign(ngsid_ctx* ctx, const uint8_t* geno, const
     HIPCHK(ctx, d_best.alloc(NL)); HIPCHK(ctx, d_dist.alloc(NL)); HIPCHK(ctx, d_dist2.alloc(NL));
     HIPCHK(ctx, hipMemsetAsync(d_best.p, 0xff, NL, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(d_dist.p, 0xff, NL, ctx->stream)); HIPCHK(ctx, hipMemsetAsync(d_dist2.p, 0xff, NL, ctx->stream));
     { ProfScope ps_(ctx, "k_phase_assign");
-      hipLaunchKernelGGL(k_phase_assign, dim3((unsigned)(items.size() / 2)), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_grp_off.p, d_site_off.p, d_hap_off.p, d_hal_off.p, d_hal.p,
+      hipLaunchKernelGGL(k_phase_assign, dim3(NGSID_GRID(ctx, items.size() / 2, PHASE_THREADS, "k_phase_assign")), dim3(PHASE_THREADS), 0, ctx->stream, d_geno.p, d_geno_off.p, d_grp_off.p, d_site_off.p, d_hap_off.p, d_hal_off.p, d_hal.p,
                          d_items.p, d_best.p, d_dist.p, d_dist2.p); }
     HIPCHK(ctx, hipGetLastError());
     NGSID_TRY(dev_get(ctx, best, d_best.p, NL)); NGSID_TRY(dev_get(ctx, dist, d_dist.p, NL)); NGSID_TRY(dev_get(ctx, dist2, d_dist2.p, NL));

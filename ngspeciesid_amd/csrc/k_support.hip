@@ -127,7 +127,7 @@ extern "C" int32_t ngsid_consensus_support(ngsid_ctx* ctx, const ngsid_reads_t* 
         HIPCHK(ctx, d_items.reserve(items.size()));
         HIPCHK(ctx, hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, ctx->stream));
         { ProfScope ps_(ctx, "k_support_sum");
-          hipLaunchKernelGGL(k_support_sum, dim3((unsigned)(items.size() / 3), (P.maxb + SUPPORT_TILE - 1) / SUPPORT_TILE), dim3(SUPPORT_TILE), 0, ctx->stream,
+          hipLaunchKernelGGL(k_support_sum, dim3(NGSID_GRID(ctx, items.size() / 3, SUPPORT_TILE, "k_support_sum"), (P.maxb + SUPPORT_TILE - 1) / SUPPORT_TILE), dim3(SUPPORT_TILE), 0, ctx->stream,
                              C.rec, P.stride, C.span, d_items.p, P.d_cen_off, d_counts.p, d_used.p); }
         HIPCHK(ctx, hipGetLastError());
         return NGSID_OK;

@@ -143,8 +143,8 @@ __device__ __forceinline__ int umi_column_ed(u64 B0, u64 B1, u64 B2, int m, u64 
 
 __device__ __forceinline__ void umi_emit(uint32_t x, uint32_t y, int dist, u64* __restrict__ fkey, uint8_t* __restrict__ fdist, u64 limit, unsigned long long* ctr)
 {
-    const unsigned long long slot = atomicAdd(ctr, 1ull);
-    if (slot < limit) { fkey[slot] = ((u64)min(x, y) << 32) | max(x, y); fdist[slot] = (uint8_t)dist; }
+    unsigned long long slot;
+    if (ngsid_found_slot(ctr, limit, &slot)) { fkey[slot] = ngsid_pair_key(x, y); fdist[slot] = (uint8_t)dist; }
 }
 
 // the tile list of the chunk: entry idx owns the tiles tsum[idx] - tiles(idx) .. tsum[idx] - 1 (tsum = inclusive sums of the tiles) and writes its number into each
@@ -240,15 +240,7 @@ int32_t umi_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, const ngsid_umi
     const uint64_t N = R.n;
     if (R.maxlen > NGSID_UMI_MAX_LEN) NGSID_FAIL(ctx, NGSID_ERR_TOO_LONG, "a sequence of %u letters exceeds NGSID_UMI_MAX_LEN=%d", R.maxlen, NGSID_UMI_MAX_LEN);
     if (N * (uint64_t)(d + 1) >= 0x7fffffffull) NGSID_FAIL(ctx, NGSID_ERR_ARG, "%llu sequences x %d seeds: the index is limited to 2^31 - 1 entries", (unsigned long long)N, d + 1);
-    {
-        DevBuf<uint32_t> bad; HIPCHK(ctx, bad.alloc(1));
-        HIPCHK(ctx, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), ctx->stream));
-        NGSID_TRY(ngsid_alphabet_scan(ctx, R, bad.p, "k_umi_check"));
-        uint32_t h_bad = 0;
-        NGSID_TRY(dev_get(ctx, &h_bad, bad.p, 1));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (h_bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "a sequence holds a letter outside upper-case ACGTN");
-    }
+    NGSID_TRY(ngsid_alphabet_check(ctx, R, nullptr, "k_umi_check", "a sequence holds a letter outside upper-case ACGTN"));
     if (N < 2) return NGSID_OK;
     // ---- host side of the split: which sequences are seedable, the set ordered by length
     auto len = [&](uint64_t s) { return (uint32_t)(R.h_off[s + 1] - R.h_off[s]); };
@@ -282,8 +274,11 @@ int32_t umi_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, const ngsid_umi
     DevBuf<unsigned long long> d_ctr; HIPCHK(ctx, d_ctr.alloc(nctr));
     HIPCHK(ctx, hipMemsetAsync(d_ctr.p, 0, nctr * sizeof(unsigned long long), ctx->stream));
     const int count = ctx->prof ? 1 : 0;
-    const long long opt = ngsid_opt(ctx, "umi_chunk_seqs", 0);
+    const long long opt = ngsid_opt(ctx, "umi_chunk_seqs", 0), opt_tiles = ngsid_opt(ctx, "umi_max_tiles", 0);
     const int Q = (d + 1) * (2 * d + 1);
+    // the tiles of a join chunk: what the tile list is allowed to hold (1 GiB) and what a launch holds, four tiles per workgroup; above max_tiles the queries are split
+    const uint64_t launch_tiles = std::min<uint64_t>((uint64_t)1 << 28, 4 * ngsid_max_blocks(256));
+    const uint64_t max_tiles = opt_tiles > 0 ? std::min<uint64_t>((uint64_t)opt_tiles, launch_tiles) : launch_tiles;
     // ---- join: queries 1 .. N - 1 in chunks (query 0 has no smaller index)
     if (any_seedable) {
         uint64_t rows = opt > 0 ? (uint64_t)opt : std::max<uint64_t>(1, ((uint64_t)8 << 20) / Q);
@@ -302,10 +297,8 @@ int32_t umi_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, const ngsid_umi
               HIPCHK(ctx, hipcub::DeviceScan::InclusiveSum(ctx->umi_tmp.p, tb, ctx->umi_tile.p, ctx->umi_tsum.p, (int)nidx, ctx->stream)); }
             NGSID_TRY(dev_get(ctx, &nt, ctx->umi_tsum.p + (nidx - 1), 1));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            if (nt > ((uint64_t)1 << 28)) {                             // more tiles than the tile list is allowed to hold (1 GiB): the same queries in smaller chunks
-                if (b1 - b0 == 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
-                rows = (b1 - b0) / 2; continue;
-            }
+            if (nt > launch_tiles && b1 - b0 == 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one sequence has %llu candidate tiles: beyond a launch", (unsigned long long)nt);
+            if (nt > max_tiles && b1 - b0 > 1) { rows = (b1 - b0) / 2; continue; }      // the same queries in smaller chunks
             if (nt) {
                 HIPCHK(ctx, ctx->umi_tidx.reserve(nt));
                 ProfScope ps_(ctx, "k_umi_join");
@@ -324,7 +317,7 @@ int32_t umi_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, const ngsid_umi
         uint32_t widest = 0;                                            // the largest range of a row
         for (int L = 0; L <= NGSID_UMI_MAX_LEN; ++L) widest = std::max(widest, lstart[std::min(L + d, NGSID_UMI_MAX_LEN) + 1] - lstart[std::max(L - d, 0)]);
         const unsigned ny = (unsigned)std::min<uint64_t>(std::max<uint64_t>(((uint64_t)widest + 255) / 256, 1), 64);
-        const uint64_t rows = opt > 0 ? (uint64_t)opt : (uint64_t)1 << 24;
+        const uint64_t rows = std::min<uint64_t>(opt > 0 ? (uint64_t)opt : (uint64_t)1 << 24, ngsid_max_blocks(256));
         for (uint64_t r0 = 0; r0 < ns.size(); r0 += rows) {
             ProfScope ps_(ctx, "k_umi_short");
             hipLaunchKernelGGL(k_umi_short, dim3((unsigned)std::min<uint64_t>(rows, ns.size() - r0), ny), dim3(256), 0, ctx->stream, pack, d_ns.p, d_order.p, d_lstart.p, (u64)r0, d,
@@ -348,7 +341,7 @@ int32_t umi_pairs_run(ngsid_ctx* ctx, const ngsid_reads_t* seqs, const ngsid_umi
     PinVec<uint64_t> keys(total);
     NGSID_TRY(dev_get(ctx, keys.data(), ctx->umi_sfound.p, total)); NGSID_TRY(dev_get(ctx, dist, ctx->umi_sdist.p, total));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint64_t k = 0; k < total; ++k) { pair_i[k] = (uint32_t)(keys[k] >> 32); pair_j[k] = (uint32_t)keys[k]; }
+    for (uint64_t k = 0; k < total; ++k) ngsid_pair_unkey(keys[k], pair_i + k, pair_j + k);
     *n_found = total;
     return NGSID_OK;
 }

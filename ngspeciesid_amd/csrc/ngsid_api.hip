@@ -451,8 +451,8 @@ extern "C" int32_t ngsid_score_reads(ngsid_ctx* ctx, const ngsid_reads_t* reads,
     DevBuf<double> ds, de; DevBuf<uint8_t> dk;
     HIPCHK(ctx, ds.alloc(n)); HIPCHK(ctx, de.alloc(n)); HIPCHK(ctx, dk.alloc(n));
     { ProfScope ps_(ctx, "k_score_reads");
-      if (R.maxlen <= 65535u) hipLaunchKernelGGL(k_score_reads<unsigned short>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, R.seq, R.qual, R.off, n, k, q_threshold, ds.p, de.p, dk.p);
-      else hipLaunchKernelGGL(k_score_reads<unsigned int>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, R.seq, R.qual, R.off, n, k, q_threshold, ds.p, de.p, dk.p); }
+      if (R.maxlen <= 65535u) hipLaunchKernelGGL(k_score_reads<unsigned short>, dim3(NGSID_GRID(ctx, (n + 63) / 64, 64, "k_score_reads")), dim3(64), 0, ctx->stream, R.seq, R.qual, R.off, n, k, q_threshold, ds.p, de.p, dk.p);
+      else hipLaunchKernelGGL(k_score_reads<unsigned int>, dim3(NGSID_GRID(ctx, (n + 63) / 64, 64, "k_score_reads")), dim3(64), 0, ctx->stream, R.seq, R.qual, R.off, n, k, q_threshold, ds.p, de.p, dk.p); }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(score, ds.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(err_rate, de.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -538,7 +538,7 @@ extern "C" int32_t ngsid_reads_subset(ngsid_ctx* ctx, const ngsid_reads_t* dev_i
     HIPCHK(ctx, hipMemsetAsync(d_bad.p, 0, sizeof(unsigned long long), ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(dof, h_noff.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
     if (n) HIPCHK(ctx, hipMemcpyAsync(d_idx.p, idx, sizeof(uint64_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (n) hipLaunchKernelGGL(k_reads_subset, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, R.seq, R.qual, R.off, d_idx.p, (const uint64_t*)dof, n, (uint8_t*)ds, (uint8_t*)dq, d_bad.p);
+    if (n) hipLaunchKernelGGL(k_reads_subset, dim3(NGSID_GRID(ctx, (n + 3) / 4, 256, "k_reads_subset")), dim3(256), 0, ctx->stream, R.seq, R.qual, R.off, d_idx.p, (const uint64_t*)dof, n, (uint8_t*)ds, (uint8_t*)dq, d_bad.p);
     HIPCHK(ctx, hipGetLastError());
     unsigned long long hb = 0;
     HIPCHK(ctx, hipMemcpyAsync(&hb, d_bad.p, sizeof hb, hipMemcpyDeviceToHost, ctx->stream));
@@ -565,7 +565,7 @@ extern "C" int32_t ngsid_reads_release(ngsid_ctx* ctx, ngsid_reads_t* dev)
 extern "C" int32_t ngsid_ctx_option(ngsid_ctx* ctx, const char* name, int64_t value)
 {
     if (!ctx || !name) return NGSID_ERR_ARG;
-    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs", "umi_chunk_seqs"};
+    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs", "umi_chunk_seqs", "near_max_tiles", "umi_max_tiles"};
     for (const char* k : known) if (!strcmp(k, name)) { ctx->options[name] = (long long)value; return NGSID_OK; }
     if (!strcmp(name, "touch")) {        // one trivial operation on the context's stream (+ wait): a caller that spends milliseconds on the host between two calls keeps the device out of its idle state
         if (ctx->mzc_fp.n < 2) HIPCHK(ctx, ctx->mzc_fp.alloc(2));

@@ -1,5 +1,5 @@
-// ngsid_host.h - host-side plumbing the entry points share: transfers, the memory budget, list checks, the grouped-reads front end, pair batches, sketch scratch, the alphabet scan,
-// the IUPAC equality and the letter code (k_demux_common.h, k_near.hip), the found-buffer loop (k_demux_scan.hip, k_near.hip)
+// ngsid_host.h - host-side plumbing the entry points share: transfers, the launch bound, the memory budget, list checks, the grouped-reads front end, pair batches, sketch scratch,
+// the alphabet check, the IUPAC equality and the letter code (k_demux_common.h, k_near.hip), the found-list emit, pair key and loop (k_demux_scan.hip, k_near.hip, k_umi.hip)
 #pragma once
 #include "ngsid_internal.h"
 #include <algorithm>
@@ -18,6 +18,19 @@ template <typename T> static inline int32_t dev_get(ngsid_ctx* ctx, T* h, const 
     if (n) HIPCHK(ctx, hipMemcpyAsync(h, d, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream));
     return NGSID_OK;
 }
+
+// ---- the launch bound: HIP takes no grid with gridDim.x * blockDim.x >= 2^32 (hipModuleLaunchKernel, hip_runtime_api.h) - a larger one is not refused but runs in part.
+// A launch whose workgroup count grows with the input either chunks by ngsid_max_blocks or passes the count through NGSID_GRID; grids clamped to a multiple of n_cu need neither.
+#define NGSID_MAX_GRID_ITEMS 0x100000000ull
+static inline uint64_t ngsid_max_blocks(unsigned threads) { return (NGSID_MAX_GRID_ITEMS - 1) / threads; }
+static inline int32_t ngsid_grid(ngsid_ctx* ctx, uint64_t blocks, unsigned threads, const char* kernel, unsigned* grid)
+{
+    if (blocks > ngsid_max_blocks(threads)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "%s: %llu workgroups of %u exceed the 2^32 - 1 work-items of a launch", kernel, (unsigned long long)blocks, threads);
+    *grid = (unsigned)blocks;
+    return NGSID_OK;
+}
+// the checked workgroup count as an expression (for a dim3): returns NGSID_ERR_ARG from the calling function where ngsid_grid refuses, never truncates
+#define NGSID_GRID(ctx, blocks, threads, kernel) ({ unsigned grid_ = 0; NGSID_TRY(ngsid_grid((ctx), (uint64_t)(blocks), (threads), (kernel), &grid_)); grid_; })
 
 // ---- the byte budget of a chunked call: the 1 / divisor share of the device memory that is free now (+ what the allocator's cache and the caller's own grow-only
 // buffers hold: both are reused), divided among the live contexts of the process, clamped to [floor, ceiling]
@@ -80,16 +93,38 @@ static inline int32_t ngsid_sketch(ngsid_ctx* ctx, const DevReads& R, int k, int
     return ngsid_minimizers_csr(ctx, R, k, w, MzOut{&S.code, &S.pos, &S.off, &S.h_off}, S.cnt.p, S.hlen.p, S.herr.p, S.rawerr.p, S.h_cnt.data(), S.h_hlen.data(), bad);
 }
 
-// ---- k_demux.hip: enqueues the scan of R's bases; *d_flag (cleared by the caller) becomes non-zero when one is outside upper-case ACGTN.  The caller reads the flag.
+// ---- k_demux.hip: enqueues the scan of R's bases; *d_flag (cleared by the caller) becomes non-zero when one is outside upper-case ACGTN.  The caller reads the flag
+// (ngsid_demux_locate does, together with its hits); everyone else calls ngsid_alphabet_check: the flag, the scan of A and of B (or null), the read, the synchronisation,
+// NGSID_ERR_ALPHABET with `message`.  prof_name: the profiling line of the scans, or null
 int32_t ngsid_alphabet_scan(ngsid_ctx* ctx, const DevReads& R, uint32_t* d_flag, const char* prof_name = nullptr);
+static inline int32_t ngsid_alphabet_check(ngsid_ctx* ctx, const DevReads& A, const DevReads* B, const char* prof_name, const char* message)
+{
+    DevBuf<uint32_t> d_flag; HIPCHK(ctx, d_flag.alloc(1));
+    HIPCHK(ctx, hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), ctx->stream));
+    NGSID_TRY(ngsid_alphabet_scan(ctx, A, d_flag.p, prof_name)); if (B) NGSID_TRY(ngsid_alphabet_scan(ctx, *B, d_flag.p, prof_name));
+    uint32_t bad = 0;
+    NGSID_TRY(dev_get(ctx, &bad, d_flag.p, 1));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "%s", message);
+    return NGSID_OK;
+}
 bool ngsid_iupac_eq(uint8_t a, uint8_t b, int iupac);      // host_io.hip: the equality rule of ngsid_host_infix_locate
 // the letter code of the demultiplexer and near-pairs kernels: A C G T -> 0 .. 3, anything else (N) -> 4
 __device__ __forceinline__ uint32_t ngsid_base_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 
-// ---- the found-buffer loop of ngsid_demux_scan and ngsid_near_pairs*: rows [0, N) in chunks of rows_first, every launch appending its records to a found buffer of F
-// records through ONE counter (*d_ctr) that runs on past the launch's `limit`, so a launch always yields its count.  launch(a, b, limit, launched) clears the counter and
-// enqueues rows [a, b) (it may lower b, or clear `launched` when the rows hold nothing to launch); fetch(a, c) enqueues the copy of the c records of the launch that began at row a.
+// ---- found lists (ngsid_demux_scan, ngsid_near_pairs*, ngsid_umi_pairs): a kernel appends its records to a found buffer through ONE counter.  ngsid_found_slot takes
+// the next slot and tells whether it lies inside the buffer; the counter runs on past `limit`, so a launch always yields its count, whatever it could store.
+__device__ __forceinline__ bool ngsid_found_slot(unsigned long long* ctr, uint64_t limit, unsigned long long* slot) { *slot = atomicAdd(ctr, 1ull); return *slot < limit; }
+// the key of a found pair of sequences: (smaller index << 32) | larger index, so that ascending keys are ascending (i, j)
+__device__ __forceinline__ uint64_t ngsid_pair_key(uint32_t x, uint32_t y) { return ((uint64_t)min(x, y) << 32) | max(x, y); }
+static inline void ngsid_pair_unkey(uint64_t key, uint32_t* i, uint32_t* j) { *i = (uint32_t)(key >> 32); *j = (uint32_t)key; }
+
+// the found-buffer loop of ngsid_demux_scan and ngsid_near_pairs*: rows [0, N) in chunks of rows_first, every launch appending its records to a found buffer of F
+// records.  launch(a, b, limit, launched) clears the counter (*d_ctr) and enqueues rows [a, b) (it may lower b, or clear `launched` when the rows hold nothing to launch);
+// fetch(a, c) enqueues the copy of the c records of the launch that began at row a.
 // -> *total: the records of all rows.  Filling stops (and counting goes on) exactly when total exceeds cap.
+// ngsid_umi_pairs is not a user: its two producers (the join and the short path) feed ONE device-resident list that a device sort orders, so nothing is fetched per launch
+// and a launch has no count of its own to act on - its chunk loops only bound the tile list and the launch.
 template <typename Launch, typename Fetch>
 static inline int32_t ngsid_found_loop(ngsid_ctx* ctx, uint64_t N, uint64_t rows_first, uint64_t F, uint64_t cap, unsigned long long* d_ctr, Launch launch, Fetch fetch,
                                        const char* row_noun, const char* record_noun, uint64_t* total_out)

@@ -639,7 +639,7 @@ static int32_t poa_consensus_impl(ngsid_ctx* ctx, const ngsid_reads_t* reads, co
     htc.mark("checks");
     DevBuf<PSeq> d_seqs; HIPCHK(ctx, d_seqs.alloc(RD.n));
     DevBuf<uint32_t> d_weight; if (weight && RD.n) NGSID_TRY(dev_put(ctx, d_weight, weight, RD.n));
-    if (RD.n) hipLaunchKernelGGL(k_make_pseq_reads, dim3((unsigned)((RD.n + 255) / 256)), dim3(256), 0, ctx->stream, RD.seq, RD.qual, RD.off, RD.n, prm->mode, weight ? d_weight.p : (const uint32_t*)nullptr, d_seqs.p);
+    if (RD.n) hipLaunchKernelGGL(k_make_pseq_reads, dim3(NGSID_GRID(ctx, (RD.n + 255) / 256, 256, "k_make_pseq_reads")), dim3(256), 0, ctx->stream, RD.seq, RD.qual, RD.off, RD.n, prm->mode, weight ? d_weight.p : (const uint32_t*)nullptr, d_seqs.p);
     HIPCHK(ctx, hipGetLastError());
     std::vector<Unit> units(n_groups);
     for (uint64_t g = 0; g < n_groups; ++g) {
@@ -858,7 +858,7 @@ int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vecto
             lists.insert(lists.end(), v.begin(), v.end()); loff[i + 1] = lists.size();
         }
         DevBuf<uint64_t> d_lists, d_loff; NGSID_TRY(dev_put(ctx, d_lists, lists.data(), lists.size())); NGSID_TRY(dev_put(ctx, d_loff, loff.data(), loff.size()));
-        { ProfScope ps_(ctx, "k_strand"); hipLaunchKernelGGL(k_strand, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ctx->stream, ctx->mz_off.p, mzcnt.p, hlen.p, mzcode.p, sk, d_rgroup.p, d_lists.p, d_loff.p, G, N, d_orient.p); }
+        { ProfScope ps_(ctx, "k_strand"); hipLaunchKernelGGL(k_strand, dim3(NGSID_GRID(ctx, (N + 3) / 4, 256, "k_strand")), dim3(256), 0, ctx->stream, ctx->mz_off.p, mzcnt.p, hlen.p, mzcode.p, sk, d_rgroup.p, d_lists.p, d_loff.p, G, N, d_orient.p); }
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -866,7 +866,7 @@ int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vecto
     NGSID_TRY(dev_get(ctx, h_orient.data(), d_orient.p, N)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // ---- oriented copies of the reads
     DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual; HIPCHK(ctx, oseq.reserve(RD.total + 16)); if (RD.qual) HIPCHK(ctx, oqual.reserve(RD.total + 16));
-    { ProfScope ps_(ctx, "k_orient"); hipLaunchKernelGGL(k_orient, dim3((unsigned)N), dim3(128), 0, ctx->stream, RD.seq, RD.qual, RD.off, N, d_orient.p, oseq.p, RD.qual ? oqual.p : nullptr); }
+    { ProfScope ps_(ctx, "k_orient"); hipLaunchKernelGGL(k_orient, dim3(NGSID_GRID(ctx, N, 128, "k_orient")), dim3(128), 0, ctx->stream, RD.seq, RD.qual, RD.off, N, d_orient.p, oseq.p, RD.qual ? oqual.p : nullptr); }
     HIPCHK(ctx, hipGetLastError());
     return NGSID_OK;
 }
@@ -993,7 +993,7 @@ static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const
             else rc = ngsid_launch_align(ctx, J, RD.maxlen, maxb, prm->aln_open);
             if (rc) return rc;
             const uint64_t T = NP * (uint64_t)nwinmax;
-            { ProfScope ps_(ctx, "k_layers"); hipLaunchKernelGGL(k_layers, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, ctx->stream, oseq.p, RD.qual ? oqual.p : nullptr, RD.off, d_pair_read.p, d_pair_group.p, NP, nwinmax,
+            { ProfScope ps_(ctx, "k_layers"); hipLaunchKernelGGL(k_layers, dim3(NGSID_GRID(ctx, (T + 3) / 4, 256, "k_layers")), dim3(256), 0, ctx->stream, oseq.p, RD.qual ? oqual.p : nullptr, RD.off, d_pair_read.p, d_pair_group.p, NP, nwinmax,
                                d_bp.p, d_span.p, d_blen.p, W, prm->quality_threshold, prm->error_threshold, (prm->aln_mode & NGSID_ALN_SUBGRAPH) ? 1 : 0, (PSeq*)d_lay_raw.p, d_valid.p, flag.p); }
             HIPCHK(ctx, hipGetLastError());
             h_valid.resize(T);

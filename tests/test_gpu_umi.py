@@ -87,6 +87,21 @@ def test_chunking_and_permutation_do_not_change_the_result(gpu_api):
         assert _triples(gpu_api.umi_pairs(seqs, 3, g)) == want, g
 
 
+@pytest.mark.parametrize("max_tiles", [1, 7, 64])
+def test_the_tile_cap_of_a_join_chunk_does_not_change_the_result(gpu_api, max_tiles):
+    """umi_max_tiles lowers the tiles one join chunk takes: the queries are split as they are beyond the real bound of a launch (tests/test_gpu_launch_bound.py), a
+    query of more tiles than the cap still goes in one launch"""
+    seqs = _families()
+    want = _triples(gpu_api.umi_pairs(seqs, 3, 9))
+    assert len(want) > 2000
+    try:
+        gpu_api.set_option("umi_max_tiles", max_tiles)
+        assert _triples(gpu_api.umi_pairs(seqs, 3, 9)) == want
+    finally:
+        gpu_api.set_option("umi_max_tiles", 0)
+        gpu_api.set_option("release_scratch", 1)
+
+
 def test_cap_protocol(gpu_api):
     seqs = _families()[:200]
     want = _triples(gpu_api.umi_pairs(seqs, 3, 9))

@@ -207,6 +207,19 @@ def test_chunking_and_residence():
         assert _pairs(api.near_pairs(list(seqs), 8)) == list(full), "after release_scratch"
 
 
+@pytest.mark.parametrize("max_tiles", [1, 7, 64])
+def test_the_tile_cap_of_a_launch_does_not_change_the_result(gpu_api, max_tiles):
+    """near_max_tiles lowers the tiles one launch takes: the rows are split as they are beyond the real bound of a launch (tests/test_gpu_launch_bound.py), a row of
+    more tiles than the cap still goes in one launch.  The 130 sequences have up to three tiles a row."""
+    seqs, full = _family_set()
+    try:
+        gpu_api.set_option("near_max_tiles", max_tiles)
+        assert _pairs(gpu_api.near_pairs(list(seqs), 8)) == list(full)
+    finally:
+        gpu_api.set_option("near_max_tiles", 0)
+        gpu_api.set_option("release_scratch", 1)
+
+
 def test_errors_come_back_as_return_codes(gpu_api):
     a, b = "ACGTTGCATGCCGATAGGCTTAACGG", "TTGACCGGTAACGTTAGCATCGGCTA"
     long_ = "ACGT" * (MAX_CONSENSUS_LEN // 4) + "A"
