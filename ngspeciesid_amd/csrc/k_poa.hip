@@ -7,10 +7,11 @@
 //     u16 indices) lives in a per-workgroup HBM scratch that stays L2 resident; it is only touched by lane-parallel
 //     phases (row-info build, node matching, node/edge creation, rank insertion) where 64 independent requests hide
 //     the L2 latency.
-//   * The per-ALIGNMENT working set lives in LDS (~20-26 KB, so 6-8 tiles are resident per CU): one packed 8-byte
-//     "row info" word per topological rank (band start, ranks of the first two predecessors, letter, flags), an
-//     8-row ring of DP rows, the sequence, a 32-row block of direction bytes for the traceback, and the per-position
-//     alignment result.  The serial loops (DP rows, traceback, heaviest bundle) run entirely out of LDS/registers.
+//   * The per-ALIGNMENT working set lives in LDS (poa_lds_bytes: 4 864 / 8 960 / 17 152 bytes at band width 64 / 128 / 256 plus the
+//     sequence; see LLT below for the figures per tile): an 8-row ring of DP rows, a 32-row block of direction bytes and of packed
+//     8-byte "row info" words (band start, distances to the first two predecessors, letter, flags) for the traceback, the sequence, and,
+//     on top of the ring and the blocks once they are free, the per-position alignment result of the merge (MergeLds).  The serial
+//     loops (DP rows, traceback, heaviest bundle) run entirely out of LDS/registers.
 //   * DP row of a node: BW = 64*CPL band columns, CPL per lane.  Chain rows (single predecessor = previous row, ~85 %)
 //     take their inputs from registers + one DPP lane shift; other rows read predecessor rows from the LDS ring
 //     (HBM copy for predecessors more than 8 rows back).  The in-row gap chain is a DPP max-plus prefix scan.
@@ -37,6 +38,7 @@
 
 #define LDSP __attribute__((address_space(3)))
 typedef LDSP uint16_t* l16; typedef LDSP uint8_t* l8; typedef LDSP int32_t* l32; typedef LDSP long long* l64; typedef LDSP unsigned long long* lu64;
+__host__ __device__ constexpr size_t poa_al16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 struct GG {   // the graph in the workgroup's HBM scratch, every array indexed by the node's TOPOLOGICAL RANK (round 4; oracle/ngsid_oracle_poa_rank.c is the
               // CPU restatement): no node ids, no edge objects.  ONE base pointer + 32-bit byte offsets derived from a few strides.
@@ -73,15 +75,30 @@ struct GG {   // the graph in the workgroup's HBM scratch, every array indexed b
     // sub-graph state of the alignment in progress (SM_* bits)
     __device__ __forceinline__ uint16_t& bbr(uint32_t p) const { return *(uint16_t*)(base + 3u * s32 + 3u * s64 + 2u * s16 + 3u * s8 + 2u * se16 + se32 + 2u * sl + 2u * p); }
     __device__ __forceinline__ uint8_t& sm(uint32_t i) const { return *(base + 3u * s32 + 3u * s64 + 3u * s16 + 3u * s8 + 2u * se16 + se32 + 2u * sl + i); }
+    // the strides for graph capacities (Vc nodes, Ec edges) and the longest member Lm, and the end offset of the last array under them = the bytes of one workgroup's
+    // scratch (sub: with bbr / sm, which only the sub-graph instances touch).  Host (poa_graph_bytes) and device (poa_tile_body) both come here.
+    __host__ __device__ void set_strides(int Vc, int Ec, int Lm)
+    {
+        const size_t n = (size_t)Vc + 1;
+        s32 = (uint32_t)poa_al16(4 * n); s64 = (uint32_t)poa_al16(8 * n); s16 = (uint32_t)poa_al16(2 * n); s8 = (uint32_t)poa_al16(n);
+        se16 = (uint32_t)poa_al16(2 * (size_t)Ec); se32 = (uint32_t)poa_al16(4 * (size_t)Ec); sl = (uint32_t)poa_al16(2 * (size_t)Lm);
+    }
+    __host__ __device__ size_t end(bool sub) const
+    {
+        const size_t nodeof_end = 3 * (size_t)s32 + 3 * (size_t)s64 + 2 * (size_t)s16 + 3 * (size_t)s8 + 2 * (size_t)se16 + se32 + 2 * (size_t)sl;      // nodeof() + sl
+        return sub ? nodeof_end + s16 + s8 : nodeof_end;                                                                                             // sm() + s8
+    }
 };
-// LDS working set.  ~10 KB per tile for 750-base reads, so sixteen tiles (four waves per SIMD) are resident per CU.  The hot arrays sit at
+// LDS working set.  poa_lds_bytes for 750-base reads (Lmax 752): 5 712 bytes per tile at band width 64, 9 872 at 128, 18 192 at 256, so the 160 KiB of a
+// CU hold 28 / 16 / 9 tiles; the register budgets of the instances cap that at 24 / 16 / 16 (poa_per_cu).  The hot arrays sit at
 // COMPILE-TIME offsets so the row loop spends no SGPRs on them.  Layout (BW = band width), alignment phases | consensus phase:
 //   [0, HR*RS*4)            hring   ring of DP rows, RS = RPADL + BW + RPADR ints each (guard cells hold 0)      | epred (2 bytes per rank)
 //   [.., + TBR*BW)          dirblk  direction rows: staged by the forward pass, block by block for the traceback      | .. sinkbits
 //   [.., + TBR*8)           rblk    row info of the last staged block (hand-over from the forward pass to the traceback)
 //   [C1, ..)                sq      (one pad byte in front, BW behind)
-// Everything else - the graph, the per-rank row info, the per-position merge arrays, the bundle scores - lives in the L2-resident HBM
-// scratch of the workgroup (GG) and is touched by lane-parallel code only.
+// The merge overlays hring / dirblk / rblk once they are free (struct MergeLds).  Everything else - the graph, the per-rank row info, the
+// per-position merge arrays of sequences too long for that overlay, the bundle scores - lives in the L2-resident HBM scratch of the
+// workgroup (GG) and is touched by lane-parallel code only.
 extern __shared__ __attribute__((aligned(16))) unsigned char poa_smem[];     // dynamic LDS of k_poa_tile (starts at LDS address 0)
 #define POA_LDS(T, off) ((T)((LDSP unsigned char*)poa_smem + (off)))
 template <int BW>
@@ -94,8 +111,12 @@ struct LLT {
     static __device__ __forceinline__ l8 sq() { return POA_LDS(l8, C1 + 16); }           // one pad byte in front (sq[-1]), BW behind
     static __device__ __forceinline__ l16 epred() { return POA_LDS(l16, 0); }
     LDSP unsigned int* sinkbits;
+    // bytes of the alignment phases: everything up to C1, then sq with 16 bytes in front of it (sq[-1]) and BW pad bytes behind the Lm sequence bytes
+    static __host__ __device__ constexpr size_t align_bytes(int Lm) { return (size_t)C1 + poa_al16((size_t)Lm + BW + 32); }
 };
-__host__ __device__ inline size_t poa_al16(size_t b) { return (b + 15) & ~(size_t)15; }
+// consensus phase: epred (2 bytes per rank) from address 0, then one sink bit per rank
+__host__ __device__ constexpr unsigned poa_sinkbits_off(int Vc) { return (unsigned)poa_al16((size_t)2 * Vc); }
+__host__ __device__ constexpr size_t poa_cons_bytes(int Vc) { return (size_t)poa_sinkbits_off(Vc) + poa_al16(((size_t)Vc + 31) / 32 * 4); }
 // A per-position u16 array of the alignment being merged (aligned rank / node, chosen node): in LDS when the sequence is short enough for the
 // regions that are free at that time (the DP ring during the traceback and the merge, the direction block during the merge), else in the
 // workgroup's HBM scratch.  `lds` is wave-uniform: every access is one scalar branch.
@@ -918,7 +939,61 @@ __device__ __forceinline__ void poa_forward(const GG& g, const LLT<64 * CPL>& w,
     bestv_out = bestv; bestpk_out = bestpk; nslow_out = nslow;
 }
 
+// ---- the LDS overlay of the merge.  After the forward pass the DP ring is free, after the traceback the direction block and the row-info block are free too: the
+// per-position and per-chunk arrays of the alignment being merged sit on top of them.  MergeLds is the ONE place that knows where each array sits, how many bytes it
+// takes and which condition makes it fit, as functions of plain integers: tile_align_add takes its offsets and its three (wave-uniform) predicates from here, the host its bound.
+//   region of LLT<BW>     seq == true                                              seq == false
+//   [HRING, DIRBLK)       alnode[L] u16, then (sh) shift[V + 1] u8                 ch_new | ch_last | ch_first from LDS address 0, up to C1
+//   [DIRBLK, RBLK)        nodeof[L] u16, then (nn) the new-node list [4][nn_cap] u16   (alnode / nodeof / shift in the HBM scratch, no list)
+//   [RBLK, C1)            ch_new[nch] u64 | ch_last[nch] u16 | ch_first[nch] u16
+//   [C1, ..)              sq: read by phases A and N, never overlaid
+template <int BW>
+struct MergeLds {
+    typedef LLT<BW> W;
+    static constexpr unsigned RING = W::DIRBLK - W::HRING, DIR = W::RBLK - W::DIRBLK, RB = W::C1 - W::RBLK;      // bytes of the three regions
+    static_assert(W::HRING % 16 == 0 && W::DIRBLK % 16 == 0 && W::RBLK % 16 == 0 && W::C1 % 16 == 0, "every overlaid array starts aligned");
+    // sizes and fit rules: functions of plain integers, the same code for the host (poa_check_limits) and the device
+    static __host__ __device__ constexpr unsigned seq_bytes(unsigned L) { return 2u * L; }                    // alnode[] / nodeof[]: one u16 per position
+    static __host__ __device__ constexpr unsigned seq_end(unsigned L) { return 2u * ((L + 7) & ~7u); }        // offset of what follows alnode[] / nodeof[] in their region
+    static __host__ __device__ constexpr unsigned chunks(unsigned L) { return (L + 63) / 64; }
+    static __host__ __device__ constexpr unsigned chunk_bytes(unsigned L) { return 12u * chunks(L); }         // u64 + u16 + u16 per 64-position chunk
+    // alnode[] ends at or below DIRBLK, nodeof[] at or below RBLK, the chunk summaries (from RBLK) at or below C1
+    static __host__ __device__ constexpr bool seq_fits(unsigned L) { return seq_bytes(L) <= RING && seq_bytes(L) <= DIR && chunk_bytes(L) <= RB; }
+    // shift[0..V] (counts fit a byte) ends below DIRBLK
+    static __host__ __device__ constexpr bool shift_fits(bool seq, unsigned L, unsigned V, unsigned nnew) { return seq && nnew <= 255u && seq_end(L) + V + 2u <= RING; }
+    // entries of the new-node list: its four u16 arrays end at or below RBLK (seq: 2 L <= DIR and DIR is a multiple of 16, so seq_end(L) <= DIR)
+    static __host__ __device__ constexpr int list_cap(bool seq, unsigned L) { return seq ? (int)(DIR - seq_end(L)) / 8 : 0; }
+    static __host__ __device__ constexpr bool list_fits(bool seq, unsigned L, int nnew) { return nnew > 0 && nnew <= list_cap(seq, L); }
+    // the arrays themselves (seq / sh as computed above; wave-uniform)
+    static __device__ __forceinline__ SeqU16 alnode(const GG& g, bool seq) { return { POA_LDS(l16, W::HRING), &g.alnode(0), seq }; }      // aligned RANK per position (NONE16 = none)
+    static __device__ __forceinline__ SeqU16 nodeof(const GG& g, bool seq) { return { POA_LDS(l16, W::DIRBLK), &g.nodeof(0), seq }; }     // existing / final rank per position
+    static __device__ __forceinline__ unsigned ch_base(bool seq) { return seq ? W::RBLK : 0u; }                                          // seq: the ring and the direction block hold alnode[] / nodeof[]
+    static __device__ __forceinline__ lu64 ch_new(bool seq) { return POA_LDS(lu64, ch_base(seq)); }                                      // [chunks] mask of the positions that need a NEW node
+    static __device__ __forceinline__ l16 ch_last(bool seq, unsigned L) { return POA_LDS(l16, ch_base(seq) + 8u * chunks(L)); }          // [chunks] aligned rank of the last aligned position, NONE16 = none
+    static __device__ __forceinline__ l16 ch_first(bool seq, unsigned L) { return ch_last(seq, L) + chunks(L); }                         // [chunks] rank chosen for the first aligned position, NONE16 = none
+    static __device__ __forceinline__ l8 sh_l(unsigned L) { return POA_LDS(l8, W::HRING + seq_end(L)); }                                 // shift[V + 1] when sh
+    static __device__ __forceinline__ l16 nn_l(unsigned L) { return POA_LDS(l16, W::DIRBLK + seq_end(L)); }                              // [4][list_cap]: position, aligned rank, nearest aligned rank at or before, reference rank
+    // shift[x] = new nodes inserted at or before old rank x (u8 in LDS when sh, else u16 in the HBM scratch); an old node moves from x to remap(x)
+    static __device__ __forceinline__ int shift(const GG& g, bool sh, unsigned L, int x) { return sh ? (int)sh_l(L)[x] : (int)g.shiftg(x); }
+    static __device__ __forceinline__ int remap(const GG& g, bool sh, unsigned L, int x) { return x + shift(g, sh, L, x); }
+    // seq == false: the chunk summaries start at LDS address 0 and must end at or below C1 (sq[-1] sits at C1 + 15).  No wave can check that for the host, so
+    // poa_check_limits refuses longer sequences: the largest L with chunk_bytes(L) <= C1
+    static __host__ __device__ constexpr unsigned max_len() { return (W::C1 / 12u) * 64u; }
+    static __host__ __device__ constexpr bool bound_ok() { return chunk_bytes(max_len()) <= W::C1 && chunk_bytes(max_len() + 1) > W::C1 && !seq_fits(max_len()); }
+};
+static_assert(MergeLds<64>::bound_ok() && MergeLds<128>::bound_ok() && MergeLds<256>::bound_ok(),
+              "max_len is the last length whose chunk summaries end below sq, and a sequence that long takes the seq == false route");
+static_assert(MergeLds<64>::max_len() == 25920 && MergeLds<128>::max_len() == 47744 && MergeLds<256>::max_len() == 91456, "the bounds DESIGN.md states");
+
 // align S to the graph and merge it.  returns 0 = dropped (no valid end cell), 1 = added, 2 = does not fit
+// This is still ONE function of eight consecutive phases (prepass, forward, best cell, traceback, A, S + D, N, E: a comment header each), with the new-node record
+// writer written out twice and the POA_REPEAT timing loops opened and closed by separate #if blocks, because every step towards one function per phase that was
+// built measured slower on the MI355X (bench.py, C3, ms per step / k_poa_tile ms, three runs each in one call; the parent 664.0 / 401.0, its spread 3.4 = the margin):
+//   - this text with only the two writer copies replaced by one __forceinline__ function:                      669.1 / 409.3  (+5.1: outside)
+//   - prepass, best cell and traceback as functions, repeats as constant ifs at the call sites, one writer:     667.9 / 410.0  (+3.9: outside)
+//   - every phase a function (two runs, another call: parent 664.3 / 405.2, spread 4.0):                        671.0 / 408.7  (+6.7: outside)
+// Results were bit-identical each time.  The builds fall into two code layouts of the forward pass (the parent's, and one with more spill reloads in the row loops,
+// k_poa_tile about 409 ms); any of the changes above tips the register allocator into the second.  profiles/poa_tile_refactor.txt section 3 has the runs.
 template <int CPL, bool SUB = false>
 __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& w, int32_t* Hg, uint8_t* Dg, uint8_t* Dfull, const PoaJobSet& J, const PSeq& S, TS& st, int lane, int& edge_out)
 {
@@ -941,8 +1016,9 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     // letter, flags) is one coalesced load per array; the only dependent loads are the anchors of the two predecessors (their band starts are recomputed
     // from them).  far[] (a successor more than HR ranks behind: the row needs an HBM copy) is a graph property kept by the merge, so the rows of a tight
     // run are known here and no second pass is needed.
-    const bool seq_lds = (unsigned)L * 2u <= (unsigned)(HR * (BW + RPADL + RPADR) * 4) && (unsigned)L * 2u <= (unsigned)(TBR * BW) && (unsigned)((L + 63) / 64) * 12u <= (unsigned)(TBR * 8);
-    const SeqU16 alnode = { POA_LDS(l16, LLT<BW>::HRING), &g.alnode(0), seq_lds }, nodeof = { POA_LDS(l16, LLT<BW>::DIRBLK), &g.nodeof(0), seq_lds };
+    typedef MergeLds<BW> ML;
+    const bool seq_lds = ML::seq_fits((unsigned)L);
+    const SeqU16 alnode = ML::alnode(g, seq_lds), nodeof = ML::nodeof(g, seq_lds);
     unsigned kinds[5] = {0, 0, 0, 0, 0};
     const bool ph_detail = POA_PHC(J) && J.phase_detail;
 #if POA_REPEAT == 1
@@ -1153,11 +1229,10 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     //             topological without a re-sort).  alnode[] keeps the aligned RANK, nodeof[] receives the existing rank or NONE16 (= a new node).
     // Per 64-position chunk phase A leaves a summary in LDS (the DP ring is free now): the mask of positions that need a NEW node, the aligned
     // rank of the chunk's last aligned position and the rank CHOSEN for its first aligned position (reused sibling or the aligned node).
-    const unsigned ch_base = seq_lds ? LLT<BW>::RBLK : 0u;                  // (the ring and the direction block hold alnode[] / nodeof[] then)
-    const lu64 ch_new = POA_LDS(lu64, ch_base);                             // [nch]
-    const l16 ch_last = POA_LDS(l16, ch_base + 8u * (unsigned)((L + 63) / 64));      // [nch] aligned rank of the last aligned position, NONE16 = none
-    const l16 ch_first = ch_last + (L + 63) / 64;                          // [nch] rank chosen for the first aligned position, NONE16 = none
-    const int nch = (L + 63) / 64;
+    const lu64 ch_new = ML::ch_new(seq_lds);                             // [nch]
+    const l16 ch_last = ML::ch_last(seq_lds, (unsigned)L);      // [nch] aligned rank of the last aligned position, NONE16 = none
+    const l16 ch_first = ML::ch_first(seq_lds, (unsigned)L);                          // [nch] rank chosen for the first aligned position, NONE16 = none
+    const int nch = (int)ML::chunks((unsigned)L);
     int nnew = 0;
     {
         int carry = -1;                                   // aligned rank of the nearest aligned position before the chunk
@@ -1205,14 +1280,14 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     //             rank ins + k.  One routine, two uses: pass 0 only needs (ins, k) to build shift[]; pass 1, after the old records have moved, writes the records.
     // shift[r] (r <= V) = new nodes inserted at or before old rank r: an old node moves from r to r + shift[r].  u8 in the LDS behind alnode[] when the counts
     // fit a byte and the ring has the room, else u16 in the HBM scratch.
-    const bool sh_lds = seq_lds && nnew <= 255 && (unsigned)(2 * ((L + 7) & ~7) + V + 2) <= (unsigned)(HR * (BW + RPADL + RPADR) * 4);
-    const l8 sh_l = POA_LDS(l8, LLT<BW>::HRING + 2u * (unsigned)((L + 7) & ~7));
+    const bool sh_lds = ML::shift_fits(seq_lds, (unsigned)L, (unsigned)V, (unsigned)nnew);
+    const l8 sh_l = ML::sh_l((unsigned)L);
     // compact list of the new nodes (position, aligned rank, nearest aligned rank at or before, reference rank) behind nodeof[] in the direction block: the
     // records of ALL new nodes are then written in one round (one dependent round trip for the anchors / ring links instead of one per 64-position chunk)
-    const int nn_cap = seq_lds ? (int)((unsigned)(TBR * BW) - 2u * (unsigned)((L + 7) & ~7)) / 8 : 0;
-    const bool nn_lds = nnew > 0 && nnew <= nn_cap;
-    const l16 nn_l = POA_LDS(l16, LLT<BW>::DIRBLK + 2u * (unsigned)((L + 7) & ~7));      // [4][nn_cap]
-    auto SH = [&](int x) __attribute__((always_inline)) -> int { return sh_lds ? (int)sh_l[x] : (int)g.shiftg(x); };
+    const int nn_cap = ML::list_cap(seq_lds, (unsigned)L);
+    const bool nn_lds = ML::list_fits(seq_lds, (unsigned)L, nnew);
+    const l16 nn_l = ML::nn_l((unsigned)L);      // [4][nn_cap]
+    auto SH = [&](int x) __attribute__((always_inline)) -> int { return ML::shift(g, sh_lds, (unsigned)L, x); };
     auto RM = [&](int x) __attribute__((always_inline)) -> int { return x + SH(x); };
     auto new_nodes = [&](const int pass) __attribute__((always_inline)) {
         int base = 0, lastal = NONE16;
@@ -1365,20 +1440,21 @@ __device__ __forceinline__ int tile_align_add(const GG& g, const LLT<64 * CPL>& 
     return 1;
 }
 
-// LDS bytes of one tile (must match the carve in k_poa_tile)
+// LDS bytes of one tile: the larger of the two phase layouts of LLT<BW>
 static size_t poa_lds_bytes(int Vc, int Ec, int Lm, int BW)
 {
     (void)Ec;
-    const size_t aln = (size_t)HR * (BW + RPADL + RPADR) * 4 + (size_t)TBR * BW + (size_t)TBR * 8 + poa_al16((size_t)Lm + BW + 32);
-    const size_t cons = poa_al16((size_t)2 * Vc) + poa_al16(((size_t)Vc + 31) / 32 * 4);
+    const size_t aln = BW == 64 ? LLT<64>::align_bytes(Lm) : BW == 128 ? LLT<128>::align_bytes(Lm) : LLT<256>::align_bytes(Lm);
+    const size_t cons = poa_cons_bytes(Vc);
     return aln > cons ? aln : cons;
 }
+// longest sequence the merge of band width BW takes (MergeLds<BW>::max_len)
+static unsigned poa_merge_max_len(int BW) { return BW == 64 ? MergeLds<64>::max_len() : BW == 128 ? MergeLds<128>::max_len() : MergeLds<256>::max_len(); }
 // HBM scratch bytes of one workgroup for the graph arrays (sub: + GG::bbr / GG::sm of the sub-graph instances)
 static size_t poa_graph_bytes(int Vc, int Ec, int Lm, bool sub)
 {
-    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t n = (size_t)Vc + 1;
-    return 3 * al(4 * n) + 3 * al(8 * n) + 2 * al(2 * n) + 3 * al(n) + 2 * al(2 * (size_t)Ec) + al(4 * (size_t)Ec) + 2 * al(2 * (size_t)Lm) + (sub ? al(2 * n) + al(n) : 0);
+    GG g; g.base = nullptr; g.set_strides(Vc, Ec, Lm);
+    return g.end(sub);
 }
 
 template <int CPL, bool SUB = false>
@@ -1388,13 +1464,9 @@ __device__ __forceinline__ void poa_tile_body(const PoaJobSet& J, uint8_t* gscra
     const int lane = threadIdx.x;
     const int Vc = J.Vcap, Ec = J.Ecap, Lm = J.Lmax;
     LLT<BW> w; GG g;
-    {
-        auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        w.sinkbits = POA_LDS(LDSP unsigned int*, (unsigned)al((size_t)2 * Vc));
-        g.base = gscratch + (size_t)blockIdx.x * gbytes;
-        g.s32 = (uint32_t)al(4 * ((size_t)Vc + 1)); g.s64 = (uint32_t)al(8 * ((size_t)Vc + 1)); g.s16 = (uint32_t)al(2 * ((size_t)Vc + 1)); g.s8 = (uint32_t)al((size_t)Vc + 1);
-        g.se16 = (uint32_t)al(2 * (size_t)Ec); g.se32 = (uint32_t)al(4 * (size_t)Ec); g.sl = (uint32_t)al(2 * (size_t)Lm);
-    }
+    w.sinkbits = POA_LDS(LDSP unsigned int*, poa_sinkbits_off(Vc));
+    g.base = gscratch + (size_t)blockIdx.x * gbytes;
+    g.set_strides(Vc, Ec, Lm);
     int32_t* Hg = J.Hglob + (size_t)blockIdx.x * Vc * BW;
     uint8_t* Dg = J.dirglob + (size_t)blockIdx.x * Vc * BW * 3 / 2;      // packed direction blocks (4 bits per cell) ...
     uint8_t* Dfull = Dg + (size_t)Vc * BW / 2;                            // ... and the byte rows of the ranks with more than two in-edges (sparse)
@@ -1481,6 +1553,8 @@ int32_t poa_check_limits(ngsid_ctx* ctx, const PoaPlan& P, int m, int g)
     for (int BW = P.band0; BW <= 256; BW *= 2) {
         const size_t lds = poa_lds_bytes(P.Vcap, P.Ecap, P.Lmax, BW);
         if (lds > 160 * 1024) POA_LIMIT(NGSID_ERR_TOO_LONG, "POA tile needs %zu bytes of LDS (> 160 KiB): sequences too long", lds);
+        // the per-chunk summaries of the merge must end below the sequence bytes in LDS (MergeLds<BW>::max_len)
+        if ((unsigned)P.Lmax > poa_merge_max_len(BW)) POA_LIMIT(NGSID_ERR_TOO_LONG, "POA sequences of up to %d bases exceed the %u the merge takes at band width %d", P.Lmax, poa_merge_max_len(BW), BW);
     }
 #undef POA_LIMIT
     return NGSID_OK;

@@ -72,6 +72,23 @@ def test_grouped_call_argument_errors(gpu_api, oracle, data, name):
         assert _eq(call(GRP, ORDER, cen), base), (name, what, "valid call after the error")
 
 
+def test_poa_merge_length_bound(gpu_api, data):
+    """Reads whose per-chunk summaries of the merge would run into the sequence bytes in LDS (k_poa.hip MergeLds<64>::max_len = 25 920 bases: 12 bytes per 64 positions
+    below LLT<64>::C1 = 4 864) are refused with NGSID_ERR_TOO_LONG before a tile is launched.  match = 2 keeps match x length below 65 536, the explicit band 64 is
+    the instance with the smallest bound, node_cap = 22 keeps the graph capacity (1.375 x length nodes, 1.5 x that edges) within the 16-bit indices and
+    still holds the edges of two reads; two reads and nothing else, so the upload is the only device work."""
+    tpl, reads, rs, cen = data
+    rng = np.random.default_rng(11)
+    long_ = "".join("ACGT"[i] for i in rng.integers(4, size=25921))      # the plan rounds the longest read up to a multiple of 16: 25 936 > 25 920
+    two = ReadSet.from_strings([long_, long_])
+    base = gpu_api.poa_consensus(rs, GRP, poa_params())
+    with pytest.raises(NgsidError) as e:
+        gpu_api.poa_consensus(two, [0, 2], poa_params(match=2, band=64, node_cap=22))
+    assert e.value.code == -6
+    assert "25920 the merge takes at band width 64" in str(e.value)
+    assert _eq(gpu_api.poa_consensus(rs, GRP, poa_params()), base), "valid call after the error"
+
+
 def _raw_cigar(api, q, t, q_idx, t_idx):
     """ngsid_sg_align_cigar_batch with a column buffer of fixed size -> return code"""
     import ctypes as C
