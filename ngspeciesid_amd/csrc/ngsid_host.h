@@ -49,7 +49,7 @@ static inline int32_t ngsid_check_lists(ngsid_ctx* ctx, const uint32_t* read_ord
     return NGSID_OK;
 }
 
-// ---- grouped-reads front end (poa_host.hip) of ngsid_polish* and of the support walk (k_support.hip): reads listed under one centre (backbone) per group.
+// ---- grouped-reads front end (polish_host.hip) of ngsid_polish* and of the support walk (k_support.hip): reads listed under one centre (backbone) per group.
 // ngsid_groups_open: argument and list checks, the reads on the device, the centres on the host.  The caller validates and clears its own outputs, returns early where
 // nothing is listed (N == 0 || G == 0), then ngsid_groups_pairs: the read -> group map (one pass over the lists; a read listed twice is an error), strands and oriented
 // copies (ngsid_polish_orient), the pairs = listed reads with a strand, in list order.  The pair vectors are pinned and belong to the calling thread: valid until its next call.

@@ -222,7 +222,7 @@ int32_t ngsid_launch_ed_align(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_
 // is a match or mismatch column; the cells of the other positions hold nothing meaningful.
 int32_t ngsid_launch_ed_align_rec(ngsid_ctx* ctx, const AlignJob& job, uint32_t max_qlen, uint32_t max_tlen, uint32_t* rec, uint32_t stride, uint16_t* pos = nullptr);
 enum { NGSID_REC_EQ = 1, NGSID_REC_SUB = 2 /* + code of the read's letter (A C G T) */, NGSID_REC_OTHER = 6 /* mismatch, read letter outside ACGT */, NGSID_REC_DEL = 7, NGSID_REC_INS = 8 };
-// poa_host.hip: first stage of ngsid_polish (strand by shared HPC minimizers + oriented copies of the reads in ctx->pol_oseq / pol_oqual); S keeps its device temporaries alive for the caller
+// polish_host.hip: first stage of ngsid_polish (strand by shared HPC minimizers + oriented copies of the reads in ctx->pol_oseq / pol_oqual); S keeps its device temporaries alive for the caller
 struct OrientBufs { DevBuf<uint32_t> d_rgroup; DevBuf<double> herr, rawerr; DevBuf<uint8_t> d_orient; };
 int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vector<std::string>& B, const std::vector<uint32_t>& h_rgroup, int k, int w, OrientBufs& S, PinVec<uint8_t>& h_orient);
 

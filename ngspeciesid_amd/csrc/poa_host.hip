@@ -1,24 +1,11 @@
-// poa_host.hip - host drivers over the POA tile engine: the depth-tiled hierarchy, ngsid_poa_consensus (a13,a14)
-// and ngsid_polish (a16,a17).  Mirrors oracle/ngsid_oracle_poa.c: run_hierarchy / ongsid_poa_consensus / ongsid_polish.
-#include "ngsid_host.h"
-#include "k_poa.h"
-#include <thread>
-#include <atomic>
+// poa_host.hip - host drivers over the POA tile engine: the depth-tiled hierarchy and ngsid_poa_consensus (a13,a14); the polisher (polish_host.hip) runs
+// its windows through run_hierarchy.  Mirrors oracle/ngsid_oracle_poa.c: run_hierarchy / ongsid_poa_consensus.
+#include "poa_host.h"
 #include <chrono>
 #include <algorithm>
-#include <vector>
-#include <string>
 #include <memory>
 
 namespace {
-
-struct Unit {                       // one consensus problem: a cluster (spoa stage) or a backbone window (polish)
-    std::vector<uint32_t> seqs;     // indices into the CURRENT level's PSeq array, in order
-    int bb = -1;                    // backbone index (into the bbs array) or -1
-    bool done = false;
-    uint32_t single_maxlen = 0;     // round 6 (single_below): set (> 0) by the caller for a unit that runs as ONE graph = the longest sequence that can enter it (reads of its members / layers, its backbone)
-    std::string result; std::vector<uint32_t> cov; bool has_result = false;
-};
 
 // weight of every base of a sequence that stands for w reads (capped like the tile consensuses of the upper levels)
 __host__ __device__ inline int32_t poa_base_weight(uint64_t w) { return w > (1u << 20) ? (1 << 20) : w < 1 ? 1 : (int32_t)w; }
@@ -46,8 +33,6 @@ __global__ void k_make_pseq_reads(const uint8_t* seq, const uint8_t* qual, const
     }
     out[i] = S;
 }
-
-struct HierParams { int m, n, g, band, node_cap, D, upper_mode; bool want_cov; int trim_tiles; int single_below = 0; bool sub = false; };      // single_below: ngsid_poa_params_t.single_below (units the caller marked with single_maxlen); sub: level 0 may hold POA_MODE_SUBGRAPH layers (the sub-graph tile instances run it)
 
 // Tile lists of a level: the sequences of every unfinished unit in tiles of hp.D (poa_ntiles), unit after unit.  The host arrays are kept across levels and
 // calls (a million entries per level; fresh allocations would page-fault every time).
@@ -536,6 +521,8 @@ static int32_t run_hierarchy_batch(ngsid_ctx* ctx, const PSeq* d_level0, uint32_
     return run_hierarchy_host(ctx, d_level0, maxlen0, d_bbs, bb_len, units, hp);
 }
 
+}  // namespace
+
 // Round 5: the level buffers of a hierarchy are sized by its level-0 tiles (output slots x graph capacity bytes per tile, + 4 bytes per base of
 // coverage when tiles are trimmed: 17.6 KB per tile of a 500-base polishing window), i.e. by the number of READS of the call - 107 GB for the two windows of 10 M
 // 750-base reads.  Units (clusters / windows) are independent hierarchies, so the call is cut into batches of whole units under a byte budget the context derives
@@ -597,8 +584,6 @@ int32_t run_hierarchy(ngsid_ctx* ctx, const PSeq* d_level0, uint32_t maxlen0, co
     return NGSID_OK;
 }
 
-}  // namespace
-
 // ---------------------------------------------------------------------------------------------- (a13,a14)
 static int32_t poa_consensus_impl(ngsid_ctx* ctx, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups,
                                   const ngsid_poa_params_t* prm, uint64_t* cons_off, uint8_t* cons, uint64_t cons_cap, uint64_t* needed, uint32_t* cov, const uint32_t* weight = nullptr);
@@ -653,483 +638,10 @@ static int32_t poa_consensus_impl(ngsid_ctx* ctx, const ngsid_reads_t* reads, co
     htc.mark("units");
     rc = run_hierarchy(ctx, d_seqs.p, RD.maxlen, nullptr, nobb, units, hp); if (rc) return rc;
     htc.mark("hierarchy");
-    uint64_t total = 0; bool overflow = false; cons_off[0] = 0;
-    for (uint64_t g = 0; g < n_groups; ++g) {
-        const std::string& s = units[g].result;
-        if (total + s.size() <= cons_cap && cons) { memcpy(cons + total, s.data(), s.size()); if (cov && units[g].cov.size() == s.size() && !s.empty()) memcpy(cov + total, units[g].cov.data(), 4 * s.size()); else if (cov) for (size_t x = 0; x < s.size(); ++x) cov[total + x] = 0; }
-        else if (s.size()) overflow = true;
-        total += s.size(); cons_off[g + 1] = total;
+    rc = ngsid_pack_strings(ctx, "consensus", n_groups, [&](size_t g) -> const std::string& { return units[g].result; }, cons_off, cons, cons_cap, needed);
+    if (cov && cons) for (uint64_t g = 0; g < n_groups && cons_off[g + 1] <= cons_cap; ++g) {      // the coverage of every consensus that fitted (zeros where the hierarchy returned none)
+        const uint64_t a = cons_off[g], len = cons_off[g + 1] - a;
+        if (units[g].cov.size() == len && len) memcpy(cov + a, units[g].cov.data(), 4 * len); else std::fill(cov + a, cov + a + len, 0u);
     }
-    if (needed) *needed = total;
-    if (overflow) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "consensus buffer too small: need %llu bytes", (unsigned long long)total);
-    return NGSID_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- (a16,a17)
-namespace {
-
-__global__ __launch_bounds__(256)
-void k_strand(const uint64_t* __restrict__ mzoff /* compact CSR offsets of the reads' minimizers */, const uint32_t* __restrict__ mzcnt, const uint32_t* __restrict__ hlen, const uint64_t* __restrict__ mzcode, int k,
-              const uint32_t* __restrict__ rgroup, const uint64_t* __restrict__ bcodes, const uint64_t* __restrict__ boff /* 2G+1: fw lists then rc lists */, uint32_t G,
-              uint64_t n, uint8_t* __restrict__ orient)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const uint32_t g = rgroup[r];
-    if (g == 0xffffffffu) { if (lane == 0) orient[r] = 255; return; }        // read belongs to no group
-    const uint32_t M = hlen[r] >= (uint32_t)k ? mzcnt[r] : 0;
-    const uint64_t* cf = bcodes + boff[g]; const uint32_t nf = (uint32_t)(boff[g + 1] - boff[g]);
-    const uint64_t* cr = bcodes + boff[G + g]; const uint32_t nr = (uint32_t)(boff[G + g + 1] - boff[G + g]);
-    int a = 0, b = 0;
-    for (uint32_t x = lane; x < M; x += 64) {
-        const uint64_t code = mzcode[mzoff[r] + x];
-        uint32_t lo = 0, hi = nf; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cf[mid] < code) lo = mid + 1; else hi = mid; }
-        a += (lo < nf && cf[lo] == code);
-        lo = 0; hi = nr; while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cr[mid] < code) lo = mid + 1; else hi = mid; }
-        b += (lo < nr && cr[lo] == code);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
-    if (lane == 0) orient[r] = (a == 0 && b == 0) ? 255 : (b > a ? 1 : 0);
-}
-
-// Polishing windows of a backbone of Bl bases: W bases each; a last window shorter than W/10 is merged into the one before it.  (racon keeps it:
-// only layers of at least 0.02 W bases enter a window, so a 7-base tail window is built from the reads that carry INSERTIONS there and the
-// consensus gains bases - seen on 5 007-base amplicons.)  Window w covers [w * W, w == nwin - 1 ? Bl : (w + 1) * W).
-__host__ __device__ __forceinline__ int polish_nwin(int Bl, int W) { const int raw = Bl <= W ? 1 : (Bl + W - 1) / W; const int tail = Bl - (raw - 1) * W; return (raw >= 2 && tail < W / 10) ? raw - 1 : raw; }
-__host__ __device__ __forceinline__ int polish_wlen(int Bl, int W, int w) { return w == polish_nwin(Bl, W) - 1 ? Bl - w * W : W; }
-
-__device__ __forceinline__ uint8_t comp_base(uint8_t c) { switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; } }
-
-__global__ void k_orient(const uint8_t* __restrict__ seq, const uint8_t* __restrict__ qual, const uint64_t* __restrict__ off, uint64_t n,
-                         const uint8_t* __restrict__ orient, uint8_t* __restrict__ oseq, uint8_t* __restrict__ oqual)
-{
-    const uint64_t r = blockIdx.x;
-    if (r >= n) return;
-    const uint64_t b = off[r]; const int len = (int)(off[r + 1] - b); const bool rc = orient[r] == 1;
-    for (int i = threadIdx.x; i < len; i += blockDim.x) {
-        if (rc) { oseq[b + i] = comp_base(seq[b + len - 1 - i]); if (qual) oqual[b + i] = qual[b + len - 1 - i]; }
-        else { oseq[b + i] = seq[b + i]; if (qual) oqual[b + i] = qual[b + i]; }
-    }
-}
-
-// one wave per (pair, window): validity filters of racon's window assignment + the PSeq of the layer (oracle ongsid_polish);
-// the lanes share the mean-quality sum over the layer's bases (coalesced), everything else is wave-uniform
-__global__ __launch_bounds__(256) void k_layers(const uint8_t* __restrict__ oseq, const uint8_t* __restrict__ oqual, const uint64_t* __restrict__ off,
-                         const uint32_t* __restrict__ pair_read, const uint32_t* __restrict__ pair_group, uint64_t npairs, int nwinmax,
-                         const int32_t* __restrict__ bp, const int32_t* __restrict__ span, const int32_t* __restrict__ blen /* per group */,
-                         int W, double qthr, double ethr, int sub /* NGSID_ALN_SUBGRAPH: a layer that does not span its window gets POA_MODE_SUBGRAPH */,
-                         PSeq* __restrict__ lay, uint16_t* __restrict__ valid /* 0 = no layer, else 1 + its first window position */, int* __restrict__ maxlen_out)
-{
-    const int lane = threadIdx.x & 63;
-    const uint64_t t = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (t >= npairs * (uint64_t)nwinmax) return;
-    const uint64_t p = t / nwinmax; const int wdx = (int)(t % nwinmax);
-    if (lane == 0) valid[t] = 0;
-    const int qb = span[p * 4 + 0], qe = span[p * 4 + 1], tb = span[p * 4 + 2], te = span[p * 4 + 3];
-    if (qb < 0) return;
-    const int qs = qe - qb + 1, ts = te - tb + 1; const int mn = qs < ts ? qs : ts, mx = qs < ts ? ts : qs;
-    if (1.0 - (double)mn / (double)mx > ethr) return;
-    const int Bl = blen[pair_group[p]]; const int nw = polish_nwin(Bl, W);
-    if (wdx >= nw) return;
-    const int32_t* b = bp + (p * (uint64_t)nwinmax + wdx) * 4;
-    int qf = b[0], ql = b[1], tf = b[2], tl = b[3];
-    if (wdx == nw - 1 && wdx + 1 < nwinmax && (Bl + W - 1) / W > nw) {       // merged tail window: the aligner's break points of the two raw windows are joined
-        const int32_t* b2 = b + 4;
-        if (b2[0] >= 0) { if (qf < 0) { qf = b2[0]; tf = b2[2]; } ql = b2[1]; tl = b2[3]; }
-    }
-    if (qf < 0) return;
-    const int len = ql - qf + 1; if ((double)len < 0.02 * (double)W) return;
-    const uint32_t read = pair_read[p]; const uint64_t rb = off[read];
-    if (oqual) {
-        long long sq = 0;
-        for (int x = qf + lane; x <= ql; x += 64) sq += (long long)oqual[rb + x] - 33;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) sq += __shfl_xor(sq, d);
-        if ((double)sq / (double)len < qthr) return;
-    }
-    const int ws = wdx * W; const int wlen = polish_wlen(Bl, W, wdx);
-    const int begin = tf - ws, end = tl - ws; const int offset = (int)(0.01 * (double)wlen);
-    PSeq S; S.s = oseq + rb + qf; S.q = oqual ? oqual + rb + qf : nullptr; S.len = len; S.uw = 1; S.cw = 1; S.a0 = begin; S.a1 = end;
-    S.mode = (begin < offset && end > wlen - offset) ? NGSID_POA_GLOBAL : (sub ? POA_MODE_SUBGRAPH : NGSID_POA_SEMI);
-    if (lane == 0) { lay[t] = S; valid[t] = (uint16_t)((begin < 0 ? 0 : (begin > 65533 ? 65533 : begin)) + 1); if (len > __atomic_load_n(maxlen_out, __ATOMIC_RELAXED)) atomicMax(maxlen_out, len); }      // (millions of atomics on one word would serialise)
-}
-
-std::string revcomp(const std::string& s) { std::string r(s.size(), 'N'); for (size_t i = 0; i < s.size(); ++i) { char c = s[s.size() - 1 - i]; r[i] = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N'; } return r; }
-
-}  // namespace
-
-struct PolishTrace { std::vector<std::string> seq; std::vector<uint64_t> used;           // [it * G + g]: the backbones after every iteration
-                     int32_t* aln = nullptr; };                                          // ngsid_polish_trace_aln: [(it * n_listed + x) * 6 ...] = the read -> backbone alignment of listed read x in iteration it
-
-static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                           uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used, PolishTrace* trace);
-
-extern "C" int32_t ngsid_polish(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                                const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                                uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used)
-{
-    ApiClock api_clock_(ctx, "polish");
-    return polish_impl(ctx, backbones, reads, read_order, grp_off, n_groups, prm, out_off, out, out_cap, needed, n_used, nullptr);
-}
-
-static int32_t polish_trace_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                                 const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                                 uint64_t* it_off, uint8_t* it_out, uint64_t it_cap, uint64_t* needed, uint64_t* it_used, int32_t* it_aln)
-{
-    if (!ctx) return NGSID_ERR_ARG;
-    if (!prm || !it_off || prm->iters < 1) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_polish_trace: null argument or iters < 1");
-    PolishTrace tr; tr.aln = it_aln; std::vector<uint64_t> ooff(n_groups + 1, 0); uint64_t need1 = 0;
-    const int32_t rc = polish_impl(ctx, backbones, reads, read_order, grp_off, n_groups, prm, ooff.data(), nullptr, 0, &need1, nullptr, &tr);
-    if (rc != NGSID_OK) return rc;                                        // (with a trace the inner call copies nothing out and checks no capacity: ADVICE r4)
-    if (tr.seq.size() != (size_t)prm->iters * n_groups || tr.used.size() != tr.seq.size()) NGSID_FAIL(ctx, NGSID_ERR_HIP, "internal: polish trace holds %zu entries for %d x %llu", tr.seq.size(), (int)prm->iters, (unsigned long long)n_groups);
-    uint64_t total = 0; bool ovf = false; it_off[0] = 0;
-    for (size_t x = 0; x < tr.seq.size(); ++x) {
-        if (it_out && total + tr.seq[x].size() <= it_cap) memcpy(it_out + total, tr.seq[x].data(), tr.seq[x].size()); else if (tr.seq[x].size()) ovf = true;
-        total += tr.seq[x].size(); it_off[x + 1] = total; if (it_used) it_used[x] = tr.used[x];
-    }
-    if (needed) *needed = total;
-    if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "trace buffer too small: need %llu bytes", (unsigned long long)total);
-    return NGSID_OK;
-}
-extern "C" int32_t ngsid_polish_trace(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                                      const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                                      uint64_t* it_off, uint8_t* it_out, uint64_t it_cap, uint64_t* needed, uint64_t* it_used)
-{
-    ApiClock api_clock_(ctx, "polish_trace");
-    return polish_trace_impl(ctx, backbones, reads, read_order, grp_off, n_groups, prm, it_off, it_out, it_cap, needed, it_used, nullptr);
-}
-// (a17, boundary 8b(1)) ngsid_polish_trace + what minimap2 leaves in read_alignments_it_{i}.paf (consensus.py:112-121): the read -> backbone alignment of every LISTED read in
-// every iteration, it_aln[(it * n_listed + x) * 6 ...] = {strand (0 +, 1 -, -1 = not aligned: no PAF line), q_begin, q_end, t_begin, t_end, edit distance}, PAF coordinates
-// (0-based, end exclusive, the query interval on the read's ORIGINAL strand); n_listed = grp_off[n_groups].
-extern "C" int32_t ngsid_polish_trace_aln(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                                          const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                                          uint64_t* it_off, uint8_t* it_out, uint64_t it_cap, uint64_t* needed, uint64_t* it_used, int32_t* it_aln)
-{
-    ApiClock api_clock_(ctx, "polish_trace");
-    if (ctx && !it_aln) NGSID_FAIL(ctx, NGSID_ERR_ARG, "ngsid_polish_trace_aln: null alignment buffer");
-    return polish_trace_impl(ctx, backbones, reads, read_order, grp_off, n_groups, prm, it_off, it_out, it_cap, needed, it_used, it_aln);
-}
-
-// First stage of ngsid_polish, shared with ngsid_consensus_support (k_support.hip): the strand of every read against the backbone B[g] of its group h_rgroup[r] (h_orient: 0 forward,
-// 1 reverse complement, 255 = in no group or no shared minimizer) and the oriented copies of the reads in ctx->pol_oseq / pol_oqual (k_orient, in flight on the stream at return).
-int32_t ngsid_polish_orient(ngsid_ctx* ctx, const DevReads& RD, const std::vector<std::string>& B, const std::vector<uint32_t>& h_rgroup, int k, int w, OrientBufs& S, PinVec<uint8_t>& h_orient)
-{
-    const uint64_t N = RD.n; const uint32_t G = (uint32_t)B.size(); int32_t rc;
-    // ---- strand detection (replaces minimap2's strand call): shared HPC minimizers with the initial backbone, fw vs rc
-    DevBuf<uint64_t>& mzcode = ctx->pol_mzcode; DevBuf<uint32_t>& mzcnt = ctx->mzc_cnt; DevBuf<uint32_t>& hlen = ctx->mzc_hlen; DevBuf<uint32_t>& d_rgroup = S.d_rgroup; DevBuf<double>& herr = S.herr; DevBuf<double>& rawerr = S.rawerr; DevBuf<uint8_t>& d_orient = S.d_orient;
-    HIPCHK(ctx, mzcnt.reserve(N)); HIPCHK(ctx, hlen.reserve(N));
-    NGSID_TRY(dev_put(ctx, d_rgroup, h_rgroup.data(), N)); HIPCHK(ctx, d_orient.alloc(N));
-    const int sk = std::min(k, 21), sw = std::max(w, sk);       // strand detection only needs SOME minimizer scheme: one-word codes, comparable between the two launches
-    {   // the clustering call that preceded this one left the minimizers of the same reads in the context (same bases, offsets, k, w): reuse them
-        bool hit = false;
-        if (ctx->mzc.valid && ctx->mzc.n == N && ctx->mzc.total == RD.total && ctx->mzc.k == sk && ctx->mzc.w == sw) {
-            unsigned long long fp = 0; rc = ngsid_reads_fingerprint(ctx, RD, &fp); if (rc) return rc;
-            hit = fp == ctx->mzc.fp;
-        }
-        if (!hit) {
-            ctx->mzc.valid = false;
-            HIPCHK(ctx, herr.alloc(N)); HIPCHK(ctx, rawerr.alloc(N));
-            static thread_local PinVec<uint32_t> h_c, h_l; h_c.resize(N); h_l.resize(N); long long bad = -1;
-            rc = ngsid_minimizers_csr(ctx, RD, sk, sw, ngsid_ctx_mz(ctx), mzcnt.p, hlen.p, herr.p, rawerr.p, h_c.data(), h_l.data(), &bad); if (rc) return rc;
-            if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "base outside ACGTN in a read (read %lld)", bad);       // (the cache stays invalid: ADVICE r4)
-            if (N >= 1024) { unsigned long long fp = 0; rc = ngsid_reads_fingerprint(ctx, RD, &fp); if (rc) return rc; ctx->mzc.n = N; ctx->mzc.total = RD.total; ctx->mzc.k = sk; ctx->mzc.w = sw; ctx->mzc.fp = fp; ctx->mzc.valid = true; }
-        }
-    }
-    {
-        // backbone fw + rc minimizers through the same kernel (a CSR of their own), then sorted on the host (a handful of short lists)
-        std::vector<std::string> two; for (uint32_t g = 0; g < G; ++g) two.push_back(B[g]); for (uint32_t g = 0; g < G; ++g) two.push_back(revcomp(B[g]));
-        std::vector<uint64_t> toff(2 * G + 1, 0); std::string cat; for (size_t i = 0; i < two.size(); ++i) { cat += two[i]; toff[i + 1] = cat.size(); }
-        ngsid_reads_t br{(const uint8_t*)cat.data(), nullptr, toff.data(), 2ull * G, NGSID_MEM_HOST, 0};
-        DevReads BR; rc = ngsid_upload_reads(ctx, &br, &BR, false); if (rc) return rc;
-        SketchBufs K; long long bad;
-        rc = ngsid_sketch(ctx, BR, sk, sw, K, &bad); if (rc) return rc;
-        if (bad >= 0) NGSID_FAIL(ctx, NGSID_ERR_ALPHABET, "base outside ACGTN in a backbone");
-        const PinVec<uint64_t>& hmo = K.h_off; const uint64_t btot = hmo[2 * G];
-        std::vector<uint64_t> hc(btot + 1);
-        NGSID_TRY(dev_get(ctx, hc.data(), K.code.p, btot));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<uint64_t> lists, loff(2 * G + 1, 0);
-        for (uint32_t i = 0; i < 2 * G; ++i) {
-            const uint32_t c = K.h_hlen[i] >= (uint32_t)sk ? K.h_cnt[i] : 0;
-            std::vector<uint64_t> v(hc.begin() + hmo[i], hc.begin() + hmo[i] + c); std::sort(v.begin(), v.end());
-            lists.insert(lists.end(), v.begin(), v.end()); loff[i + 1] = lists.size();
-        }
-        DevBuf<uint64_t> d_lists, d_loff; NGSID_TRY(dev_put(ctx, d_lists, lists.data(), lists.size())); NGSID_TRY(dev_put(ctx, d_loff, loff.data(), loff.size()));
-        { ProfScope ps_(ctx, "k_strand"); hipLaunchKernelGGL(k_strand, dim3(NGSID_GRID(ctx, (N + 3) / 4, 256, "k_strand")), dim3(256), 0, ctx->stream, ctx->mz_off.p, mzcnt.p, hlen.p, mzcode.p, sk, d_rgroup.p, d_lists.p, d_loff.p, G, N, d_orient.p); }
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    h_orient.resize(N);
-    NGSID_TRY(dev_get(ctx, h_orient.data(), d_orient.p, N)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // ---- oriented copies of the reads
-    DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual; HIPCHK(ctx, oseq.reserve(RD.total + 16)); if (RD.qual) HIPCHK(ctx, oqual.reserve(RD.total + 16));
-    { ProfScope ps_(ctx, "k_orient"); hipLaunchKernelGGL(k_orient, dim3(NGSID_GRID(ctx, N, 128, "k_orient")), dim3(128), 0, ctx->stream, RD.seq, RD.qual, RD.off, N, d_orient.p, oseq.p, RD.qual ? oqual.p : nullptr); }
-    HIPCHK(ctx, hipGetLastError());
-    return NGSID_OK;
-}
-
-// The grouped-reads front end (ngsid_host.h), first half: argument and list checks, the reads on the device, the centres on the host
-int32_t ngsid_groups_open(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid_reads_t* reads, const uint32_t* read_order, const uint64_t* grp_off, uint64_t n_groups, GroupedReads& S)
-{
-    if (!centres || !reads || !grp_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    if (centres->n != n_groups) NGSID_FAIL(ctx, NGSID_ERR_ARG, "one centre (backbone) per group expected");
-    NGSID_TRY(ngsid_upload_reads(ctx, reads, &S.RD, false));
-    NGSID_TRY(ngsid_check_lists(ctx, read_order, grp_off, n_groups, S.RD.n));
-    const uint32_t G = (uint32_t)n_groups; S.G = G; S.N = S.RD.n; S.NL = grp_off[n_groups];
-    S.boff.assign(G + 1, 0); S.B.resize(G);
-    if (G) {
-        if (centres->mem == NGSID_MEM_DEVICE) {
-            HIPCHK(ctx, hipMemcpy(S.boff.data(), centres->off, 8 * (G + 1), hipMemcpyDeviceToHost)); S.bseq.resize(S.boff[G] + 1);
-            if (S.boff[G]) HIPCHK(ctx, hipMemcpy(S.bseq.data(), centres->seq, S.boff[G], hipMemcpyDeviceToHost));
-        } else { memcpy(S.boff.data(), centres->off, 8 * (G + 1)); S.bseq.assign(centres->seq, centres->seq + S.boff[G]); S.bseq.push_back(0); }
-    }
-    for (uint32_t g = 0; g < G; ++g) { S.B[g].assign((const char*)S.bseq.data() + S.boff[g], (size_t)(S.boff[g + 1] - S.boff[g])); S.maxb = std::max<uint32_t>(S.maxb, (uint32_t)S.B[g].size()); }
-    return NGSID_OK;
-}
-
-// ... second half: the read -> group map, strands and oriented copies, the pairs in list order (group by group)
-int32_t ngsid_groups_pairs(ngsid_ctx* ctx, const uint32_t* read_order, const uint64_t* grp_off, int k, int w, GroupedReads& S, int8_t* strand)
-{
-    static thread_local PinVec<uint8_t> h_orient; static thread_local PinVec<uint32_t> pair_read, pair_group, pair_x;
-    S.h_orient = &h_orient; S.pair_read = &pair_read; S.pair_group = &pair_group; S.pair_x = &pair_x; pair_read.clear(); pair_group.clear(); pair_x.clear();
-    const uint32_t G = S.G; const OffView& off = S.RD.h_off;
-    S.h_rgroup.assign(S.N, 0xffffffffu); S.gbases.assign(G, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        uint64_t tot = 0;
-        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-            const uint64_t r = read_order ? read_order[x] : x;
-            if (S.h_rgroup[r] != 0xffffffffu) NGSID_FAIL(ctx, NGSID_ERR_ARG, "read %llu is listed twice (groups %u and %u): strand and layers are kept per read, list every read under one centre (backbone)", (unsigned long long)r, S.h_rgroup[r], g);
-            S.h_rgroup[r] = g; tot += off[r + 1] - off[r];
-        }
-        S.gbases[g] = tot;
-    }
-    NGSID_TRY(ngsid_polish_orient(ctx, S.RD, S.B, S.h_rgroup, k, w, S.ob, h_orient));
-    S.gbeg.assign(G + 1, 0);
-    for (uint32_t g = 0; g < G; ++g) {
-        for (uint64_t x = grp_off[g]; x < grp_off[g + 1]; ++x) {
-            const uint64_t r = read_order ? read_order[x] : x;
-            if (h_orient[r] == 255) continue;
-            pair_read.push_back((uint32_t)r); pair_group.push_back(g); pair_x.push_back((uint32_t)x); if (strand) strand[x] = (int8_t)h_orient[r];
-        }
-        S.gbeg[g + 1] = pair_read.size();
-    }
-    S.NP = pair_read.size();
-    return NGSID_OK;
-}
-
-static int32_t polish_impl(ngsid_ctx* ctx, const ngsid_reads_t* backbones, const ngsid_reads_t* reads, const uint32_t* read_order,
-                           const uint64_t* grp_off, uint64_t n_groups, const ngsid_polish_params_t* prm,
-                           uint64_t* out_off, uint8_t* out, uint64_t out_cap, uint64_t* needed, uint64_t* n_used, PolishTrace* trace)
-{
-    if (!ctx) return NGSID_ERR_ARG;
-    if (!prm || !out_off) NGSID_FAIL(ctx, NGSID_ERR_ARG, "null argument");
-    HostTimer ht(ctx->stream, "polish");
-    GroupedReads S; int32_t rc = ngsid_groups_open(ctx, backbones, reads, read_order, grp_off, n_groups, S); if (rc) return rc;
-    const DevReads& RD = S.RD; std::vector<std::string>& B = S.B;       // (the backbones are tiny and are rebuilt on the host after every iteration)
-    const uint64_t N = S.N; const uint32_t G = S.G;
-    const int W = prm->window > 0 ? prm->window : 500;
-    ht.mark("upload + checks");
-    if (N == 0 || G == 0) {
-        uint64_t total = 0; out_off[0] = 0; bool ovf = false;
-        for (uint32_t g = 0; g < G; ++g) { if (trace) {} else if (total + B[g].size() <= out_cap && out) memcpy(out + total, B[g].data(), B[g].size()); else if (B[g].size()) ovf = true; total += B[g].size(); out_off[g + 1] = total; if (n_used) n_used[g] = 0; }
-        if (trace) for (int it = 0; it < prm->iters; ++it) for (uint32_t g = 0; g < G; ++g) { trace->seq.push_back(B[g]); trace->used.push_back(0); }
-        if (trace && trace->aln) for (uint64_t x = 0; x < (uint64_t)prm->iters * grp_off[n_groups] * 6; ++x) trace->aln[x] = -1;
-        if (needed) *needed = total; if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "output buffer too small"); return NGSID_OK;
-    }
-    // ---- strands and pairs (usable reads of reads that belong to a group), fixed over the iterations; the TGS/NGS window type of a group from the mean length of its reads
-    DevBuf<int> flag; HIPCHK(ctx, flag.alloc(1));
-    rc = ngsid_groups_pairs(ctx, read_order, grp_off, prm->k, prm->w, S); if (rc) return rc;
-    std::vector<uint8_t> tgs(G, 0);
-    for (uint32_t g = 0; g < G; ++g) { const uint64_t ns = grp_off[g + 1] - grp_off[g]; tgs[g] = ns > 0 && ((double)S.gbases[g] / (double)ns) > 1000.0; }
-    DevBuf<uint8_t>& oseq = ctx->pol_oseq; DevBuf<uint8_t>& oqual = ctx->pol_oqual;
-    PinVec<uint8_t>& h_orient = *S.h_orient; PinVec<uint32_t> &pair_read = *S.pair_read, &pair_group = *S.pair_group, &pair_pos = *S.pair_x;      // (pair_pos: the alignment trace's position of a pair's read in the caller's list)
-    ht.mark("group map + minimizers + strand + orient");
-    const bool want_aln = trace && trace->aln; const uint64_t NL = grp_off[n_groups];
-    DevBuf<int32_t> d_dist; static thread_local PinVec<int32_t> h_span, h_dist;
-    if (want_aln) { HIPCHK(ctx, d_dist.alloc(pair_read.size() + 1)); h_span.resize(pair_read.size() * 4 + 4); h_dist.resize(pair_read.size() + 1); }
-    uint64_t NP = pair_read.size();
-    DevBuf<uint32_t> d_pair_read, d_pair_group; DevBuf<int32_t> d_open, d_span, d_blen; DevBuf<int32_t>& d_bp = ctx->pol_bp; DevBuf<uint8_t>& d_lay_raw = ctx->pol_lay; DevBuf<uint16_t>& d_valid = ctx->pol_valid;
-    NGSID_TRY(dev_put(ctx, d_pair_read, pair_read.data(), NP)); NGSID_TRY(dev_put(ctx, d_pair_group, pair_group.data(), NP)); HIPCHK(ctx, d_open.alloc(NP)); HIPCHK(ctx, d_span.alloc(NP * 4)); HIPCHK(ctx, d_blen.alloc(G));
-    if (NP) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)d_open.p, prm->aln_open, NP, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> used(G, 0);
-    ht.mark("orient + pairs");
-
-    std::vector<uint8_t> stable(G, 0);              // stop_when_stable: groups whose last iteration returned the backbone unchanged
-    for (int it = 0; it < prm->iters; ++it) {
-        if (prm->stop_when_stable && it > 0) {
-            bool any_active = false; for (uint32_t g = 0; g < G; ++g) any_active = any_active || !stable[g];
-            if (!any_active) break;
-            // drop the pairs of the stable groups (their reads would be aligned and stacked into exactly the same windows again)
-            size_t keep = 0;
-            for (size_t p = 0; p < pair_read.size(); ++p) if (!stable[pair_group[p]]) { pair_read[keep] = pair_read[p]; pair_group[keep] = pair_group[p]; if (want_aln) pair_pos[keep] = pair_pos[p]; ++keep; }
-            if (keep != pair_read.size()) {
-                pair_read.resize(keep); pair_group.resize(keep); NP = keep; if (want_aln) pair_pos.resize(keep);
-                if (NP) { HIPCHK(ctx, hipMemcpyAsync(d_pair_read.p, pair_read.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream)); HIPCHK(ctx, hipMemcpyAsync(d_pair_group.p, pair_group.data(), 4 * NP, hipMemcpyHostToDevice, ctx->stream)); HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); }
-            }
-        }
-        // upload the current backbones
-        std::vector<uint64_t> boff(G + 1, 0); std::string cat; std::vector<int32_t> blen(G); int nwinmax = 1; uint32_t maxb = 0;
-        for (uint32_t g = 0; g < G; ++g) { cat += B[g]; boff[g + 1] = cat.size(); blen[g] = (int32_t)B[g].size(); nwinmax = std::max(nwinmax, (int)((B[g].size() + W - 1) / W)); maxb = std::max<uint32_t>(maxb, (uint32_t)B[g].size()); }
-        ngsid_reads_t br{(const uint8_t*)cat.data(), nullptr, boff.data(), G, NGSID_MEM_HOST, 0};
-        DevReads BB; rc = ngsid_upload_reads(ctx, &br, &BB, false); if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(d_blen.p, blen.data(), 4 * G, hipMemcpyHostToDevice, ctx->stream));
-        for (uint32_t g = 0; g < G; ++g) if (!stable[g]) used[g] = 0;
-        std::vector<Unit> units; std::vector<PSeq> bbs; std::vector<int> bb_len; std::vector<std::pair<uint32_t, int>> unit_gw;
-        static thread_local PinVec<uint16_t> h_valid; int max_layer = 1;
-        HIPCHK(ctx, hipMemsetAsync(flag.p, 0, sizeof(int), ctx->stream));
-        if (NP) {
-            HIPCHK(ctx, d_bp.reserve(NP * (uint64_t)nwinmax * 4)); HIPCHK(ctx, d_lay_raw.reserve(sizeof(PSeq) * NP * (uint64_t)nwinmax)); HIPCHK(ctx, d_valid.reserve(NP * (uint64_t)nwinmax));
-            AlignJob J{};
-            J.qseq = oseq.p; J.qoff = RD.off; J.tseq = BB.seq; J.toff = BB.off; J.qidx = d_pair_read.p; J.tidx = d_pair_group.p; J.npairs = NP;
-            J.match = prm->aln_match; J.mismatch = prm->aln_mismatch; J.ext = prm->aln_ext; J.k = 1; J.open = d_open.p; J.match_id = nullptr;
-            J.score = nullptr; J.ncols = nullptr; J.nmatch = nullptr; J.region = nullptr; J.bp = d_bp.p; J.bp_windows = nwinmax; J.window = W; J.span = d_span.p;
-            int aln_mode = prm->aln_mode & ~NGSID_ALN_SUBGRAPH; if (aln_mode == 2) aln_mode = 1;      // (the sub-graph flag is a rule of the window layers, not of this aligner)
-            if (aln_mode == 3) { aln_mode = 1; J.clip = 1; }          // edit distance + overlap-span clipping (include/ngsid.h)
-            if (aln_mode == 1) rc = ngsid_launch_ed_align(ctx, J, RD.maxlen, maxb, want_aln ? d_dist.p : nullptr);          // unit-cost, bit-parallel (k_ed_align.hip)
-            else rc = ngsid_launch_align(ctx, J, RD.maxlen, maxb, prm->aln_open);
-            if (rc) return rc;
-            const uint64_t T = NP * (uint64_t)nwinmax;
-            { ProfScope ps_(ctx, "k_layers"); hipLaunchKernelGGL(k_layers, dim3(NGSID_GRID(ctx, (T + 3) / 4, 256, "k_layers")), dim3(256), 0, ctx->stream, oseq.p, RD.qual ? oqual.p : nullptr, RD.off, d_pair_read.p, d_pair_group.p, NP, nwinmax,
-                               d_bp.p, d_span.p, d_blen.p, W, prm->quality_threshold, prm->error_threshold, (prm->aln_mode & NGSID_ALN_SUBGRAPH) ? 1 : 0, (PSeq*)d_lay_raw.p, d_valid.p, flag.p); }
-            HIPCHK(ctx, hipGetLastError());
-            h_valid.resize(T);
-            HIPCHK(ctx, hipMemcpyAsync(&max_layer, flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(h_valid.data(), d_valid.p, 2 * T, hipMemcpyDeviceToHost, ctx->stream));
-            if (want_aln) { HIPCHK(ctx, hipMemcpyAsync(h_span.data(), d_span.p, 16 * NP, hipMemcpyDeviceToHost, ctx->stream)); if (aln_mode == 1) HIPCHK(ctx, hipMemcpyAsync(h_dist.data(), d_dist.p, 4 * NP, hipMemcpyDeviceToHost, ctx->stream)); }
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-            if (want_aln) {        // this iteration's records: the previous iteration's for the groups that are stable (same backbone, same reads: the same alignments), fresh ones for the pairs just aligned
-                int32_t* A = trace->aln + (size_t)it * NL * 6;
-                if (it == 0) for (uint64_t x = 0; x < NL * 6; ++x) A[x] = -1; else memcpy(A, A - NL * 6, sizeof(int32_t) * NL * 6);
-                for (uint64_t p = 0; p < NP; ++p) {
-                    int32_t* a = A + (size_t)pair_pos[p] * 6; const uint32_t r = pair_read[p]; const int32_t ql = (int32_t)(RD.h_off[r + 1] - RD.h_off[r]);
-                    const int32_t qf = h_span[p * 4], qe = h_span[p * 4 + 1], tf = h_span[p * 4 + 2], te = h_span[p * 4 + 3];
-                    if (qf < 0) { for (int c = 0; c < 6; ++c) a[c] = -1; continue; }
-                    const bool rcs = h_orient[r] == 1;
-                    a[0] = rcs ? 1 : 0; a[1] = rcs ? ql - 1 - qe : qf; a[2] = rcs ? ql - qf : qe + 1; a[3] = tf; a[4] = te + 1; a[5] = aln_mode == 1 ? h_dist[p] : -1;
-                }
-            }
-        } else if (want_aln) { int32_t* A = trace->aln + (size_t)it * NL * 6; if (it == 0) for (uint64_t x = 0; x < NL * 6; ++x) A[x] = -1; else memcpy(A, A - NL * 6, sizeof(int32_t) * NL * 6); }
-        ht.mark("align + layers + valid copy");
-        // ---- units = (group, window) with their layers in read order
-        std::vector<std::vector<int>> unit_of(G);
-        for (uint32_t g = 0; g < G; ++g) { if (stable[g]) continue; const int nw = polish_nwin((int)B[g].size(), W); unit_of[g].assign(nw, -1);
-            for (int wdx = 0; wdx < nw; ++wdx) { unit_of[g][wdx] = (int)units.size(); units.emplace_back(); unit_gw.push_back({g, wdx}); } }
-        {   // layers of every window in pair (= read) order; the units of a group are consecutive, a window holds at most one layer per pair of its group
-            std::vector<uint32_t> ubase(G), unw(G), npg(G, 0);
-            for (uint32_t g = 0; g < G; ++g) { unw[g] = (uint32_t)unit_of[g].size(); ubase[g] = unw[g] ? (uint32_t)unit_of[g][0] : 0; }
-            for (uint64_t p = 0; p < NP; ++p) npg[pair_group[p]]++;
-            const uint32_t* pg = pair_group.data(); const uint16_t* hv0 = h_valid.data();
-            // pairs come group by group (the caller's read lists); then every (group, window) unit is filled and ordered by its own host thread
-            // from the group's pair range.  Otherwise (never seen) one pass over all pairs.
-            bool by_group = true; std::vector<uint64_t> gbeg(G + 1, 0);
-            for (uint64_t p = 1; p < NP; ++p) if (pg[p] < pg[p - 1]) { by_group = false; break; }
-            if (by_group) { uint64_t acc = 0; for (uint32_t g = 0; g < G; ++g) { gbeg[g] = acc; acc += npg[g]; } gbeg[G] = acc; }
-            // racon adds the layers of a window in the order of their first window position (src/window.cpp: rank sorted by positions_.first);
-            // ties keep the read order (stable): counting sort on the window position
-            auto order_unit = [&](std::vector<uint32_t>& v, std::vector<uint32_t>& tmpv, std::vector<uint32_t>& cnt) {
-                if (v.size() < 2) return;
-                uint32_t kmax = 0; bool sorted = true;
-                for (size_t x = 0; x < v.size(); ++x) { const uint32_t kx = hv0[v[x]]; kmax = std::max(kmax, kx); if (x && hv0[v[x - 1]] > kx) sorted = false; }
-                if (sorted) return;
-                cnt.assign((size_t)kmax + 2, 0);
-                for (uint32_t id : v) cnt[hv0[id] + 1]++;
-                for (size_t k2 = 1; k2 < cnt.size(); ++k2) cnt[k2] += cnt[k2 - 1];
-                tmpv.resize(v.size());
-                for (uint32_t id : v) tmpv[cnt[hv0[id]]++] = id;
-                std::copy(tmpv.begin(), tmpv.end(), v.begin());
-            };
-            if (by_group && NP >= 65536) {
-                std::vector<uint64_t> used_g(G, 0);
-                const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-                const size_t ntask = units.size() + G;                          // one task per unit + one per group (reads used)
-                std::atomic<size_t> next_task{0};
-                auto worker = [&]() {
-                    std::vector<uint32_t> tmpv, cnt;
-                    for (;;) {
-                        const size_t t = next_task.fetch_add(1); if (t >= ntask) break;
-                        if (t < units.size()) {
-                            const uint32_t g = unit_gw[t].first, wdx = (uint32_t)unit_gw[t].second;
-                            auto& v = units[t].seqs; v.resize(npg[g]); uint32_t* c = v.data();
-                            for (uint64_t p = gbeg[g]; p < gbeg[g + 1]; ++p) { *c = (uint32_t)(p * (uint64_t)nwinmax + wdx); c += hv0[p * (uint64_t)nwinmax + wdx] != 0; }
-                            v.resize((size_t)(c - v.data()));
-                            order_unit(v, tmpv, cnt);
-                        } else {
-                            const uint32_t g = (uint32_t)(t - units.size()); const uint32_t nwg = unw[g]; uint64_t u = 0;
-                            for (uint64_t p = gbeg[g]; p < gbeg[g + 1]; ++p) { const uint16_t* hv = hv0 + p * (uint64_t)nwinmax; uint32_t any = 0; for (uint32_t wdx = 0; wdx < nwg; ++wdx) any |= hv[wdx] != 0; u += any; }
-                            used_g[g] = u;
-                        }
-                    }
-                };
-                std::vector<std::thread> th; for (unsigned x = 1; x < hw; ++x) th.emplace_back(worker);
-                worker(); for (auto& t : th) t.join();
-                for (uint32_t g = 0; g < G; ++g) used[g] += (uint32_t)used_g[g];
-            } else {
-                // lists sized for the worst case, filled through raw cursors, trimmed afterwards
-                std::vector<uint32_t*> cur(units.size(), nullptr);
-                for (uint32_t g = 0; g < G; ++g) for (uint32_t wdx = 0; wdx < unw[g]; ++wdx) { auto& v = units[ubase[g] + wdx].seqs; v.resize(npg[g]); cur[ubase[g] + wdx] = v.data(); }
-                for (uint64_t p = 0; p < NP; ++p) {
-                    const uint32_t g = pg[p]; const uint16_t* hv = hv0 + p * (uint64_t)nwinmax; const uint32_t nwg = unw[g], ub = ubase[g]; uint32_t any = 0;
-                    for (uint32_t wdx = 0; wdx < nwg; ++wdx) { const uint32_t v = hv[wdx] != 0; *cur[ub + wdx] = (uint32_t)(p * (uint64_t)nwinmax + wdx); cur[ub + wdx] += v; any |= v; }
-                    used[g] += any;
-                }
-                for (size_t u = 0; u < units.size(); ++u) if (cur[u]) units[u].seqs.resize((size_t)(cur[u] - units[u].seqs.data()));
-                std::vector<uint32_t> tmpv, cnt;
-                for (size_t u = 0; u < units.size(); ++u) order_unit(units[u].seqs, tmpv, cnt);
-            }
-        }
-        std::vector<size_t> nlayers(units.size());
-        for (size_t u = 0; u < units.size(); ++u) {
-            nlayers[u] = units[u].seqs.size();
-            if (units[u].seqs.size() < 2) { units[u].seqs.clear(); units[u].done = true; continue; }          // racon: < 3 sequences incl. backbone -> keep backbone
-            const uint32_t g = unit_gw[u].first; const int ws = unit_gw[u].second * W; const int wlen = polish_wlen((int)B[g].size(), W, unit_gw[u].second);
-            PSeq S; S.s = BB.seq + boff[g] + ws; S.q = nullptr; S.len = wlen; S.uw = 0; S.cw = 0; S.mode = NGSID_POA_GLOBAL; S.a0 = 0; S.a1 = -1;
-            units[u].bb = (int)bbs.size(); bbs.push_back(S); bb_len.push_back(wlen);
-        }
-        DevBuf<PSeq> d_bbs; NGSID_TRY(dev_put(ctx, d_bbs, bbs.data(), bbs.size()));
-        bool any_tgs = prm->trim == 2; for (uint32_t g = 0; g < G; ++g) any_tgs = any_tgs || (tgs[g] && prm->trim);
-        HierParams hp{prm->match, prm->mismatch, prm->gap, prm->band > 0 ? prm->band : (RD.maxlen <= NGSID_POA_BAND64_MAXLEN ? 64 : 128), prm->node_cap, prm->tile_depth, NGSID_POA_GLOBAL, any_tgs, (prm->trim >= 2 ? 1 : 0) | (prm->trim == 3 ? 4 : 0)};      // trim_tiles: 1 = trim tile consensuses, 4 = except the tile that ends a unit (trim 3)
-        hp.single_below = prm->single_below > 0 ? prm->single_below : 0;
-        hp.sub = (prm->aln_mode & NGSID_ALN_SUBGRAPH) != 0;
-        if (hp.single_below > 0) for (size_t u = 0; u < units.size(); ++u) {       // windows with few layers: ONE graph; the longest sequence that can enter it = the longest READ behind its layers, or the window
-            Unit& U = units[u]; if (U.done || U.seqs.size() >= (size_t)hp.single_below) continue;
-            uint32_t mx = (uint32_t)std::max(1, bb_len[U.bb]);
-            for (uint32_t id : U.seqs) { const uint32_t r = pair_read[id / (uint32_t)nwinmax]; mx = std::max<uint32_t>(mx, (uint32_t)(RD.h_off[r + 1] - RD.h_off[r])); }
-            U.single_maxlen = mx;
-        }
-        ht.mark("unit lists");
-        rc = run_hierarchy(ctx, (const PSeq*)d_lay_raw.p, (uint32_t)std::max(max_layer, 1), d_bbs.p, bb_len, units, hp); if (rc) return rc;
-        ht.mark("hierarchy");
-        // ---- new backbones
-        std::vector<std::string> NB(G);
-        for (size_t u = 0; u < units.size(); ++u) {
-            const uint32_t g = unit_gw[u].first; const int ws = unit_gw[u].second * W; const int wlen = polish_wlen((int)B[g].size(), W, unit_gw[u].second);
-            std::string c = units[u].has_result ? units[u].result : std::string();
-            if (!c.empty() && prm->trim && (tgs[g] || prm->trim == 2) && units[u].cov.size() == c.size()) {      // trim 3: racon's window rule (TGS only) with trimmed tiles
-                const uint32_t avg = (uint32_t)(nlayers[u] / 2); int b = 0, e = (int)c.size() - 1;
-                for (; b < (int)c.size(); ++b) if (units[u].cov[b] >= avg) break;
-                for (; e >= 0; --e) if (units[u].cov[e] >= avg) break;
-                if (b < e) c = c.substr(b, e - b + 1);
-            }
-            if (c.empty()) c = B[g].substr(ws, wlen);
-            NB[g] += c;
-        }
-        for (uint32_t g = 0; g < G; ++g) { if (stable[g]) NB[g] = B[g]; else if (prm->stop_when_stable && NB[g] == B[g]) stable[g] = 1; }
-        B.swap(NB);
-        if (trace) for (uint32_t g = 0; g < G; ++g) { trace->seq.push_back(B[g]); trace->used.push_back(used[g]); }
-    }
-    if (trace && trace->aln) for (size_t it = trace->seq.size() / std::max<uint32_t>(G, 1); it < (size_t)prm->iters; ++it) { if (it == 0) { for (uint64_t x = 0; x < grp_off[n_groups] * 6; ++x) trace->aln[x] = -1; } else memcpy(trace->aln + it * grp_off[n_groups] * 6, trace->aln + (it - 1) * grp_off[n_groups] * 6, sizeof(int32_t) * grp_off[n_groups] * 6); }
-    if (trace) while (trace->seq.size() < (size_t)prm->iters * G) { const size_t x = trace->seq.size() - G; trace->seq.push_back(trace->seq[x]); trace->used.push_back(trace->used[x]); }      // every group stable: the remaining iterations return the same strings
-    uint64_t total = 0; bool ovf = false; out_off[0] = 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        if (trace) { /* ngsid_polish_trace: the final sequences are the trace's last iteration, no buffer was handed in */ }
-        else if (total + B[g].size() <= out_cap && out) memcpy(out + total, B[g].data(), B[g].size()); else if (B[g].size()) ovf = true;
-        total += B[g].size(); out_off[g + 1] = total; if (n_used) n_used[g] = used[g];
-    }
-    if (needed) *needed = total;
-    if (ovf) NGSID_FAIL(ctx, NGSID_ERR_CAPACITY, "output buffer too small: need %llu bytes", (unsigned long long)total);
-    return NGSID_OK;
+    return rc;
 }

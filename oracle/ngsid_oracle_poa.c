@@ -490,7 +490,7 @@ static uint8_t comp_base(uint8_t c) { switch (c) { case 'A': return 'T'; case 'C
 typedef struct { pseq* v; int n, cap; } layervec;
 static void lv_push(layervec* L, pseq s) { if (L->n == L->cap) { L->cap = L->cap ? L->cap * 2 : 16; L->v = realloc(L->v, sizeof(pseq) * (size_t)L->cap); } L->v[L->n++] = s; }
 
-/* polishing windows: W bases each, a last window shorter than W/10 is merged into the one before it (see csrc/poa_host.hip polish_nwin) */
+/* polishing windows: W bases each, a last window shorter than W/10 is merged into the one before it (see csrc/polish_host.hip polish_nwin) */
 static int polish_nwin(int Bl, int W) { const int raw = Bl <= W ? 1 : (Bl + W - 1) / W; const int tail = Bl - (raw - 1) * W; return (raw >= 2 && tail < W / 10) ? raw - 1 : raw; }
 static int polish_wlen(int Bl, int W, int w) { return w == polish_nwin(Bl, W) - 1 ? Bl - w * W : W; }
 

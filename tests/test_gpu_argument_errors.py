@@ -72,6 +72,25 @@ def test_grouped_call_argument_errors(gpu_api, oracle, data, name):
         assert _eq(call(GRP, ORDER, cen), base), (name, what, "valid call after the error")
 
 
+def test_polish_unit_threads_out_of_range(gpu_api, data):
+    """polish_unit_threads takes 0 (by the number of pairs) and 1 .. 16: 17 and -1 are refused through the C-ABI (the wrapper's set_option would also remember them
+    for the lane contexts), the setting stays what it was and the context polishes as before"""
+    import ctypes as C
+    tpl, reads, rs, cen = data
+    call = _grouped_calls(gpu_api, data)["polish_trace"]
+    base = call(GRP, ORDER, cen)
+    opt = lambda v: gpu_api.lib.ngsid_ctx_option(gpu_api.ctx, b"polish_unit_threads", C.c_int64(v))
+    try:
+        assert opt(16) == 0
+        for bad in (17, -1):
+            assert opt(bad) == -2, bad
+            with pytest.raises(NgsidError, match="polish_unit_threads"): gpu_api._err(-2)      # (the message the library left)
+            assert _eq(call(GRP, ORDER, cen), base), (bad, "valid call after the error")
+    finally:
+        assert opt(0) == 0
+    assert _eq(call(GRP, ORDER, cen), base)
+
+
 def test_poa_merge_length_bound(gpu_api, data):
     """Reads whose per-chunk summaries of the merge would run into the sequence bytes in LDS (k_poa.hip MergeLds<64>::max_len = 25 920 bases: 12 bytes per 64 positions
     below LLT<64>::C1 = 4 864) are refused with NGSID_ERR_TOO_LONG before a tile is launched.  match = 2 keeps match x length below 65 536, the explicit band 64 is

@@ -5,9 +5,11 @@ tests/test_polish_reference_cpu.py asserts that this is at least 70 % and at lea
   ii   tile_depth = 4 with single_below = 64: the route small windows take by default;
   iii  all groups of a family that share their parameters in ONE call, reads stored in shuffled order and reached through read_order, groups listed in shuffled
        order (short and long backbones alternate: the launch is sized by the longest, every group indexed by its own length);
-  iv   route iii on contexts with poa_host_levels 0 / 1 and poa_out_slots 1 (include/ngsid.h: results never depend on them);
+  iv   route iii on contexts with poa_host_levels 0 / 1, poa_out_slots 1 and polish_unit_threads 1 / 4 (include/ngsid.h: results never depend on them);
   v    family f (the window count changes between iterations) with stop_when_stable 0 and 1: identical outputs;
-  vi   family b under NGSID_ALN_SUBGRAPH against the reference's sub-graph layers, one group per call and all in one call.
+  vi   family b under NGSID_ALN_SUBGRAPH against the reference's sub-graph layers, one group per call and all in one call;
+  vii  on one polish_unit_threads 4 context (the unit-list builder with as many threads as a large call gives it): route v with all groups in one call (the pairs
+       of the stable groups dropped, the pair ranges recomputed), and family d one group per call (groups without a pair, fewer tasks than threads).
 Expected values are computed once per family (polish_cases.expected).  Every library call runs under a time limit of its own: a call that hangs ends the process
 (faulthandler) instead of the next one being started on the same device.
 """
@@ -19,7 +21,8 @@ import polish_cases as pc
 
 pytestmark = pytest.mark.gpu
 STEP_LIMIT = 120      # seconds per library call (they take milliseconds)
-OPTIONS = {"host_levels0": {"poa_host_levels": 0}, "host_levels1": {"poa_host_levels": 1}, "out_slots1": {"poa_out_slots": 1}}
+OPTIONS = {"host_levels0": {"poa_host_levels": 0}, "host_levels1": {"poa_host_levels": 1}, "out_slots1": {"poa_out_slots": 1},
+           "unit_threads1": {"polish_unit_threads": 1}, "unit_threads4": {"polish_unit_threads": 4}}
 MIN_COMPARED = 8
 
 
@@ -123,6 +126,32 @@ def test_stop_when_stable_changes_nothing(gpu_api):
             d = pc.differences(e, *one)
             assert not d, "%s [stop_when_stable %d]: %s" % (g.name, sws, "\n".join(d))
     assert n >= 2 * MIN_COMPARED
+
+
+@pytest.fixture(scope="module")
+def threads4_api():
+    from ngspeciesid_amd import runtime
+    with limit(): api = runtime.new_api(options={"polish_unit_threads": 4})
+    yield api
+    with limit(): api.close()
+
+
+def test_unit_threads_stop_when_stable_equals_reference(threads4_api):
+    """route vii: family f, stop_when_stable 0 and 1, one call for all groups"""
+    gs = pc.family("f_iterations"); ex = pc.expected("f_iterations")
+    n = 0
+    for sws in (0, 1):
+        for g, e, w in zip(gs, ex, _call(threads4_api, gs, _prm(gs[0], stop_when_stable=sws), "polish_trace_aln", shuffle_seed=7)):
+            if not e[3]: continue
+            n += 1
+            d = pc.differences(e, *w)
+            assert not d, "%s [unit threads 4, stop_when_stable %d]: %s" % (g.name, sws, "\n".join(d))
+    assert n >= 2 * MIN_COMPARED
+
+
+def test_unit_threads_one_group_per_call_equals_reference(threads4_api):
+    """route vii: family d, one group per call"""
+    _per_group(threads4_api, "d_strands", "unit threads 4", tile_depth=0, band=0)
 
 
 def test_subgraph_layers_equal_reference(gpu_api):
