@@ -79,6 +79,8 @@ MAX_CONSENSUS_LEN = 16384                                                       
 NEAR_MAX_DIST, NEAR_BOTH_STRANDS = 31, 1                                            # include/ngsid_near.h NGSID_NEAR_MAX_DIST, NGSID_NEAR_BOTH_STRANDS
 NEAR_WIDE_MAX_DIST = 255                                                            # include/ngsid_near.h NGSID_NEAR_WIDE_MAX_DIST
 UMI_MAX_LEN, UMI_MAX_DIST = 64, 8                                                   # include/ngsid_umi.h NGSID_UMI_MAX_LEN, NGSID_UMI_MAX_DIST
+RECRUIT_MAX_LEN, RECRUIT_NFIELD, RECRUIT_BOTH_STRANDS = 2048, 6, 1                  # include/ngsid_recruit.h NGSID_RECRUIT_MAX_LEN, _NFIELD, _BOTH_STRANDS
+RECRUIT_FIELDS = ("cons", "ed", "strand", "end", "cons2", "ed2")                    # the six integers per read of Api.recruit
 
 
 def chimera_profile_offsets(query_lens, pair_off):
@@ -903,6 +905,23 @@ class Api:
                _p(bin_of), _p(cent), C.byref(nb))
         if rc: raise NgsidError(rc, "umi_centroids: an index out of range, a pair (x, x), or an order that is no permutation")
         return bin_of[:n], cent[:int(nb.value)].copy()
+
+    # ---- include/ngsid_recruit.h
+    def recruit(self, rs: ReadSet, read_off, cons, cons_off, max_ed, both_strands=True):
+        """ngsid_recruit: every read located inside every consensus of its group (reads read_off[g]:read_off[g + 1] against consensuses cons_off[g]:cons_off[g + 1]),
+        on both strands with both_strands, and the two nearest consensuses per read -> hits [n, 6] int32 in RECRUIT_FIELDS order: -1 where there is nothing, strand 0.
+        max_ed: one bound per consensus.  cons: a list of strings or a host ReadSet.  There is no CPU implementation: a library without the entry point is an error."""
+        self._need("ngsid_recruit.h", "recruit")
+        cs = _as_reads(cons)
+        if cs.mem != MEM_HOST: raise ValueError("recruit takes the consensuses as a host read set")
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64); co = np.ascontiguousarray(cons_off, dtype=np.uint64)
+        me = np.ascontiguousarray(max_ed, dtype=np.int32)
+        if len(ro) != len(co) or len(ro) < 1: raise ValueError("recruit: read_off and cons_off hold one entry per group + 1")
+        if len(me) != cs.n: raise ValueError("recruit: max_ed holds one entry per consensus")
+        hits = np.full((max(rs.n, 1), RECRUIT_NFIELD), -1, dtype=np.int32); hits[:, 2] = 0
+        rc = self._call("recruit", C.byref(rs.c), _p(ro), C.byref(cs.c), _p(co), C.c_uint64(len(ro) - 1), _p0(me), C.c_uint32(RECRUIT_BOTH_STRANDS if both_strands else 0), _p(hits))
+        if rc: self._err(rc)
+        return hits[:rs.n]
 
 
 class RefDb:

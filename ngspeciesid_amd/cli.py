@@ -48,7 +48,7 @@ DEMUX_NEEDS_T1 = ("--demux_sheet requires --t 1: the demultiplexed samples are h
 
 def build_parser():
     p = argparse.ArgumentParser(description="Reference-free clustering and consensus forming of targeted ONT or PacBio reads (MI355X hot path)",
-                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample; `variants --fasta A B ... --outfolder O` (first argument `variants`) writes the files of --variants with every FASTA taken as one sample; `umi --fastq X --outfolder O --umi_fwd PRE,POST --umi_rev PRE,POST` (first argument `umi`; `umi --help`) bins the reads of a UMI protocol by molecule and writes one polished consensus per bin",
+                                epilog="extension: `classify --fasta X --reference_db DB --outfile T` (first argument `classify`; `classify --help`) classifies the sequences of any FASTA against a reference library: the table of --reference_db; `chimeras --fasta X --outfile T` (first argument `chimeras`) writes the table of --chimeras for the sequences of any FASTA, taken as one sample; `variants --fasta A B ... --outfolder O` (first argument `variants`) writes the files of --variants with every FASTA taken as one sample; `recruit --fastq X --fasta CONS.fasta --outfolder O` (first argument `recruit`) writes the files of --recruit for any reads and any FASTA, taken as one sample; `umi --fastq X --outfolder O --umi_fwd PRE,POST --umi_rev PRE,POST` (first argument `umi`; `umi --help`) bins the reads of a UMI protocol by molecule and writes one polished consensus per bin",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--version', action='version', version='%(prog)s 0.3.1-mi355x')
     p.add_argument('--debug', action='store_true')
@@ -109,6 +109,9 @@ def build_parser():
     p.add_argument('--hp_min_share', type=float, default=_hp.DEFAULTS["min_share"], help='extension: the called length holds at least this share of those reads')
     p.add_argument('--hp_min_margin', type=float, default=_hp.DEFAULTS["min_margin"], help="extension: and leads the consensus's own length by at least this share of them")
     p.add_argument('--hp_min_strand_depth', type=int, default=_hp.DEFAULTS["min_strand_depth"], help="extension: a strand with at least this many reads of its own that does not prefer the called length to the consensus's vetoes the call")
+    from . import recruit as _recruit
+    p.add_argument('--recruit', action='store_true', help='extension: recruit every read of the sample to its nearest final consensus. Every read of sorted.fastq is located on the GPU inside every final consensus (the consensus end to end, the read\'s ends free, both strands, unit-cost edit distance) and counts for the nearest one within the identity bound; writes <outfolder>/recount.tsv (consensus reads_clustered reads_recruited from_own_clusters from_other_centres from_unclustered, then the ambiguous and unassigned totals) and read_assignments.tsv (read consensus strand ed identity status; with --fastq_dir / --demux_sheet both per sample folder and <outfolder>/recount_all.tsv). No other output changes. Needs --consensus')
+    _recruit.add_flags(p)
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -170,6 +173,25 @@ def _umi_subparser(cf):
     return cf
 
 
+def _recruit_subparser(cf):
+    """the `recruit` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import recruit as _recruit
+    cf.add_argument('--fastq', type=str, required=True, help='the reads')
+    cf.add_argument('--fasta', type=str, required=True, help='the sequences the reads are recruited to, taken as one sample (at most 2048 letters each); read counts are taken from names of this tool\'s consensuses (..._total_supporting_reads_N), else 0')
+    cf.add_argument('--outfolder', type=str, required=True, help='where recount.tsv and read_assignments.tsv go')
+    cf.add_argument('--q', dest="quality_threshold", type=float, default=7.0, help='the read filter of the run the reads come from: the default of --recruit_min_identity')
+    _recruit.add_flags(cf)
+    cf.set_defaults(which='recruit')
+    return cf
+
+
+def _check_recruit(args):
+    from . import recruit as _recruit
+    err = _recruit.check_args(args)
+    if err:
+        logging.error(err); sys.exit(1)
+
+
 def _check_variants(args):
     from . import variants as _variants
     err = _variants.check_args(args)
@@ -201,6 +223,8 @@ def cli(argv=None):
         args = _chimeras_subparser(argparse.ArgumentParser(prog='chimeras', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'variants':
         args = _variants_subparser(argparse.ArgumentParser(prog='variants', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'recruit':
+        args = _recruit_subparser(argparse.ArgumentParser(prog='recruit', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'umi':
         args = _umi_subparser(argparse.ArgumentParser(prog='umi', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
@@ -232,6 +256,15 @@ def cli(argv=None):
         from . import variants as _variants
         tab = _variants.variants_fasta(args)
         logging.info("Wrote %d variants of %d sequences to %s." % (len(tab["variants"]), len(tab["members"]), args.outfolder))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'recruit':
+        _check_recruit(args)
+        for f in (args.fastq, args.fasta):
+            if not os.path.isfile(f):
+                logging.error("%s is not a file." % f); sys.exit(1)
+        from . import recruit as _recruit
+        res = _recruit.recruit_fastq(args)
+        logging.info("Recruited %d of %d reads to %d sequences; wrote %s." % (int((res["status"] == _recruit.ASSIGNED).sum()), len(res["status"]), len(res["counts"]["centres"]), args.outfolder))
         sys.exit(0)
     if getattr(args, "which", "main") == 'umi':
         from . import umi as _umi
@@ -296,6 +329,10 @@ def cli(argv=None):
         if not (getattr(args, "fastq_dir", None) or getattr(args, "demux_sheet", None)):
             logging.error("--variants joins the consensuses of several samples: it needs --fastq_dir or --demux_sheet."); sys.exit(1)
         _check_variants(args)
+    if getattr(args, "recruit", False):
+        if not args.consensus:
+            logging.error("--recruit recruits reads to consensus sequences: it needs --consensus."); sys.exit(1)
+        _check_recruit(args)
     if getattr(args, "hp_polish", False):
         if not args.consensus:
             logging.error("--hp_polish corrects consensus sequences: it needs --consensus."); sys.exit(1)

@@ -565,7 +565,7 @@ extern "C" int32_t ngsid_reads_release(ngsid_ctx* ctx, ngsid_reads_t* dev)
 extern "C" int32_t ngsid_ctx_option(ngsid_ctx* ctx, const char* name, int64_t value)
 {
     if (!ctx || !name) return NGSID_ERR_ARG;
-    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs", "umi_chunk_seqs", "near_max_tiles", "umi_max_tiles", "polish_unit_threads"};
+    static const char* known[] = {"minimizers_chunk_bases", "poa_level_budget_mb", "cluster_block", "cluster_block_cap", "cluster_trunc", "cluster_seg_order", "ed_band", "ed_win_all", "align32", "align_noclass", "poa_tiles_per_cu", "minimizers_lean", "minimizers_mode", "poa_host_levels", "align_paired", "align_skew", "poa_out_slots", "ed_lds_pad_kb", "ed_win6", "support_budget_mb", "demux_chunk_reads", "demux_scan_chunk_reads", "classify_chunk_queries", "chimera_chunk_queries", "near_chunk_seqs", "near_chunk_pairs", "umi_chunk_seqs", "near_max_tiles", "umi_max_tiles", "polish_unit_threads", "recruit_chunk_reads", "recruit_cutoff"};
     if (!strcmp(name, "polish_unit_threads") && (value < 0 || value > 16)) NGSID_FAIL(ctx, NGSID_ERR_ARG, "polish_unit_threads must be 0 (by the number of pairs) or 1 .. 16");
     for (const char* k : known) if (!strcmp(k, name)) { ctx->options[name] = (long long)value; return NGSID_OK; }
     if (!strcmp(name, "touch")) {        // one trivial operation on the context's stream (+ wait): a caller that spends milliseconds on the host between two calls keeps the device out of its idle state

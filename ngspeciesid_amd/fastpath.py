@@ -773,6 +773,21 @@ def _chimera_step(args, api, groups, T):
     T["chimeras"] = time() - t0
 
 
+def _recruit_step(args, api, sr, work, merged, goff, list_order, T):
+    """--recruit: every read of the sample's sorted reads (the oriented ones under --strand_aware) against the final sequences of its centres, one library call
+    (recruit.run) -> recount.tsv, read_assignments.tsv in the sample's folder.  A read's origin is the centre whose merged clusters hold it (whole clusters, whatever
+    --max_seqs_for_consensus kept of them)."""
+    from . import recruit
+    t0 = time()
+    n = sr.n
+    lists = [np.concatenate([np.asarray(list_order[int(goff[c]):int(goff[c + 1])], dtype=np.int64) for c in cs]) for _, _, _, cs in merged]
+    ids = [m[1] for m in merged]; seqs = [m[2] for m in merged]
+    res = recruit.run(api, work, [0, n], [seqs], [recruit.origin_of(n, lists)], [[m[0] for m in merged]], **recruit.policy_from_args(args))[0]
+    recruit.write_sample(args.outfolder, [sr.names.get(i) + sr.suffix(i) for i in range(n)], ids, seqs, res)
+    args._recruit = (ids, res["counts"])
+    T["recruit"] = time() - t0
+
+
 def _variant_step(args, api, groups, T):
     """--variants: the final consensuses of every (sample, folder, centres) group of a multi-sample run compared with each other in one library call and joined into
     study-wide variants (variants.run) -> <outfolder>/variants.fasta, variant_table.tsv, variant_members.tsv"""
@@ -840,6 +855,11 @@ def _main_samples(args, api):
     if getattr(args, "hp_polish", False) and args.consensus:
         from . import hp
         hp.write_table(os.path.join(args.outfolder, "hp_polish_all.tsv"), [(os.path.basename(a.outfolder),) + r for a, _ in subs for r in getattr(a, "_hp_rows", [])], ("sample",) + hp.TABLE_HEADER)
+    if getattr(args, "recruit", False) and args.consensus:
+        from . import recruit
+        for x, (a, _) in enumerate(subs):
+            ids, counts = getattr(a, "_recruit", ([], dict(centres=[], ambiguous=0, unassigned=0)))
+            recruit.write_recount(os.path.join(args.outfolder, "recount_all.tsv"), ids, counts, sample=os.path.basename(a.outfolder), header=x == 0, mode="w" if x == 0 else "a")
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 
@@ -922,6 +942,8 @@ def _finish(args, api, st, clustered, t0):
         logging.debug(f"Forming draft consensus with abundance_cutoff >= {abundance_cutoff} ({args.abundance_ratio * 100}% of {len(sel)} reads)")
         merged = consensus_and_polish(args, sr, work_dev, reps, sizes, goff, list_order, abundance_cutoff, api, acc_id, T)
         logging.info(f"Finished Consensus creation: {len(merged)} created")
+        if getattr(args, "recruit", False):
+            _recruit_step(args, api, sr, work_dev, merged, goff, list_order, T)
     if work_dev is not work:
         work_dev.release()
     return dict(n_sorted=sr.n, n_clustered=len(sel), clusters=len(reps), centers=merged, timings=T, counters=counters)
