@@ -293,6 +293,14 @@ int32_t ngsid_host_thread_cap(int32_t n);
  *   span), 255.  job == NULL writes synchronously, else the call is queued on the background writers (ngsid_host_async_wait). */
 int32_t ngsid_host_write_paf(const char* path, uint64_t n, const uint64_t* idx, const uint8_t* names, const uint64_t* name_off, const uint32_t* name_len,
                              const uint8_t* sfx, const uint64_t* sfx_off, const uint64_t* off, const int32_t* aln, const char* tname, uint32_t tlen, int32_t max_threads, uint64_t* job);
+/* ngsid_host_write_sam: `header` as it stands, then one SAM record per listed read j = read idx[j] (names as in ngsid_host_write_paf).  With target[j] >= 0, strand[j] >= 0 and
+ *   aln[5 j] >= 0 (the five fields of ngsid_read_cigars, include/ngsid_cigar.h) the record is mapped: FLAG 0 / 16, RNAME = target name tnames[tname_off[t] .. tname_off[t + 1]),
+ *   POS t_begin + 1, MAPQ 255, the CIGAR text of ops[op_off[j] .. op_off[j + 1]), * 0 0, SEQ reverse-complemented and QUAL reversed on strand 1, NM:i:nm.  Otherwise it is
+ *   unmapped: FLAG 4, * 0 0 *, * 0 0, SEQ and QUAL as in the file.  QUAL is '*' when qual is NULL or no_qual[j] != 0 (no_qual may be NULL).  job as in ngsid_host_write_paf. */
+int32_t ngsid_host_write_sam(const char* path, const char* header, uint64_t n, const uint64_t* idx, const uint8_t* names, const uint64_t* name_off, const uint32_t* name_len,
+                             const uint8_t* sfx, const uint64_t* sfx_off, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, const uint8_t* no_qual,
+                             const int8_t* strand, const int32_t* target, const uint8_t* tnames, const uint64_t* tname_off,
+                             const int32_t* aln, const uint64_t* op_off, const uint32_t* ops, int32_t max_threads, uint64_t* job);
 int32_t ngsid_host_fastq_index(const uint8_t* buf, uint64_t len, uint64_t* rec, uint32_t* name_len, uint32_t* seq_len, uint64_t cap_records, uint64_t* n_records);
 int32_t ngsid_host_gather(const uint8_t* src, const uint64_t* src_off, const uint32_t* len, uint64_t n, uint8_t* dst, const uint64_t* dst_off);
 int32_t ngsid_host_normalize_bases(uint8_t* seq, uint64_t len, uint64_t* changed);

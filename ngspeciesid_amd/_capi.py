@@ -115,6 +115,11 @@ def phase_offsets(grp_off, site_off):
 HP_NBUCKET, HP_OTHER = 17, 16                                                      # include/ngsid_hp.h: buckets 0 - 14 exact run lengths, 15 = 15 or more, 16 = spanned, no length
 
 
+CIGAR_NFIELD, CIGAR_MERGE_M = 5, 1                                                 # include/ngsid_cigar.h NGSID_CIGAR_NFIELD, NGSID_CIGAR_MERGE_M
+CIGAR_FIELDS = ("t_begin", "t_end", "q_begin", "q_end", "nm")                      # the five integers per listed read of Api.read_cigars
+CIGAR_OPS = "MIDNSHP=X"                                                            # BAM's op codes: an entry of ops is length << 4 | code
+
+
 def cluster_params(k=13, w=20, min_shared=5, min_fraction=0.8, mapped_threshold=0.7, aligned_threshold=0.4,
                    min_prob_no_hits=0.1, symmetric=False, p_shared=None):
     p = ClusterParams()
@@ -709,6 +714,21 @@ class Api:
         rc = self._call("hp_runs", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(run_off), _p0(run_start), _p(hist), _p(strand))
         if rc: self._err(rc)
         return hist[:nr], strand[:int(grp_off[-1])]
+
+    # ---- include/ngsid_cigar.h
+    def read_cigars(self, centres: ReadSet, rs: ReadSet, grp_off, read_order=None, k=13, w=20, clip=False, merge_m=False, cap=None):
+        """ngsid_read_cigars: the alignment of every listed read to the centre of its group -> (aln [n_listed, 5] int32 in CIGAR_FIELDS order, op_off [n_listed + 1] uint64,
+        ops uint32 = length << 4 | BAM op, strand [n_listed] int8).  ops[op_off[x]:op_off[x + 1]] are the ops of listed read x: soft clip, the runs of the counted columns
+        ('=' 7, 'X' 8, 'I' 1, 'D' 2; merge_m: '=' and 'X' as 'M' 0), soft clip, in the oriented read's coordinates; a read without a strand or a counted column has none and
+        -1 in its five fields.  Grouping, strands and counted columns as in consensus_support().  cap None: the count call, then the fill call (the store pass runs twice);
+        a cap: the fill call alone (NgsidError NGSID_ERR_CAPACITY with .needed when there are more ops).  There is no CPU implementation: a library without the entry point
+        is an error."""
+        grp_off, ro, ng, strand, prm = self._support_head("read_cigars", "ngsid_cigar.h", ("read_cigars",), centres, grp_off, read_order, k, w, clip)
+        nl = int(grp_off[-1])
+        head = (C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), C.c_uint32(CIGAR_MERGE_M if merge_m else 0), _p(strand))
+        (aln, op_off, ops), n = self._found_list("read_cigars", head, 3, lambda c: (np.full((max(nl, 1), CIGAR_NFIELD), -1, dtype=np.int32), np.zeros(nl + 1, dtype=np.uint64),
+                                                                                   np.zeros(max(c, 1), dtype=np.uint32)), cap)
+        return aln[:nl], op_off, ops[:n], strand[:nl]
 
     # ---- include/ngsid_phase.h
     def phase_genotypes(self, centres: ReadSet, rs: ReadSet, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):

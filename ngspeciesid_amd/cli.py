@@ -112,6 +112,8 @@ def build_parser():
     from . import recruit as _recruit
     p.add_argument('--recruit', action='store_true', help='extension: recruit every read of the sample to its nearest final consensus. Every read of sorted.fastq is located on the GPU inside every final consensus (the consensus end to end, the read\'s ends free, both strands, unit-cost edit distance) and counts for the nearest one within the identity bound; writes <outfolder>/recount.tsv (consensus reads_clustered reads_recruited from_own_clusters from_other_centres from_unclustered, then the ambiguous and unassigned totals) and read_assignments.tsv (read consensus strand ed identity status; with --fastq_dir / --demux_sheet both per sample folder and <outfolder>/recount_all.tsv). No other output changes. Needs --consensus')
     _recruit.add_flags(p)
+    from . import sam as _sam
+    _sam.add_flags(p)
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -185,6 +187,19 @@ def _recruit_subparser(cf):
     return cf
 
 
+def _sam_subparser(cf):
+    """the `sam` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import recruit as _recruit
+    cf.add_argument('--fastq', type=str, required=True, help='the reads')
+    cf.add_argument('--fasta', type=str, required=True, help='the sequences the reads are recruited and aligned to (at most 2048 letters each): every one is a target of the file')
+    cf.add_argument('--outfile', type=str, required=True, help='the SAM file: assigned reads mapped to their sequence (CIGAR with = and X, NM tag), all other reads unmapped')
+    cf.add_argument('--q', dest="quality_threshold", type=float, default=7.0, help='the read filter of the run the reads come from: the default of --recruit_min_identity')
+    cf.add_argument('--sam_merge_m', action='store_true', help='write M instead of = and X')
+    _recruit.add_flags(cf)
+    cf.set_defaults(which='sam')
+    return cf
+
+
 def _check_recruit(args):
     from . import recruit as _recruit
     err = _recruit.check_args(args)
@@ -225,6 +240,8 @@ def cli(argv=None):
         args = _variants_subparser(argparse.ArgumentParser(prog='variants', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'recruit':
         args = _recruit_subparser(argparse.ArgumentParser(prog='recruit', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'sam':
+        args = _sam_subparser(argparse.ArgumentParser(prog='sam', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'umi':
         args = _umi_subparser(argparse.ArgumentParser(prog='umi', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
@@ -265,6 +282,15 @@ def cli(argv=None):
         from . import recruit as _recruit
         res = _recruit.recruit_fastq(args)
         logging.info("Recruited %d of %d reads to %d sequences; wrote %s." % (int((res["status"] == _recruit.ASSIGNED).sum()), len(res["status"]), len(res["counts"]["centres"]), args.outfolder))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'sam':
+        _check_recruit(args)
+        for f in (args.fastq, args.fasta):
+            if not os.path.isfile(f):
+                logging.error("%s is not a file." % f); sys.exit(1)
+        from . import sam as _sam
+        res = _sam.sam_fastq(args)
+        logging.info("Wrote %d records (%d mapped) to %s." % (res["records"], res["mapped"], args.outfile))
         sys.exit(0)
     if getattr(args, "which", "main") == 'umi':
         from . import umi as _umi
@@ -333,6 +359,11 @@ def cli(argv=None):
         if not args.consensus:
             logging.error("--recruit recruits reads to consensus sequences: it needs --consensus."); sys.exit(1)
         _check_recruit(args)
+    if getattr(args, "write_sam", False) or getattr(args, "sam_merge_m", False):
+        from . import sam as _sam
+        err = _sam.check_args(args) or (None if args.consensus else "--write_sam aligns reads to consensus sequences: it needs --consensus.")
+        if err:
+            logging.error(err); sys.exit(1)
     if getattr(args, "hp_polish", False):
         if not args.consensus:
             logging.error("--hp_polish corrects consensus sequences: it needs --consensus."); sys.exit(1)

@@ -397,6 +397,85 @@ extern "C" int32_t ngsid_host_write_paf(const char* path, uint64_t n, const uint
     } catch (...) { return NGSID_ERR_ARG; }
 }
 
+// reads_to_consensus.sam: the header text as the caller built it (policy: ngspeciesid_amd/sam.py), then one record per listed read j (read idx[j]).  A record with a target
+// (target[j] >= 0), a strand and an alignment (aln[5 j] >= 0: the five fields of ngsid_read_cigars) is MAPPED: FLAG 0 / 16, RNAME, POS = t_begin + 1, MAPQ 255, the CIGAR text of
+// ops[op_off[j] .. op_off[j + 1]) (length << 4 | BAM op), SEQ reverse-complemented and QUAL reversed on strand 1, NM:i:nm.  Any other record is unmapped: FLAG 4, '*', 0, 0, '*',
+// SEQ / QUAL as in the file.  QUAL is '*' without qualities (qual NULL, or no_qual[j] != 0).  The name: as in ngsid_host_write_paf (per-read suffix, cut at the first blank).
+static int32_t write_sam_impl(const char* path, const char* header, uint64_t n, const uint64_t* idx, const uint8_t* names, const uint64_t* name_off, const uint32_t* name_len,
+                              const uint8_t* sfx, const uint64_t* sfx_off, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, const uint8_t* no_qual,
+                              const int8_t* strand, const int32_t* target, const uint8_t* tnames, const uint64_t* tname_off,
+                              const int32_t* aln, const uint64_t* op_off, const uint32_t* ops)
+{
+    if (!path || !header || (n && (!idx || !names || !name_off || !name_len || !seq || !off || !strand || !target || !aln || !op_off))) return NGSID_ERR_ARG;
+    if (n && op_off[n] > op_off[0] && !ops) return NGSID_ERR_ARG;
+    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666); if (fd < 0) return NGSID_ERR_ARG;
+    const size_t hl = strlen(header);
+    const int T = std::max(1, n_threads(n * 1024));
+    std::vector<std::vector<uint8_t>> part((size_t)T);
+    auto put_u = [](uint8_t* o, uint64_t v) -> uint8_t* { char b[24]; int k = 0; do { b[k++] = (char)('0' + v % 10); v /= 10; } while (v); while (k) *o++ = (uint8_t)b[--k]; return o; };
+    auto mapped = [&](uint64_t j) { return target[j] >= 0 && strand[j] >= 0 && aln[5 * j] >= 0 && tnames && tname_off; };
+    auto comp = [](uint8_t c) -> uint8_t { switch (c & 0xDF) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; } };
+    static const char OPS[] = "MIDNSHP=X???????";
+    std::atomic<int> failed{0};
+    parallel_ranges(n, T, [&](uint64_t a, uint64_t b, int t) {
+        size_t cap = 0;
+        for (uint64_t j = a; j < b; ++j) {
+            const uint64_t i = idx[j]; const bool m = mapped(j);
+            cap += (size_t)name_len[i] + (sfx_off ? (size_t)(sfx_off[i + 1] - sfx_off[i]) : 0) + 2 * (size_t)(off[i + 1] - off[i]) + 96;
+            if (m) cap += (size_t)(tname_off[target[j] + 1] - tname_off[target[j]]) + 11 * (size_t)(op_off[j + 1] - op_off[j]);
+        }
+        std::vector<uint8_t>& ov = part[(size_t)t]; ov.resize(cap); uint8_t* o = ov.data();
+        for (uint64_t j = a; j < b; ++j) {
+            const uint64_t i = idx[j]; const bool m = mapped(j), rev = m && strand[j] == 1; const int32_t* r = aln + 5 * j;
+            const uint8_t* nm = names + name_off[i]; uint32_t L = name_len[i], k = 0;
+            while (k < L && nm[k] != ' ' && !(nm[k] >= 9 && nm[k] <= 13)) ++k;
+            memcpy(o, nm, k); o += k;
+            if (k == L && sfx_off) { const size_t sl = (size_t)(sfx_off[i + 1] - sfx_off[i]); memcpy(o, sfx + sfx_off[i], sl); o += sl; }
+            *o++ = '\t';
+            if (m) {
+                o = put_u(o, rev ? 16 : 0); *o++ = '\t';
+                const size_t tl = (size_t)(tname_off[target[j] + 1] - tname_off[target[j]]); memcpy(o, tnames + tname_off[target[j]], tl); o += tl; *o++ = '\t';
+                o = put_u(o, (uint64_t)r[0] + 1); memcpy(o, "\t255\t", 5); o += 5;
+                if (op_off[j + 1] == op_off[j]) *o++ = '*';
+                for (uint64_t x = op_off[j]; x < op_off[j + 1]; ++x) { o = put_u(o, ops[x] >> 4); *o++ = (uint8_t)OPS[ops[x] & 15u]; }
+            } else { memcpy(o, "4\t*\t0\t0\t*", 9); o += 9; }
+            memcpy(o, "\t*\t0\t0\t", 7); o += 7;
+            const uint64_t l = off[i + 1] - off[i]; const uint8_t* s = seq + off[i];
+            if (!l) *o++ = '*';
+            else if (rev) for (uint64_t x = 0; x < l; ++x) *o++ = comp(s[l - 1 - x]);
+            else { memcpy(o, s, l); o += l; }
+            *o++ = '\t';
+            if (!qual || !l || (no_qual && no_qual[j])) *o++ = '*';
+            else if (rev) for (uint64_t x = 0; x < l; ++x) *o++ = qual[off[i] + l - 1 - x];
+            else { memcpy(o, qual + off[i], l); o += l; }
+            if (m) { memcpy(o, "\tNM:i:", 6); o += 6; o = put_u(o, (uint64_t)std::max(r[4], 0)); }
+            *o++ = '\n';
+        }
+        ov.resize((size_t)(o - ov.data())); });
+    { size_t done = 0; while (done < hl) { const ssize_t w = pwrite(fd, header + done, hl - done, (off_t)done); if (w <= 0) { failed.store(1); break; } done += (size_t)w; } }
+    std::vector<uint64_t> base((size_t)T + 1, hl); for (int t = 0; t < T; ++t) base[t + 1] = base[t] + part[(size_t)t].size();
+    parallel_ranges((uint64_t)T, T, [&](uint64_t a, uint64_t b, int) { for (uint64_t t = a; t < b; ++t) {
+        const std::vector<uint8_t>& o = part[(size_t)t]; uint64_t done = 0;
+        while (done < o.size()) { const ssize_t w = pwrite(fd, o.data() + done, (size_t)(o.size() - done), (off_t)(base[t] + done)); if (w <= 0) { failed.store(1); break; } done += (uint64_t)w; } } });
+    int32_t rc = failed.load() ? NGSID_ERR_ARG : NGSID_OK;
+    if (close(fd) != 0) rc = NGSID_ERR_ARG;
+    return rc;
+}
+// job == NULL: synchronous; else queued on the native background writers (every pointer must stay valid until ngsid_host_async_wait(*job) returned; the path and the header are copied)
+extern "C" int32_t ngsid_host_write_sam(const char* path, const char* header, uint64_t n, const uint64_t* idx, const uint8_t* names, const uint64_t* name_off, const uint32_t* name_len,
+                                        const uint8_t* sfx, const uint64_t* sfx_off, const uint8_t* seq, const uint8_t* qual, const uint64_t* off, const uint8_t* no_qual,
+                                        const int8_t* strand, const int32_t* target, const uint8_t* tnames, const uint64_t* tname_off,
+                                        const int32_t* aln, const uint64_t* op_off, const uint32_t* ops, int32_t max_threads, uint64_t* job)
+{
+    if (!job) return write_sam_impl(path, header, n, idx, names, name_off, name_len, sfx, sfx_off, seq, qual, off, no_qual, strand, target, tnames, tname_off, aln, op_off, ops);
+    if (!path || !header) return NGSID_ERR_ARG;
+    try {
+        std::string p(path), h(header);
+        *job = async_jobs().submit([=] { return write_sam_impl(p.c_str(), h.c_str(), n, idx, names, name_off, name_len, sfx, sfx_off, seq, qual, off, no_qual, strand, target, tnames, tname_off, aln, op_off, ops); }, max_threads);
+        return NGSID_OK;
+    } catch (...) { return NGSID_ERR_ARG; }
+}
+
 // Read-only mapping of an input file and its release (round 5).  Unmapping the 1.5 GB FASTQ of C3 takes ~75 ms (page-table teardown); done by the interpreter's own mmap object it
 // happened on the launch thread, with the interpreter lock held, in the middle of the ingest.  ngsid_host_unmap_file(..., 1) hands it to a detached native thread.
 extern "C" int32_t ngsid_host_map_file(const char* path, const uint8_t** data, uint64_t* len)

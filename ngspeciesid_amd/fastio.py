@@ -261,6 +261,31 @@ def write_paf(path, idx, names: Names, rs_off, aln, tname, tlen, suffixes=None, 
         raise OSError("cannot write %s" % path)
 
 
+def write_sam(path, header, idx, names: Names, rs: ReadSet, strand, target, tnames, aln, op_off, ops, suffixes=None, no_qual=None, jobs: NativeJobs = None, threads=0):
+    """SAM: the text `header`, then one record per listed read idx[j] - mapped to tnames[target[j]] with (aln[j], ops[op_off[j]:op_off[j + 1]]) of Api.read_cigars and
+    strand[j] where target[j] >= 0, strand[j] >= 0 and aln[j, 0] >= 0, unmapped (flag 4) otherwise.  The CIGAR text is formatted by the library (ngsid_host_write_sam).
+    QUAL is '*' for a read set without qualities and for the records no_qual marks.  suffixes = per-READ CSR (bytes, offsets) as in write_paf."""
+    lib = runtime.load_library()
+    if not hasattr(lib, "ngsid_host_write_sam"): raise RuntimeError("the bound library does not export ngsid_host_write_sam (include/ngsid.h): rebuild it from this tree")
+    idx = np.ascontiguousarray(idx, dtype=np.uint64); n = len(idx)
+    aln = np.ascontiguousarray(aln, dtype=np.int32).reshape(-1, 5); op_off = np.ascontiguousarray(op_off, dtype=np.uint64); ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    strand = np.ascontiguousarray(strand, dtype=np.int8); target = np.ascontiguousarray(target, dtype=np.int32)
+    if not (len(aln) == len(strand) == len(target) == n and len(op_off) == n + 1 and (n == 0 or int(op_off[-1]) <= len(ops))): raise ValueError("write_sam: one strand, target, aln row and op_off entry per listed read")
+    if n and int(target.max()) >= len(tnames): raise ValueError("write_sam: target out of range")
+    tb, to = _csr(tnames)
+    nq = None if no_qual is None else np.ascontiguousarray(no_qual, dtype=np.uint8)
+    if len(ops) == 0: ops = np.zeros(1, dtype=np.uint32)
+    sb, so = (None, None) if suffixes is None else suffixes
+    args = (path.encode(), header.encode(), C.c_uint64(n), _p(idx), _p(names.buf), _p(names.off), _p(names.len), _p(sb), _p(so), _p(rs.seq), _p(rs.qual), _p(rs.off), _p(nq),
+            _p(strand), _p(target), _p(tb), _p(to), _p(aln), _p(op_off), _p(ops), C.c_int32(int(threads or 0)))
+    if jobs is not None:
+        jid = C.c_uint64(0)
+        if lib.ngsid_host_write_sam(*args, C.byref(jid)) == 0:
+            jobs.jobs.append((jid.value, path, (idx, names, sb, so, rs, nq, strand, target, tb, to, aln, op_off, ops))); return
+    if lib.ngsid_host_write_sam(*args, None):
+        raise OSError("cannot write %s" % path)
+
+
 def write_tsv(path, idx, names: Names, prefixes, append=False, jobs: NativeJobs = None):
     """lines 'prefix<TAB>name' for reads idx; prefixes = (byte buffer, offsets) CSR or a list of strings, one per line."""
     idx = np.ascontiguousarray(idx, dtype=np.uint64)

@@ -626,6 +626,7 @@ def _merge_and_polish(args, sr, work, centers, groups, node_cap, api, acc_id, T,
         T["support"] = T.get("support", 0.0) + time() - t0
     if getattr(args, "split_haplotypes", False):
         _split_haplotypes(args, api, sr, work, merged, polish_lists, node_cap, clip, counts_of if getattr(args, "consensus_support", False) and merged else None, T)
+    args._sam_lists = (polish_lists, clip)                  # --write_sam (_sam_step, behind --recruit): the lists and the clipping of the LAST pass
     return merged
 
 
@@ -784,8 +785,30 @@ def _recruit_step(args, api, sr, work, merged, goff, list_order, T):
     ids = [m[1] for m in merged]; seqs = [m[2] for m in merged]
     res = recruit.run(api, work, [0, n], [seqs], [recruit.origin_of(n, lists)], [[m[0] for m in merged]], **recruit.policy_from_args(args))[0]
     recruit.write_sample(args.outfolder, [sr.names.get(i) + sr.suffix(i) for i in range(n)], ids, seqs, res)
-    args._recruit = (ids, res["counts"])
+    args._recruit = (ids, res["counts"]); args._recruit_res = res
     T["recruit"] = time() - t0
+
+
+def _sam_step(args, api, sr, work, merged, flip, T):
+    """--write_sam: every listed read aligned to the final sequence of its centre, one library call (sam.align) -> racon_cl_id_{id}/reads_to_consensus.sam, without --racon
+    consensus_reference_{id}.sam.  The reads listed are the polisher's (clip as in the polisher); behind --recruit every assigned read under its recruited centre, the
+    ambiguous ones as unmapped records in the file of their nearest centre (sam.recruited_lists).  SEQ and QUAL are the file's (the sorted reads); flip: the reads
+    --strand_aware turned before they were aligned."""
+    from . import sam
+    t0 = time()
+    racon = getattr(args, "racon", False) and args.racon_iter >= 0
+    lists, clip = args._sam_lists
+    near = [None] * len(merged)
+    if getattr(args, "recruit", False) and getattr(args, "_recruit_res", None) is not None:
+        lists, near, _ = sam.recruited_lists(args._recruit_res["hits"], args._recruit_res["status"], len(merged))
+        if getattr(args, "_overlong", False): lists = [l[sr.lens[l] <= MAX_CONSENSUS_LEN] for l in lists]
+    seqs = [m[2] for m in merged]
+    parts = sam.align(api, work, seqs, [np.asarray(l, dtype=np.uint32) for l in lists], k=args.k, w=args.w, clip=clip, merge_m=getattr(args, "sam_merge_m", False))
+    for x, (nr, c_id, center, cs) in enumerate(merged):
+        path = os.path.join(args.outfolder, "racon_cl_id_{0}".format(c_id), "reads_to_consensus.sam") if racon else os.path.join(args.outfolder, "consensus_reference_{0}.sam".format(c_id))
+        name = "consensus_cl_id_{0}_total_supporting_reads_{1}".format(c_id, nr)
+        sam.write(path, sr.names, sr.rs, [name], [len(seqs[x])], [(0, parts[x])], extra_unmapped=near[x], suffixes=sr.sfx, flip=flip, jobs=args._writers.native if getattr(args, "_writers", None) is not None else None)
+    T["write_sam"] = time() - t0
 
 
 def _variant_step(args, api, groups, T):
@@ -944,6 +967,8 @@ def _finish(args, api, st, clustered, t0):
         logging.info(f"Finished Consensus creation: {len(merged)} created")
         if getattr(args, "recruit", False):
             _recruit_step(args, api, sr, work_dev, merged, goff, list_order, T)
+        if getattr(args, "write_sam", False) and merged:
+            _sam_step(args, api, sr, work_dev, merged, flip if getattr(args, "strand_aware", False) and len(sel) == sr.n else None, T)
     if work_dev is not work:
         work_dev.release()
     return dict(n_sorted=sr.n, n_clustered=len(sel), clusters=len(reps), centers=merged, timings=T, counters=counters)

@@ -149,7 +149,7 @@ def _support_of(api, rs, seqs, lists, k, w):
 
 
 def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None):
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
     """Everything behind the clustering call, once for a list of samples: reads [seg_off[s], seg_off[s+1]) of rs are sample s, out[s] is its result dict (rep_of in read
     indices local to the sample) and bands[s] the band of its draft and polishing calls.  Per sample the cluster table and the selection with the sample's own cut-off, the
     reverse-complement bookkeeping and the pooled read lists; for all samples ONE alignment call, one consensus_support call and one search, and per distinct band one draft
@@ -255,6 +255,22 @@ def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ra
         for o, part in zip(out, per):
             o["recruit"] = part
         T["recruit"] = T.get("recruit", 0.0) + time.perf_counter() - t0
+    if alignments:
+        from . import sam as sam_mod
+        t0 = time.perf_counter()
+        lists = {}                                                              # per sample the reads listed under every centre, read numbers of rs
+        for s in tab:
+            if recruit:                                                         # every assigned read under its recruited centre (sam.recruited_lists)
+                a0 = np.uint32(int(seg_off[s]))
+                lists[s] = [l + a0 for l in sam_mod.recruited_lists(out[s]["recruit"]["hits"], out[s]["recruit"]["status"], len(polished[s]))[0]]
+            else:
+                lists[s] = [np.asarray(l, dtype=np.uint32) for l in pooled[s]]
+        parts = sam_mod.align(api, rs, flat, [l for s in tab for l in lists[s]], k=k, w=w, **(alignment_kwargs or {}))
+        for s, part in zip(tab, _deal(parts, sizes)):
+            a0 = int(seg_off[s])
+            for e in part: e["reads"] = e["reads"].astype(np.int64) - a0         # local to the sample, like rep_of
+            out[s]["alignments"] = part
+        T["alignments"] = T.get("alignments", 0.0) + time.perf_counter() - t0
     return polished, pooled, prms
 
 
@@ -262,7 +278,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
                  strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None, chimeras=False, chimera_kwargs=None,
-                 hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None):
+                 hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
@@ -281,7 +297,10 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     dict(round, pos, letter, old, new, hist [2, 17]) for the runs it changed (hp_kwargs: rounds and the thresholds of hp.call).
     recruit=True (extension; recruit.py, include/ngsid_recruit.h): also recruit = dict(hits [n, 6] int32 in RECRUIT_FIELDS order with centre numbers, status [n] int8, counts =
     recruit.recount): every read of the call (the oriented ones under strand_aware) located inside every final sequence on both strands, ONE Api.recruit call behind hp_polish
-    (recruit_kwargs: min_identity, q, min_margin, both_strands); every other key is what recruit=False returns."""
+    (recruit_kwargs: min_identity, q, min_margin, both_strands); every other key is what recruit=False returns.
+    alignments=True (extension; sam.py, include/ngsid_cigar.h): also alignments = one dict(reads, strand, aln [n, 5] in CIGAR_FIELDS order, op_off, ops) per centre - the
+    alignment of every listed read to the centre's final sequence, ONE Api.read_cigars call behind hp_polish; the reads listed are the pooled lists the polisher takes, with
+    recruit=True every assigned read under its recruited centre (alignment_kwargs: clip, merge_m, cap); every other key is what alignments=False returns."""
     T = timings if timings is not None else {}
     t0 = time.perf_counter()
     prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
@@ -304,13 +323,14 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     if recruit:
         from . import recruit as recruit_mod
         res["recruit"] = recruit_mod.nothing(n)                                  # what stays without a centre: every read unassigned
+    if alignments: res["alignments"] = []
     if not do_consensus:
         return res
     # one sample, reads [0, n); band goes through as it is: for band <= 0 the library applies the POA_BAND64_MAXLEN rule to the reads of the call, which here are the sample's
     # (reading the lengths of a device-resident set here would cost a copy of its offsets to the host in every step)
     stages = _consensus_stages(api, rs, score, [0, n], [res], [band], T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
                                do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs,
-                               recruit, recruit_kwargs)
+                               recruit, recruit_kwargs, alignments, alignment_kwargs)
     if split_haplotypes and stages is not None:
         from . import phase
         t0 = time.perf_counter()
@@ -346,7 +366,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
                          strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None,
-                         variants=False, variant_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None):
+                         variants=False, variant_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
@@ -358,7 +378,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     sample's dict): the final sequences of ALL samples in one near-pairs call, clustered by abundance (variant_kwargs: identity, max_dist, both_strands, wide_max_dist - the last replaces max_dist and takes the wide kernels); every other key
     is what variants=False returns.  hp_polish=True: the hp_polish key of run_hot_path per sample, ONE Api.hp_runs call per round for all samples; the variants see the
     corrected sequences.  recruit=True: the recruit key of run_hot_path per sample (read indices and centre numbers local to the sample), ONE Api.recruit call for all
-    samples.  strand_aware is not supported here (ValueError)."""
+    samples.  alignments=True: the alignments key of run_hot_path per sample (read indices local to the sample), ONE Api.read_cigars call for all samples.
+    strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
     T = timings if timings is not None else {}
@@ -379,6 +400,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     if recruit:
         from . import recruit as recruit_mod
         for s, o in enumerate(out): o["recruit"] = recruit_mod.nothing(int(so[s + 1] - so[s]))
+    if alignments:
+        for o in out: o["alignments"] = []
     if not do_consensus:
         return out
     t0 = time.perf_counter()
@@ -386,7 +409,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
                       do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs,
-                      recruit, recruit_kwargs)
+                      recruit, recruit_kwargs, alignments, alignment_kwargs)
     if variants:
         from . import variants as variants_mod
         t0 = time.perf_counter()
