@@ -120,6 +120,10 @@ CIGAR_FIELDS = ("t_begin", "t_end", "q_begin", "q_end", "nm")                   
 CIGAR_OPS = "MIDNSHP=X"                                                            # BAM's op codes: an entry of ops is length << 4 | code
 
 
+ERRPROF_NCOUNT, ERRPROF_NQ = 96, 94                                                # include/ngsid_errprof.h NGSID_ERRPROF_NCOUNT, _NQ
+ERRPROF_PAIR, ERRPROF_INS_LETTER, ERRPROF_CEN_OTHER, ERRPROF_READS, ERRPROF_INS_LEN, ERRPROF_DEL_LEN, ERRPROF_HPCTX = 0, 24, 29, 30, 32, 48, 64      # where the tables of Api.error_profile start
+
+
 def cluster_params(k=13, w=20, min_shared=5, min_fraction=0.8, mapped_threshold=0.7, aligned_threshold=0.4,
                    min_prob_no_hits=0.1, symmetric=False, p_shared=None):
     p = ClusterParams()
@@ -729,6 +733,20 @@ class Api:
         (aln, op_off, ops), n = self._found_list("read_cigars", head, 3, lambda c: (np.full((max(nl, 1), CIGAR_NFIELD), -1, dtype=np.int32), np.zeros(nl + 1, dtype=np.uint64),
                                                                                    np.zeros(max(c, 1), dtype=np.uint32)), cap)
         return aln[:nl], op_off, ops[:n], strand[:nl]
+
+    # ---- include/ngsid_errprof.h
+    def error_profile(self, centres: ReadSet, rs: ReadSet, grp_off, read_order=None, k=13, w=20, clip=False, qualities=True):
+        """ngsid_error_profile: what the reads of every group did to the letters of its centre, per strand -> (counts [n_groups, 2, ERRPROF_NCOUNT] uint64, qtab
+        [n_groups, 2, ERRPROF_NQ, 3] uint64 or None, strand [n_listed] int8).  counts[g, s]: PAIR [4, 6] (centre letter x read letter A C G T, other, deleted), INS_LETTER [5],
+        CEN_OTHER, READS, INS_LEN [16], DEL_LEN [16], HPCTX [8, 4] at the ERRPROF_* offsets; qtab[g, s, q]: read bases of reported quality q in '=', 'X' and 'I' columns
+        (all zeros for a read set without qualities; qualities=False: None, the table and its cost are skipped).  Grouping, strands and counted columns as in
+        consensus_support().  There is no CPU implementation: a library without the entry point is an error."""
+        grp_off, ro, ng, strand, prm = self._support_head("error_profile", "ngsid_errprof.h", ("error_profile",), centres, grp_off, read_order, k, w, clip)
+        counts = np.zeros((max(ng, 1), 2, ERRPROF_NCOUNT), dtype=np.uint64)
+        qtab = np.zeros((max(ng, 1), 2, ERRPROF_NQ, 3), dtype=np.uint64) if qualities else None
+        rc = self._call("error_profile", C.byref(centres.c), C.byref(rs.c), _p(ro), _p(grp_off), C.c_uint64(ng), C.byref(prm), _p(counts), _p(qtab), _p(strand))
+        if rc: self._err(rc)
+        return counts[:ng], None if qtab is None else qtab[:ng], strand[:int(grp_off[-1])]
 
     # ---- include/ngsid_phase.h
     def phase_genotypes(self, centres: ReadSet, rs: ReadSet, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):

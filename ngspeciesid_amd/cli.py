@@ -114,6 +114,8 @@ def build_parser():
     _recruit.add_flags(p)
     from . import sam as _sam
     _sam.add_flags(p)
+    from . import errprof as _errprof
+    _errprof.add_flags(p)
     from . import phase as _phase
     p.add_argument('--split_haplotypes', action='store_true', help='extension: split every cluster whose reads carry linked variant sites (two alleles, a NUMT beside its original, sister species) into haplotypes. Sites come from the per-base support, the read x site genotypes, pair tables and the assignment are computed on the GPU; every haplotype gets its own draft and polish. Writes <outfolder>/haplotypes.tsv (cluster_id haplotype reads sites alleles) and racon_cl_id_{id}/consensus_h{j}.fasta (without --racon consensus_reference_{id}_h{j}.fasta); with --reference_db the haplotypes are rows of classification.tsv. Needs --consensus; not with --fastq_dir / --demux_sheet')
     p.add_argument('--hap_min_alt_frac', type=float, default=_phase.DEFAULTS["min_alt_frac"], help='extension: a base is a candidate site when its second most frequent allele holds at least this share of the depth')
@@ -200,6 +202,18 @@ def _sam_subparser(cf):
     return cf
 
 
+def _errprof_subparser(cf):
+    """the `errprof` sub-command: parsed by a parser of its own, like `classify`"""
+    from . import recruit as _recruit
+    cf.add_argument('--fastq', type=str, required=True, help='the reads')
+    cf.add_argument('--fasta', type=str, required=True, help='the sequences the reads are recruited to and profiled against (at most 2048 letters each)')
+    cf.add_argument('--outfolder', type=str, required=True, help='where error_profile.tsv and quality_calibration.tsv go')
+    cf.add_argument('--q', dest="quality_threshold", type=float, default=7.0, help='the read filter of the run the reads come from: the default of --recruit_min_identity')
+    _recruit.add_flags(cf)
+    cf.set_defaults(which='errprof')
+    return cf
+
+
 def _check_recruit(args):
     from . import recruit as _recruit
     err = _recruit.check_args(args)
@@ -242,6 +256,8 @@ def cli(argv=None):
         args = _recruit_subparser(argparse.ArgumentParser(prog='recruit', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'sam':
         args = _sam_subparser(argparse.ArgumentParser(prog='sam', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
+    elif argv and argv[0] == 'errprof':
+        args = _errprof_subparser(argparse.ArgumentParser(prog='errprof', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     elif argv and argv[0] == 'umi':
         args = _umi_subparser(argparse.ArgumentParser(prog='umi', formatter_class=argparse.ArgumentDefaultsHelpFormatter)).parse_args(argv[1:])
     else:
@@ -291,6 +307,15 @@ def cli(argv=None):
         from . import sam as _sam
         res = _sam.sam_fastq(args)
         logging.info("Wrote %d records (%d mapped) to %s." % (res["records"], res["mapped"], args.outfile))
+        sys.exit(0)
+    if getattr(args, "which", "main") == 'errprof':
+        _check_recruit(args)
+        for f in (args.fastq, args.fasta):
+            if not os.path.isfile(f):
+                logging.error("%s is not a file." % f); sys.exit(1)
+        from . import errprof as _errprof
+        res = _errprof.errprof_fastq(args)
+        logging.info("Profiled %d reads against %d sequences; wrote %s." % (sum(len(l) for l in res["lists"]), len(res["ids"]), args.outfolder))
         sys.exit(0)
     if getattr(args, "which", "main") == 'umi':
         from . import umi as _umi
@@ -364,6 +389,8 @@ def cli(argv=None):
         err = _sam.check_args(args) or (None if args.consensus else "--write_sam aligns reads to consensus sequences: it needs --consensus.")
         if err:
             logging.error(err); sys.exit(1)
+    if getattr(args, "error_profile", False) and not args.consensus:
+        logging.error("--error_profile profiles reads against consensus sequences: it needs --consensus."); sys.exit(1)
     if getattr(args, "hp_polish", False):
         if not args.consensus:
             logging.error("--hp_polish corrects consensus sequences: it needs --consensus."); sys.exit(1)

@@ -15,6 +15,7 @@ struct RecPlan {
     const uint8_t* d_cen_seq = nullptr; const uint64_t* d_cen_off = nullptr;      // device: the centres
     const uint8_t* bseq = nullptr;                   // host: the bytes of the centres (boff)
     const uint8_t* h_orient = nullptr; const uint32_t* pair_read = nullptr;      // host: strand of every READ (0, 1, 255 = none), read of every pair
+    const uint8_t* d_oqual = nullptr;                // device: the oriented qualities (as d_oseq), null when the read set came without qualities
 };
 struct RecChunk { const uint32_t* rec; const int32_t* span; uint64_t c0, c1; const uint16_t* pos; };   // path matrix and spans {q_begin, q_end, t_begin, t_end} of the pairs [c0, c1), row 0 = pair c0;
                                                                                   // pos (want_pos only, else null): read index of every '=' / 'X' column, [pair][stride * 8] uint16

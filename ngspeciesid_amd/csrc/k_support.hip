@@ -78,7 +78,7 @@ int32_t ngsid_rec_walk(ngsid_ctx* ctx, const ngsid_reads_t* centres, const ngsid
     // ---- chunks of pairs under the byte budget of the path matrix (the share of the free device memory the POA batches take; option "support_budget_mb")
     const uint32_t stride = ((maxb + 63u) & ~63u) / 8;                    // dwords per row
     P.stride = stride; P.d_cen_seq = BB.seq; P.d_cen_off = BB.off; P.d_pair_group = d_pair_group.p;
-    P.d_oseq = ctx->pol_oseq.p; P.d_read_off = RD.off; P.d_pair_read = d_pair_read.p;
+    P.d_oseq = ctx->pol_oseq.p; P.d_oqual = RD.qual ? ctx->pol_oqual.p : nullptr; P.d_read_off = RD.off; P.d_pair_read = d_pair_read.p;
     rc = start(P); if (rc) return rc;
     const long long mb = ngsid_opt(ctx, "support_budget_mb", 0);
     const size_t budget = mb > 0 ? (size_t)mb << 20 : ngsid_mem_share(3, (size_t)256 << 20, (size_t)16 << 30, (size_t)16 << 30);

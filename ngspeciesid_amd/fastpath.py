@@ -811,6 +811,23 @@ def _sam_step(args, api, sr, work, merged, flip, T):
     T["write_sam"] = time() - t0
 
 
+def _errprof_step(args, api, sr, work, merged, T):
+    """--error_profile: what the listed reads did to the letters of the final sequence of their centre, one library call (errprof.profile) -> error_profile.tsv and
+    quality_calibration.tsv in the sample's folder.  The reads listed are the polisher's (clip as in the polisher); behind --recruit every assigned read under its
+    recruited centre (sam.recruited_lists), as --write_sam does it."""
+    from . import errprof, sam
+    t0 = time()
+    lists, clip = args._sam_lists
+    if getattr(args, "recruit", False) and getattr(args, "_recruit_res", None) is not None:
+        lists, _, _ = sam.recruited_lists(args._recruit_res["hits"], args._recruit_res["status"], len(merged))
+        if getattr(args, "_overlong", False): lists = [l[sr.lens[l] <= MAX_CONSENSUS_LEN] for l in lists]
+    ids = [m[1] for m in merged]
+    parts = errprof.profile(api, work, [m[2] for m in merged], [np.asarray(l, dtype=np.uint32) for l in lists], k=args.k, w=args.w, clip=clip)
+    errprof.write_sample(args.outfolder, ids, parts)
+    args._errprof = (ids, parts)
+    T["error_profile"] = time() - t0
+
+
 def _variant_step(args, api, groups, T):
     """--variants: the final consensuses of every (sample, folder, centres) group of a multi-sample run compared with each other in one library call and joined into
     study-wide variants (variants.run) -> <outfolder>/variants.fasta, variant_table.tsv, variant_members.tsv"""
@@ -883,6 +900,12 @@ def _main_samples(args, api):
         for x, (a, _) in enumerate(subs):
             ids, counts = getattr(a, "_recruit", ([], dict(centres=[], ambiguous=0, unassigned=0)))
             recruit.write_recount(os.path.join(args.outfolder, "recount_all.tsv"), ids, counts, sample=os.path.basename(a.outfolder), header=x == 0, mode="w" if x == 0 else "a")
+    if getattr(args, "error_profile", False) and args.consensus:
+        from . import errprof
+        first = True
+        for a, _ in subs:
+            if getattr(a, "_errprof", None) is None: continue
+            errprof.append_all(args.outfolder, os.path.basename(a.outfolder), a._errprof[0], a._errprof[1], first); first = False
     return dict(samples=out, timings=T, n_sorted=sum(r["n_sorted"] for r in out.values()), n_clustered=sum(r["n_clustered"] for r in out.values()),
                 clusters=sum(r["clusters"] for r in out.values()))
 
@@ -969,6 +992,8 @@ def _finish(args, api, st, clustered, t0):
             _recruit_step(args, api, sr, work_dev, merged, goff, list_order, T)
         if getattr(args, "write_sam", False) and merged:
             _sam_step(args, api, sr, work_dev, merged, flip if getattr(args, "strand_aware", False) and len(sel) == sr.n else None, T)
+        if getattr(args, "error_profile", False) and merged:
+            _errprof_step(args, api, sr, work_dev, merged, T)
     if work_dev is not work:
         work_dev.release()
     return dict(n_sorted=sr.n, n_clustered=len(sel), clusters=len(reps), centers=merged, timings=T, counters=counters)

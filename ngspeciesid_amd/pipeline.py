@@ -149,14 +149,15 @@ def _support_of(api, rs, seqs, lists, k, w):
 
 
 def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
-                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
+                      do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras=False, chimera_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None, error_profile=False, error_profile_kwargs=None):
     """Everything behind the clustering call, once for a list of samples: reads [seg_off[s], seg_off[s+1]) of rs are sample s, out[s] is its result dict (rep_of in read
     indices local to the sample) and bands[s] the band of its draft and polishing calls.  Per sample the cluster table and the selection with the sample's own cut-off, the
     reverse-complement bookkeeping and the pooled read lists; for all samples ONE alignment call, one consensus_support call and one search, and per distinct band one draft
     and one polishing call.  Fills centers (and support / classify, when asked for) into the dicts of the samples that have a centre above their cut-off and leaves the other
     dicts as they are.  hp_polish (extension, hp.py): the homopolymer run-length vote over the final sequences of ALL samples - one Api.hp_runs call per round - after
     the polishing (or the draft, without it) and before support, classification and chimeras, which see the corrected sequences; hp_polish of a sample's dict = one change
-    table per centre.  -> None when no sample has one, else (polished, pooled, prms): polished[s] the final sequences and pooled[s] the polisher's read lists (read numbers
+    table per centre.  error_profile (extension, errprof.py): the read error tables of the final sequences over the lists of support, one Api.error_profile call for all
+    samples.  -> None when no sample has one, else (polished, pooled, prms): polished[s] the final sequences and pooled[s] the polisher's read lists (read numbers
     of rs) of every centre of sample s, prms[band] the (draft, polish or None) parameter structs of that band's calls."""
     tile_depth = TILE_DEPTH if tile_depth is None else tile_depth
     single_below = SINGLE_BELOW if single_below is None else single_below
@@ -227,6 +228,12 @@ def _consensus_stages(api, rs, score, seg_off, out, bands, T, k, w, abundance_ra
         for s, part in zip(tab, _deal(_support_of(api, rs, flat, [l for s in tab for l in pooled[s]], k, w), sizes)):
             out[s]["support"] = part
         T["support"] = T.get("support", 0.0) + time.perf_counter() - t0
+    if error_profile:                                                           # the read error tables of the final sequences over the lists support=True takes: one call
+        from . import errprof as errprof_mod
+        t0 = time.perf_counter()
+        for s, part in zip(tab, _deal(errprof_mod.profile(api, rs, flat, [l for s in tab for l in pooled[s]], k=k, w=w, **(error_profile_kwargs or {})), sizes)):
+            out[s]["error_profile"] = part
+        T["error_profile"] = T.get("error_profile", 0.0) + time.perf_counter() - t0
     if classify is not None:
         from . import classify as classify_mod
         t0 = time.perf_counter()
@@ -278,7 +285,7 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
                  rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                  p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
                  strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, split_haplotypes=False, haplotype_kwargs=None, chimeras=False, chimera_kwargs=None,
-                 hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
+                 hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None, error_profile=False, error_profile_kwargs=None):
     """Returns dict(rep_of, status, counters, hpc_err, centers=[(n_reads, c_id, draft, polished, groups)]); with strand_aware (extension, off by
     default: strand.py) also flip [n] = reads that were reverse-complemented for the consensus stages, and rep_of is the merged membership.
     support=True (extension): also support = one [len, 8] uint32 array per centre - the read support of every base of its final sequence over the pooled reads the
@@ -300,7 +307,10 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
     (recruit_kwargs: min_identity, q, min_margin, both_strands); every other key is what recruit=False returns.
     alignments=True (extension; sam.py, include/ngsid_cigar.h): also alignments = one dict(reads, strand, aln [n, 5] in CIGAR_FIELDS order, op_off, ops) per centre - the
     alignment of every listed read to the centre's final sequence, ONE Api.read_cigars call behind hp_polish; the reads listed are the pooled lists the polisher takes, with
-    recruit=True every assigned read under its recruited centre (alignment_kwargs: clip, merge_m, cap); every other key is what alignments=False returns."""
+    recruit=True every assigned read under its recruited centre (alignment_kwargs: clip, merge_m, cap); every other key is what alignments=False returns.
+    error_profile=True (extension; errprof.py, include/ngsid_errprof.h): also error_profile = one dict(counts [2, 96], qtab [2, 94, 3] or None, n_listed, n_stranded) per centre -
+    what the pooled reads the polisher takes (the lists of support=True) did to the letters of the centre's final sequence, ONE Api.error_profile call behind hp_polish
+    (error_profile_kwargs: clip, qualities); every other key is what error_profile=False returns.  The centre is made of the same reads: errprof.py says what that hides."""
     T = timings if timings is not None else {}
     t0 = time.perf_counter()
     prm = cluster_params(k=k, w=w, p_shared=p_shared, **(cluster_kwargs or {}))
@@ -324,13 +334,14 @@ def run_hot_path(api: Api, rs: ReadSet, score: np.ndarray, acc_rank=None, k=13, 
         from . import recruit as recruit_mod
         res["recruit"] = recruit_mod.nothing(n)                                  # what stays without a centre: every read unassigned
     if alignments: res["alignments"] = []
+    if error_profile: res["error_profile"] = []
     if not do_consensus:
         return res
     # one sample, reads [0, n); band goes through as it is: for band <= 0 the library applies the POA_BAND64_MAXLEN rule to the reads of the call, which here are the sample's
     # (reading the lengths of a device-resident set here would cost a copy of its offsets to the host in every step)
     stages = _consensus_stages(api, rs, score, [0, n], [res], [band], T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
                                do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs,
-                               recruit, recruit_kwargs, alignments, alignment_kwargs)
+                               recruit, recruit_kwargs, alignments, alignment_kwargs, error_profile, error_profile_kwargs)
     if split_haplotypes and stages is not None:
         from . import phase
         t0 = time.perf_counter()
@@ -366,7 +377,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
                          rc_identity_threshold=0.9, max_seqs_for_consensus=-1, racon_iter=3, tile_depth=None, band=0, node_cap=0,
                          p_shared=None, cluster_kwargs=None, do_consensus=True, do_polish=True, timings=None, polish_trim=2, polish_aln_mode=2, polish_stop_when_stable=True,
                          strand_aware=False, draft_trim=None, single_below=None, support=False, classify=None, classify_kwargs=None, chimeras=False, chimera_kwargs=None,
-                         variants=False, variant_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None):
+                         variants=False, variant_kwargs=None, hp_polish=False, hp_kwargs=None, recruit=False, recruit_kwargs=None, alignments=False, alignment_kwargs=None,
+                         error_profile=False, error_profile_kwargs=None):
     """run_hot_path for many samples in one pass: reads [seg_off[s], seg_off[s+1]) of rs (each sample in its own score order) are sample s.  Returns one
     run_hot_path-shaped dict per sample, read indices local to the sample - what run_hot_path returns for that sample's reads alone.  One segmented clustering
     call, one draft consensus call, one alignment call for the reverse-complement detection and one polishing call serve all samples; with band <= 0 the samples
@@ -379,6 +391,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     is what variants=False returns.  hp_polish=True: the hp_polish key of run_hot_path per sample, ONE Api.hp_runs call per round for all samples; the variants see the
     corrected sequences.  recruit=True: the recruit key of run_hot_path per sample (read indices and centre numbers local to the sample), ONE Api.recruit call for all
     samples.  alignments=True: the alignments key of run_hot_path per sample (read indices local to the sample), ONE Api.read_cigars call for all samples.
+    error_profile=True: the error_profile key of run_hot_path per sample, ONE Api.error_profile call for all samples.
     strand_aware is not supported here (ValueError)."""
     if strand_aware:
         raise ValueError("run_hot_path_samples: strand_aware is not supported in multi-sample mode (run the samples one by one)")
@@ -402,6 +415,8 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
         for s, o in enumerate(out): o["recruit"] = recruit_mod.nothing(int(so[s + 1] - so[s]))
     if alignments:
         for o in out: o["alignments"] = []
+    if error_profile:
+        for o in out: o["error_profile"] = []
     if not do_consensus:
         return out
     t0 = time.perf_counter()
@@ -409,7 +424,7 @@ def run_hot_path_samples(api: Api, rs: ReadSet, score: np.ndarray, seg_off, acc_
     T["host_group"] = T.get("host_group", 0.0) + time.perf_counter() - t0
     _consensus_stages(api, rs, score, so, out, bands, T, k, w, abundance_ratio, rc_identity_threshold, max_seqs_for_consensus, racon_iter, tile_depth, node_cap,
                       do_polish, polish_trim, polish_aln_mode, polish_stop_when_stable, draft_trim, single_below, support, classify, classify_kwargs, chimeras, chimera_kwargs, hp_polish, hp_kwargs,
-                      recruit, recruit_kwargs, alignments, alignment_kwargs)
+                      recruit, recruit_kwargs, alignments, alignment_kwargs, error_profile, error_profile_kwargs)
     if variants:
         from . import variants as variants_mod
         t0 = time.perf_counter()
