@@ -1,7 +1,8 @@
 /* ngsid_cigar.h - the alignment of every read to the centre of its group as a run-length-encoded list of BAM operations, on top of include/ngsid_support.h.
  *
  * Additive: ngsid_abi_version() stays 2.  The call has no twin in the CPU oracle - its definition is restated from the oracle's parts by the tests
- * (tests/cigar_reference.py: strands and alignment columns as tests/support_reference.py, run lengths in numpy).  The library returns integers only; the text
+ * (tests/cigar_reference.py: strands and alignment columns as tests/support_reference.py, run lengths in numpy).  The columns and strands those parts give are also pinned, without the
+ * oracle, by tests/columns_reference.py (from tests/ed_reference.py and the strand rule of tests/polish_reference.py; tests/test_gpu_rec_reference.py).  The library returns integers only; the text
  * of a CIGAR is made by the record writer (ngsid_host_write_sam, include/ngsid.h) and which reads are listed under which centre is policy (ngspeciesid_amd/sam.py). */
 #ifndef NGSID_CIGAR_H
 #define NGSID_CIGAR_H
@@ -38,7 +39,9 @@ extern "C" {
  *   - the lengths of the ops that consume the centre (M, =, X, D) sum to t_end - t_begin + 1;
  *   - the first and the last op that is not S are match ops (M, =, X);
  *   - neighbouring ops differ;
- *   - an I run never touches a D run (next to each other they cost two edits where one X costs one: no minimum-cost path holds the pair).
+ *   - an I run never touches a D run (next to each other they cost two edits where one X costs one: no minimum-cost path holds the pair).  This holds for the
+ *     counted columns, which are all a caller sees.  Outside them the free centre ends are centre-only columns that cost nothing: read letters in front of the
+ *     first match column follow the free prefix directly (they are soft-clipped here), and those behind the last one are followed by the free suffix.
  *
  * Capacity: *needed is always the total number of ops.  cap = 0 with null aln, op_off and ops is the count call (NGSID_ERR_CAPACITY whenever there is an op,
  * NGSID_OK otherwise).  A fill call with fewer than *needed entries of room returns NGSID_ERR_CAPACITY; the call streams chunk by chunk, so on that error the

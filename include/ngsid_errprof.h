@@ -2,7 +2,8 @@
  * include/ngsid_support.h.
  *
  * Additive: ngsid_abi_version() stays 2.  The call has no twin in the CPU oracle - its definition is restated from the oracle's parts by the tests
- * (tests/errprof_reference.py: strands and alignment columns as tests/support_reference.py, counted columns as tests/cigar_reference.py, the tables in numpy).
+ * (tests/errprof_reference.py: strands and alignment columns as tests/support_reference.py, counted columns as tests/cigar_reference.py, the tables in numpy).  The columns and strands those parts give are also pinned, without the
+ * oracle, by tests/columns_reference.py (from tests/ed_reference.py and the strand rule of tests/polish_reference.py; tests/test_gpu_rec_reference.py).
  * The library returns integer sums only; rates, shares, the empirical Phred of a quality bin and every sentence about what the tables mean are policy and live in
  * the binding layer (ngspeciesid_amd/errprof.py).  NB the centre is made of the same reads: an error the majority of a group shares is invisible here, and a true
  * minority variant counts as an error. */

@@ -1,7 +1,8 @@
 /* ngsid_hp.h - per homopolymer run of a consensus sequence, how long that run is in every read, on top of include/ngsid_support.h.
  *
  * Additive: ngsid_abi_version() stays 2.  The call has no twin in the CPU oracle - its definition is restated from the oracle's parts by the tests
- * (tests/hp_reference.py: strands and alignment columns as tests/support_reference.py, read positions by cumulative sums, counting in numpy).  The library
+ * (tests/hp_reference.py: strands and alignment columns as tests/support_reference.py, read positions by cumulative sums, counting in numpy).  The columns and strands those parts give are also pinned, without the
+ * oracle, by tests/columns_reference.py (from tests/ed_reference.py and the strand rule of tests/polish_reference.py; tests/test_gpu_rec_reference.py).  The library
  * returns integers only; which length is called from a histogram is policy and lives in the binding layer (ngspeciesid_amd/hp.py). */
 #ifndef NGSID_HP_H
 #define NGSID_HP_H

@@ -3,7 +3,8 @@
  * Additive: ngsid_abi_version() stays 2.  Three calls: the allele of every read at chosen centre positions (read x site genotypes), the 5 x 5 co-occurrence table of every
  * pair of sites, and the assignment of every read to the nearest of a set of haplotypes.  Which positions are sites, which sites are linked and which allele strings are
  * haplotypes is policy and lives in the binding layer (ngspeciesid_amd/phase.py); the library returns integers only.  The calls have no twin in the CPU oracle - their
- * definition is restated from the oracle's parts by the tests (tests/phase_reference.py).
+ * definition is restated from the oracle's parts by the tests (tests/phase_reference.py).  The columns and strands those parts give are also pinned, without the
+ * oracle, by tests/columns_reference.py (from tests/ed_reference.py and the strand rule of tests/polish_reference.py; tests/test_gpu_rec_reference.py).
  *
  * The genotype matrix crosses the boundary as a HOST array in both directions (at most 64 B per listed read). */
 #ifndef NGSID_PHASE_H

@@ -1,7 +1,8 @@
 /* ngsid_support.h - per-base read support of a consensus sequence, on top of include/ngsid.h.
  *
  * Additive: ngsid_abi_version() stays 2.  The call has no twin in the CPU oracle - its definition is restated from the oracle's parts by the tests
- * (tests/support_reference.py: strands of ongsid_polish_trace_aln, alignment columns of ongsid_i_ed_ops, counting in numpy).  The library returns integers
+ * (tests/support_reference.py: strands of ongsid_polish_trace_aln, alignment columns of ongsid_i_ed_ops, counting in numpy).  The columns and strands those parts give are also pinned, without the
+ * oracle, by tests/columns_reference.py (from tests/ed_reference.py and the strand rule of tests/polish_reference.py; tests/test_gpu_rec_reference.py).  The library returns integers
  * only; the quality formula lives in the binding layer (consensus.support_phred). */
 #ifndef NGSID_SUPPORT_H
 #define NGSID_SUPPORT_H

@@ -3,7 +3,7 @@
 Strands and alignment columns as tests/support_reference.py (the oracle's polish_trace record [0], ongsid_i_ed_ops); the counted columns, the spans, nm and the run
 lengths in numpy, here.  cigar_reference returns exactly what Api.read_cigars returns."""
 import numpy as np
-from support_reference import ed_ops, strands, _COMP, CLIP_RUN
+from support_reference import ed_ops, strands, columns, strand_list, _COMP, CLIP_RUN
 
 OP_M, OP_I, OP_D, OP_S, OP_EQ, OP_X = 0, 1, 2, 4, 7, 8
 COLUMN_OP = np.array([OP_EQ, OP_X, OP_I, OP_D], dtype=np.int64)                 # the oracle's column codes 0 '=' 1 'X' 2 'I' 3 'D' as BAM ops
@@ -68,12 +68,12 @@ def oriented(rs, r, strand):
     return np.ascontiguousarray(_COMP[read[::-1]] if strand == 1 else read)
 
 
-def cigar_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, merge_m=False, only=None):
+def cigar_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, merge_m=False, only=None, source=None):
     """-> (aln [n_listed, 5] int32, op_off [n_listed + 1] uint64, ops uint32, strand [n_listed] int8) as Api.read_cigars returns them.  only: a set of listed positions -
-    the others get no ops and -1 (for a sample of a large call; their strand is still filled)"""
+    the others get no ops and -1 (for a sample of a large call; their strand is still filled); source as in support_reference"""
     grp_off = np.asarray(grp_off, dtype=np.uint64); ng = len(grp_off) - 1; nl = int(grp_off[-1])
     ro = np.arange(nl, dtype=np.uint32) if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-    st = strands(oracle, centres, rs, grp_off, ro, k, w) if nl else np.zeros(0, np.int8)
+    st = strand_list(oracle, source, centres, rs, grp_off, ro, k, w) if nl else np.zeros(0, np.int8)
     aln = np.full((nl, 5), -1, dtype=np.int32); op_off = np.zeros(nl + 1, dtype=np.uint64); ops = []
     for g in range(ng):
         centre = np.frombuffer(centres[g].encode(), dtype=np.uint8)
@@ -81,7 +81,7 @@ def cigar_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, c
             op_off[x + 1] = op_off[x]
             if st[x] < 0 or (only is not None and x not in only) or len(centre) == 0: continue
             read = oriented(rs, int(ro[x]), int(st[x]))
-            a, runs = cigar_of_columns(ed_ops(oracle, read, centre), len(read), clip, merge_m)
+            a, runs = cigar_of_columns(columns(oracle, source, read, centre), len(read), clip, merge_m)
             if a is None: continue
             aln[x] = a; ops += [(l << 4) | o for l, o in runs]; op_off[x + 1] = op_off[x] + np.uint64(len(runs))
     return aln, op_off, np.array(ops, dtype=np.uint32), st

@@ -3,7 +3,7 @@
 Strands and alignment columns as tests/support_reference.py (the oracle's polish_trace record [0], ongsid_i_ed_ops), the counted columns as tests/cigar_reference.py; the
 tables in numpy, here, from the column list, the oriented read, the oriented qualities and the centre.  errprof_reference returns exactly what Api.error_profile returns."""
 import numpy as np
-from support_reference import ed_ops, strands
+from support_reference import ed_ops, strands, columns, strand_list
 from cigar_reference import counted, oriented
 
 NCOUNT, NQ = 96, 94
@@ -61,11 +61,11 @@ def profile_columns(cnt, qt, ops, read, qual, centre, clip):
         qt += np.bincount(qq * 3 + np.array([0, 1, 2, 0])[o[rd]], minlength=NQ * 3).astype(np.uint64).reshape(NQ, 3)
 
 
-def errprof_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, qualities=True):
-    """-> (counts [n_groups, 2, 96] uint64, qtab [n_groups, 2, 94, 3] uint64 or None, strand [n_listed] int8) as Api.error_profile returns them"""
+def errprof_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, qualities=True, source=None):
+    """-> (counts [n_groups, 2, 96] uint64, qtab [n_groups, 2, 94, 3] uint64 or None, strand [n_listed] int8) as Api.error_profile returns them; source as in support_reference"""
     grp_off = np.asarray(grp_off, dtype=np.uint64); ng = len(grp_off) - 1; nl = int(grp_off[-1])
     ro = np.arange(nl, dtype=np.uint32) if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
-    st = strands(oracle, centres, rs, grp_off, ro, k, w) if nl else np.zeros(0, np.int8)
+    st = strand_list(oracle, source, centres, rs, grp_off, ro, k, w) if nl else np.zeros(0, np.int8)
     counts = np.zeros((ng, 2, NCOUNT), dtype=np.uint64); qtab = np.zeros((ng, 2, NQ, 3), dtype=np.uint64) if qualities else None
     for g in range(ng):
         centre = np.frombuffer(centres[g].encode(), dtype=np.uint8)
@@ -77,7 +77,7 @@ def errprof_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20,
             if rs.qual is not None:
                 qual = rs.qual[int(rs.off[r]):int(rs.off[r + 1])]
                 if s == 1: qual = qual[::-1]
-            profile_columns(counts[g, s], None if qtab is None else qtab[g, s], ed_ops(oracle, read, centre), read, qual, centre, clip)
+            profile_columns(counts[g, s], None if qtab is None else qtab[g, s], columns(oracle, source, read, centre), read, qual, centre, clip)
     return counts, qtab, st
 
 

@@ -3,7 +3,7 @@
 Strands and alignment columns: tests/support_reference.py (record [0] of the oracle's polish trace; ongsid_i_ed_ops: 0 '=', 1 'X', 2 'I' read only, 3 'D' centre only).
 Read and centre position of every column: cumulative sums, as count_read does.  The histogram: here."""
 import numpy as np
-from support_reference import strands, ed_ops, _COMP, CLIP_RUN
+from support_reference import strands, ed_ops, columns, strand_list, _COMP, CLIP_RUN
 
 NBUCKET, OTHER = 17, 16
 
@@ -56,8 +56,8 @@ def check_lists(centres, run_off, run_start):
     return True
 
 
-def hp_reference(oracle, centres, rs, grp_off, run_off, run_start, read_order=None, k=13, w=20, clip=False):
-    """-> (hist [n_runs, 2, 17] uint32, strand) as Api.hp_runs returns them"""
+def hp_reference(oracle, centres, rs, grp_off, run_off, run_start, read_order=None, k=13, w=20, clip=False, source=None):
+    """-> (hist [n_runs, 2, 17] uint32, strand) as Api.hp_runs returns them; source as in support_reference"""
     grp_off = np.asarray(grp_off, dtype=np.uint64); run_off = np.asarray(run_off, dtype=np.uint64); run_start = np.asarray(run_start, dtype=np.uint32)
     assert check_lists(centres, run_off, run_start)
     ng = len(grp_off) - 1; nl = int(grp_off[-1])
@@ -66,7 +66,7 @@ def hp_reference(oracle, centres, rs, grp_off, run_off, run_start, read_order=No
     for g in range(ng):
         a, b = int(grp_off[g]), int(grp_off[g + 1])
         if a == b: continue
-        st = strands(oracle, [centres[g]], rs, np.array([0, b - a], dtype=np.uint64), ro[a:b].copy(), k, w)
+        st = strand_list(oracle, source, [centres[g]], rs, np.array([0, b - a], dtype=np.uint64), ro[a:b].copy(), k, w)
         strand[a:b] = st
         starts = run_start[int(run_off[g]):int(run_off[g + 1])]
         if len(starts) == 0: continue
@@ -76,7 +76,7 @@ def hp_reference(oracle, centres, rs, grp_off, run_off, run_start, read_order=No
             read = rs.seq[int(rs.off[r]):int(rs.off[r + 1])]
             if st[x] == 1: read = _COMP[read[::-1]]
             read = np.ascontiguousarray(read)
-            bk = read_runs(ed_ops(oracle, read, centre), read, centre, starts, clip)
+            bk = read_runs(columns(oracle, source, read, centre), read, centre, starts, clip)
             for j in np.nonzero(bk >= 0)[0]:
                 hist[int(run_off[g]) + j, int(st[x]), bk[j]] += 1
     return hist, strand

@@ -5,18 +5,18 @@ rules) - one read's counters ARE its genotype: at a base it counts, exactly one 
 Pair tables and assignment: numpy, here.  PhaseAdapter gives an oracle-backed Api the three phase_* methods (and consensus_support), so the pipeline runs on the CPU."""
 import numpy as np
 from ngspeciesid_amd._capi import ReadSet, phase_offsets
-from support_reference import support_reference, strands, count_read, _COMP
+from support_reference import support_reference, strands, strand_list, count_read, _COMP
 
 _CODE = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate(b"ACGT"):
     _CODE[_c] = _i; _CODE[_c + 32] = _i
 
 
-def read_genotype(oracle, read, centre, sites, clip):
+def read_genotype(oracle, read, centre, sites, clip, source=None):
     """codes of ONE oriented read at the centre positions `sites`"""
     cnt = np.zeros((len(centre), 8), dtype=np.uint32)
     out = np.full(len(sites), 7, dtype=np.uint8)
-    if len(sites) == 0 or not count_read(oracle, cnt, read, centre, clip): return out
+    if len(sites) == 0 or not count_read(oracle, cnt, read, centre, clip, source): return out
     c = cnt[np.asarray(sites, dtype=np.int64)]
     assert c[:, :7].max() <= 1
     for j in range(len(sites)):
@@ -28,8 +28,8 @@ def read_genotype(oracle, read, centre, sites, clip):
     return out
 
 
-def genotypes_reference(oracle, centres, rs, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False):
-    """-> (geno, geno_off, strand) as Api.phase_genotypes returns them"""
+def genotypes_reference(oracle, centres, rs, grp_off, site_off, site_pos, read_order=None, k=13, w=20, clip=False, source=None):
+    """-> (geno, geno_off, strand) as Api.phase_genotypes returns them; source as in support_reference"""
     grp_off = np.asarray(grp_off, dtype=np.uint64); site_off = np.asarray(site_off, dtype=np.uint64); site_pos = np.asarray(site_pos, dtype=np.uint32)
     ng = len(grp_off) - 1; nl = int(grp_off[-1])
     ro = np.arange(nl, dtype=np.uint32) if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
@@ -39,7 +39,7 @@ def genotypes_reference(oracle, centres, rs, grp_off, site_off, site_pos, read_o
         a, b = int(grp_off[g]), int(grp_off[g + 1])
         if a == b: continue
         sites = site_pos[int(site_off[g]):int(site_off[g + 1])]
-        st = strands(oracle, [centres[g]], rs, np.array([0, b - a], dtype=np.uint64), ro[a:b].copy(), k, w)
+        st = strand_list(oracle, source, [centres[g]], rs, np.array([0, b - a], dtype=np.uint64), ro[a:b].copy(), k, w)
         strand[a:b] = st
         centre = np.frombuffer(centres[g].encode(), dtype=np.uint8)
         block = geno[int(geno_off[g]):int(geno_off[g + 1])].reshape(b - a, len(sites))
@@ -47,7 +47,7 @@ def genotypes_reference(oracle, centres, rs, grp_off, site_off, site_pos, read_o
             if st[x] < 0 or len(sites) == 0: continue
             read = rs.seq[int(rs.off[r]):int(rs.off[r + 1])]
             if st[x] == 1: read = _COMP[read[::-1]]
-            block[x] = read_genotype(oracle, np.ascontiguousarray(read), centre, sites, clip)
+            block[x] = read_genotype(oracle, np.ascontiguousarray(read), centre, sites, clip, source)
     return geno, geno_off, strand
 
 

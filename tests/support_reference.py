@@ -1,7 +1,8 @@
 """The definition of ngsid_consensus_support (include/ngsid_support.h) restated from the CPU oracle's parts.  Test infrastructure - never imported by the product.
 
 Strand of a read: record [0] of the oracle's polish_trace(aln=True) with iters = 1 (the polisher's shared-minimizer rule).  Alignment columns: ongsid_i_ed_ops, an external
-symbol of libngsid_oracle.so, through ctypes (0 '=', 1 'X', 2 'I' read only, 3 'D' centre only, forward order, the free centre ends as 'D').  Counting: numpy, here."""
+symbol of libngsid_oracle.so, through ctypes (0 '=', 1 'X', 2 'I' read only, 3 'D' centre only, forward order, the free centre ends as 'D').  Counting: numpy, here.
+With source=columns_reference (tests/columns_reference.py) strands and columns come from the independent anchors instead, and no oracle is needed."""
 import ctypes as C
 import numpy as np
 from ngspeciesid_amd._capi import ReadSet, polish_params
@@ -28,9 +29,18 @@ def strands(oracle, centres, rs, grp_off, read_order, k, w):
     return np.asarray(aln)[0][:, 0].astype(np.int8)
 
 
-def count_read(oracle, cnt, read, centre, clip):
+def columns(oracle, source, read, centre):
+    """the column list of one oriented read: the oracle's (source None), or source.ed_ops(read, centre) - tests/columns_reference.py, which needs no oracle"""
+    return ed_ops(oracle, read, centre) if source is None else source.ed_ops(read, centre)
+
+
+def strand_list(oracle, source, centres, rs, grp_off, read_order, k, w):
+    return strands(oracle, centres, rs, grp_off, read_order, k, w) if source is None else source.strands(centres, rs, grp_off, read_order, k, w)
+
+
+def count_read(oracle, cnt, read, centre, clip, source=None):
     """adds the counted columns of one oriented read to cnt [len(centre), 8]; -> True when the read counted at least one column"""
-    ops = ed_ops(oracle, read, centre)
+    ops = columns(oracle, source, read, centre)
     if clip:
         eq = np.concatenate(([0], (ops == 0).astype(np.int8), [0])); d = np.diff(eq)
         beg = np.nonzero(d == 1)[0]; end = np.nonzero(d == -1)[0] - 1          # runs of '=' columns [beg, end]
@@ -55,22 +65,23 @@ def count_read(oracle, cnt, read, centre, clip):
     return True
 
 
-def _part(oracle, centre_str, rs, reads, k, w, clip):
+def _part(oracle, centre_str, rs, reads, k, w, clip, source=None):
     """strands and counters of the listed reads `reads` (one group) against one centre"""
-    st = strands(oracle, [centre_str], rs, np.array([0, len(reads)], dtype=np.uint64), reads, k, w)
+    st = strand_list(oracle, source, [centre_str], rs, np.array([0, len(reads)], dtype=np.uint64), reads, k, w)
     centre = np.frombuffer(centre_str.encode(), dtype=np.uint8); cnt = np.zeros((len(centre), 8), dtype=np.uint32); used = 0
     off = rs.off
     for x, r in enumerate(reads.tolist()):
         if st[x] < 0: continue
         read = rs.seq[int(off[r]):int(off[r + 1])]
         if st[x] == 1: read = _COMP[read[::-1]]
-        used += count_read(oracle, cnt, np.ascontiguousarray(read), centre, clip)
+        used += count_read(oracle, cnt, np.ascontiguousarray(read), centre, clip, source)
     return st, cnt, used
 
 
-def support_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, threads=16, chunk=128):
+def support_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20, clip=False, threads=16, chunk=128, source=None):
     """-> (counts [total, 8] uint32, cen_off, n_used, strand) as Api.consensus_support returns them.  A read's strand and columns depend on its own centre only, so the listed
-    reads are dealt to host threads in chunks (the oracle's C code runs outside the interpreter lock) and the counters summed."""
+    reads are dealt to host threads in chunks (the oracle's C code runs outside the interpreter lock) and the counters summed.  source: where strands and columns come from -
+    None: the oracle; tests/columns_reference.py: the independent anchor (oracle may then be None)."""
     from concurrent.futures import ThreadPoolExecutor
     grp_off = np.asarray(grp_off, dtype=np.uint64); ng = len(grp_off) - 1; nl = int(grp_off[-1])
     ro = np.arange(nl, dtype=np.uint32) if read_order is None else np.ascontiguousarray(read_order, dtype=np.uint32)
@@ -78,7 +89,7 @@ def support_reference(oracle, centres, rs, grp_off, read_order=None, k=13, w=20,
     counts = np.zeros((int(cen_off[-1]), 8), dtype=np.uint32); used = np.zeros(ng, dtype=np.uint64); strand = np.full(nl, -1, dtype=np.int8)
     tasks = [(g, a, min(a + chunk, int(grp_off[g + 1]))) for g in range(ng) for a in range(int(grp_off[g]), int(grp_off[g + 1]), chunk)]
     with ThreadPoolExecutor(max_workers=threads) as ex:
-        parts = list(ex.map(lambda t: _part(oracle, centres[t[0]], rs, ro[t[1]:t[2]].copy(), k, w, clip), tasks))
+        parts = list(ex.map(lambda t: _part(oracle, centres[t[0]], rs, ro[t[1]:t[2]].copy(), k, w, clip, source), tasks))
     for (g, a, b), (st, cnt, u) in zip(tasks, parts):
         strand[a:b] = st; counts[int(cen_off[g]):int(cen_off[g + 1])] += cnt; used[g] += u
     return counts, cen_off, used, strand
